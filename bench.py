@@ -11,11 +11,20 @@ all-gathered over RCCL (the only exchange the path has).
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line (contract in the task description) with `roofline` (dominant kernel = the
-implicit-GEMM conv kernel, MFMA-bound; achieved = algorithmic conv FLOPs per launch / HIP-event duration of
-those launches inside the timed region) and, at N = 1, `cpu_baseline` (the oracle port timed on the host cores) and
-`parity_mode` (the same workload in dtype f16x3, the arithmetic that meets the 1e-4 clause: its own timed steps after the
-headline's timed region, with its agreement against the fp32 oracle).
+Rank 0 prints ONE JSON line: `metric`, `value` (images/s over the timed steps), `unit`, `higher_is_better`, `dtype`,
+`ms_per_step` (milliseconds of one timed step) and the configuration.  A plain run does nothing else: set up, warm up, time
+exactly `--steps` steps, write the outputs when `--dump-outputs DIR` is given, print the line.
+
+`--full` adds everything else the benchmark measures or checks, after the timed region: `roofline` (dominant kernel = the
+implicit-GEMM conv kernel, MFMA-bound; achieved = algorithmic conv FLOPs per launch / HIP-event duration of those launches
+inside the timed region, which then carries HIP events on PROFILED_STEPS steps), the per-kernel solo steps, the `sustained`
+leg, `--layers`, under torch.distributed.run the gather check / `ranks_seen` / `per_rank_images_per_s` / `gather_ms`, and at
+N = 1 `cpu_baseline` (the oracle port timed on the host cores) and `parity_mode` (the same workload in dtype f16x3, the
+arithmetic that meets the 1e-4 clause: its own timed steps after the headline's timed region, with its agreement against the
+fp32 oracle).
+
+`--dump-outputs DIR` writes what the timed path returned in its last timed step (rank 0's detections: classes, scores,
+bboxes, anchor_index, count) as DIR/<field>.npy; weights and images are seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -45,8 +54,13 @@ SUSTAINED_WINDOW = 100         # steps per window of the sustained leg
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
-    ap.add_argument('--steps', type=int, default=20)
-    ap.add_argument('--warmup', type=int, default=5)
+    ap.add_argument('--steps', type=int, default=20, help='timed steps')
+    ap.add_argument('--warmup', type=int, default=5, help='untimed steps before them')
+    ap.add_argument('--full', action='store_true',
+                    help='also run every other measurement and check after the timed region (roofline with per-launch HIP events, solo '
+                         'per-kernel steps, sustained leg, cpu_baseline, parity_mode, gather check); a plain run only times the steps')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write the detections of the last timed step as DIR/<field>.npy (float32 / float64)')
     ap.add_argument('--batch', type=int, default=32, help='images per GPU per step (BASELINE config 2: 32)')
     ap.add_argument('--variant', default='full', choices=['full', 'reducedfc', 'ssd512'],
                     help="full = BASELINE configs 2/3 (default); reducedfc = config 4; ssd512 = config 5")
@@ -77,12 +91,33 @@ def parse():
                     help='host flow control of the pipeline (DetectPipeline.max_queued): submit() waits while that many submitted batches '
                          'have not finished on the GPU; 0 = unbounded (the host enqueues as fast as it can: 1.3 %% slower over the timed '
                          'region, window-to-window dips of 10 %% in the sustained leg)')
-    ap.add_argument('--layers', default='', help='write the per-launch timing table to this file')
-    ap.add_argument('--check-gather', action='store_true', default=True,
-                    help='under torch.distributed.run (default on): after the timed region every rank compares the all-gathered '
+    ap.add_argument('--layers', default='', help='with --full: write the per-launch timing table to this file')
+    ap.add_argument('--check-gather', action='store_true', default=None,
+                    help='under torch.distributed.run (default on with --full): after the timed region every rank compares the all-gathered '
                          'records with its own local ones and checks every rank\'s counts; the JSON line gets "gather_check"')
     ap.add_argument('--no-check-gather', dest='check_gather', action='store_false')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    if args.layers and not args.full:
+        ap.error('--layers needs --full (the table comes from the profiled steps)')
+    if args.check_gather is None:
+        args.check_gather = args.full
+    return args
+
+
+def dump_outputs(det, directory):
+    """What the timed path handed its caller in its last step (DetectionBuffers of one batch) -> directory/<field>.npy.  Rows at or
+    behind an image's `count` are not part of the result and are written as zeros; the integer fields (classes, anchor_index, count)
+    as float64, which holds every int32 exactly; scores and bboxes as the float32 the path computed."""
+    os.makedirs(directory, exist_ok=True)
+    count = det.count.cpu().numpy()
+    valid = np.arange(det.capacity)[None, :] < count[:, None]
+    for name in det.FIELDS:
+        a = getattr(det, name).cpu().numpy()
+        if name != 'count':
+            a = np.where(valid.reshape(valid.shape + (1,) * (a.ndim - 2)), a, 0).astype(a.dtype)
+        np.save(os.path.join(directory, name + '.npy'), a if a.dtype == np.float32 else a.astype(np.float64))
 
 
 def physical_cores():
@@ -358,23 +393,28 @@ def main():
     lib = _lib.lib()
     contexts = [slot._context() for slot in pipe.slots]
 
-    def before_timed():
-        # HIP events around every launch for PROFILED_STEPS of each slot's timed steps (each event costs ~3 us of host +
-        # queue time, so not on all of them)
-        for ctx in contexts:
-            _lib.check(lib.ron_profile_reset(ctx))
-            _lib.check(lib.ron_profile_enable(ctx, min(PROFILED_STEPS, args.steps)))
+    before_timed = after_timed = None
+    if args.full:
+        def before_timed():
+            # HIP events around every launch for PROFILED_STEPS of each slot's timed steps (each event costs ~3 us of host +
+            # queue time, so not on all of them)
+            for ctx in contexts:
+                _lib.check(lib.ron_profile_reset(ctx))
+                _lib.check(lib.ron_profile_enable(ctx, min(PROFILED_STEPS, args.steps)))
 
-    def after_timed(_det):
-        for ctx in contexts:
-            _lib.check(lib.ron_profile_enable(ctx, 0))
+        def after_timed(_det):
+            for ctx in contexts:
+                _lib.check(lib.ron_profile_enable(ctx, 0))
 
     res = parallel.bench_loop(pipe, images, args.steps, args.warmup, in_flight, detect_args, top_k, rank=rank, world=world,
                               use_dist=use_dist, device=dev, check_gather=args.check_gather, consumer_stream=io_stream,
-                              before_timed=before_timed, after_timed=after_timed)
+                              before_timed=before_timed, after_timed=after_timed, measure_gather=args.full)
     dt, det, gather_check = res['dt'], res['det'], res['gather_check']
+    if args.dump_outputs and rank == 0:
+        # before anything else is submitted: the pipeline hands this output set to a later batch
+        dump_outputs(det, args.dump_outputs)
     ranks_seen = None
-    if use_dist:
+    if use_dist and args.full:
         # who took part: the process group's size and the distinct GPUs behind its ranks (one process per GPU: they must be equal)
         mine = {'rank': rank, 'local_rank': local_rank, 'device': torch.cuda.current_device(),
                 'uuid': str(getattr(torch.cuda.get_device_properties(dev), 'uuid', 'cuda:%d' % local_rank)), 'image_seed': lay['image_seed']}
@@ -402,55 +442,56 @@ def main():
             rows.append(row)
         return rows
 
-    rows = collect_rows(contexts)
+    if args.full:
+        rows = collect_rows(contexts)
 
-    # ---- the per-kernel view: PROFILED_STEPS more steps AFTER the timed region, one launch at a time (slot 0 only, nothing
-    # else in flight), so that a launch's HIP-event duration is that kernel's alone
-    solo_rows = rows
-    if in_flight > 1:
-        _lib.check(lib.ron_profile_reset(contexts[0]))
-        _lib.check(lib.ron_profile_enable(contexts[0], PROFILED_STEPS))
-        for _ in range(PROFILED_STEPS):
-            pipe.slots[0].detect(images, top_k=top_k, **detect_args)
-        torch.cuda.synchronize()
-        _lib.check(lib.ron_profile_enable(contexts[0], 0))
-        solo_rows = collect_rows(contexts[:1])
-    # ---- the sustained leg: the same loop for >= --sustained-seconds, behind the timed region and the per-kernel steps (every rank takes
-    # part; with a process group the gather stays in the loop).  It comes AFTER the solo steps: three seconds of two batches in flight leave the
-    # chip in the power state of that load, and solo steps taken right behind them read 10 % slower than the same steps behind a 75 ms
-    # burst (per-kernel 0.465 vs 0.514 of peak, round 6)
-    sustained = None
-    if args.sustained_seconds > 0:
-        sustained = sustained_leg(pipe, images, dt / args.steps * 1e3, args.sustained_seconds, in_flight, detect_args, top_k,
-                                  world * args.batch, world * args.batch * args.steps / dt, rank=rank, world=world,
-                                  use_dist=use_dist, device=dev, consumer_stream=io_stream)
-    solo_conv = [r for r in solo_rows if r['is_conv'] and r['launches'] > 0]
-    solo_ms = sum(r['total_ms'] for r in solo_conv)
-    solo_flop = sum(r['gflop_per_image'] * 1e9 * args.batch * r['launches'] for r in solo_conv)
-    solo_launches = sum(r['launches'] for r in solo_conv)
-    per_kernel_tflops = solo_flop / (solo_ms * 1e-3) / 1e12 if solo_ms > 0 else 0.0
-    conv = [r for r in rows if r['is_conv'] and r['launches'] > 0]
-    conv_ms = sum(r['total_ms'] for r in conv)
-    conv_launches = sum(r['launches'] for r in conv)
-    conv_flop = sum(r['gflop_per_image'] * 1e9 * args.batch * r['launches'] for r in conv)
-    profiled_steps = max((r['launches'] for r in conv), default=0)
-    conv_gflop_per_image = sum(r['gflop_per_image'] for r in rows if r['is_conv'])
-    per_launch_tflops = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
-    if in_flight == 1:
-        # one launch at a time: algorithmic FLOPs per launch / that kernel's average launch duration
-        achieved = per_launch_tflops
-        basis = 'conv FLOPs per launch / HIP-event duration of the launch (launches do not overlap)'
-    else:
-        # launches of different slots share the GPU, so a launch's duration is no longer the kernel's alone (and the
-        # durations of a step add up to more than the step): charge the conv kernel with the WHOLE timed region instead
-        achieved = conv_gflop_per_image * 1e9 * args.batch * args.steps / dt / 1e12
-        basis = ('%d batches in flight: conv FLOPs of the timed region / timed wall time (the other kernels\' time is charged to '
-                 'the conv kernel too); per-launch durations overlap, see concurrency' % in_flight)
-    algo_bytes = sum(r['bytes_per_launch'] * r['launches'] for r in conv) / max(conv_launches, 1)
-    traffic, traffic_source = load_traffic(args)
-    mfma_busy, mfma_busy_source = load_mfma_busy(args)
-    k_loop_clock, k_loop_clock_source = load_kloop_clock(args, in_flight)
-    peak = {'bf16': PEAK_BF16_TFLOPS, 'fp16': PEAK_F16_TFLOPS, 'fp32': PEAK_F32_TFLOPS, 'f16x3': PEAK_F16X3_TFLOPS}[args.dtype]
+        # ---- the per-kernel view: PROFILED_STEPS more steps AFTER the timed region, one launch at a time (slot 0 only, nothing
+        # else in flight), so that a launch's HIP-event duration is that kernel's alone
+        solo_rows = rows
+        if in_flight > 1:
+            _lib.check(lib.ron_profile_reset(contexts[0]))
+            _lib.check(lib.ron_profile_enable(contexts[0], PROFILED_STEPS))
+            for _ in range(PROFILED_STEPS):
+                pipe.slots[0].detect(images, top_k=top_k, **detect_args)
+            torch.cuda.synchronize()
+            _lib.check(lib.ron_profile_enable(contexts[0], 0))
+            solo_rows = collect_rows(contexts[:1])
+        # ---- the sustained leg: the same loop for >= --sustained-seconds, behind the timed region and the per-kernel steps (every rank takes
+        # part; with a process group the gather stays in the loop).  It comes AFTER the solo steps: three seconds of two batches in flight leave the
+        # chip in the power state of that load, and solo steps taken right behind them read 10 % slower than the same steps behind a 75 ms
+        # burst (per-kernel 0.465 vs 0.514 of peak, round 6)
+        sustained = None
+        if args.sustained_seconds > 0:
+            sustained = sustained_leg(pipe, images, dt / args.steps * 1e3, args.sustained_seconds, in_flight, detect_args, top_k,
+                                      world * args.batch, world * args.batch * args.steps / dt, rank=rank, world=world,
+                                      use_dist=use_dist, device=dev, consumer_stream=io_stream)
+        solo_conv = [r for r in solo_rows if r['is_conv'] and r['launches'] > 0]
+        solo_ms = sum(r['total_ms'] for r in solo_conv)
+        solo_flop = sum(r['gflop_per_image'] * 1e9 * args.batch * r['launches'] for r in solo_conv)
+        solo_launches = sum(r['launches'] for r in solo_conv)
+        per_kernel_tflops = solo_flop / (solo_ms * 1e-3) / 1e12 if solo_ms > 0 else 0.0
+        conv = [r for r in rows if r['is_conv'] and r['launches'] > 0]
+        conv_ms = sum(r['total_ms'] for r in conv)
+        conv_launches = sum(r['launches'] for r in conv)
+        conv_flop = sum(r['gflop_per_image'] * 1e9 * args.batch * r['launches'] for r in conv)
+        profiled_steps = max((r['launches'] for r in conv), default=0)
+        conv_gflop_per_image = sum(r['gflop_per_image'] for r in rows if r['is_conv'])
+        per_launch_tflops = conv_flop / (conv_ms * 1e-3) / 1e12 if conv_ms > 0 else 0.0
+        if in_flight == 1:
+            # one launch at a time: algorithmic FLOPs per launch / that kernel's average launch duration
+            achieved = per_launch_tflops
+            basis = 'conv FLOPs per launch / HIP-event duration of the launch (launches do not overlap)'
+        else:
+            # launches of different slots share the GPU, so a launch's duration is no longer the kernel's alone (and the
+            # durations of a step add up to more than the step): charge the conv kernel with the WHOLE timed region instead
+            achieved = conv_gflop_per_image * 1e9 * args.batch * args.steps / dt / 1e12
+            basis = ('%d batches in flight: conv FLOPs of the timed region / timed wall time (the other kernels\' time is charged to '
+                     'the conv kernel too); per-launch durations overlap, see concurrency' % in_flight)
+        algo_bytes = sum(r['bytes_per_launch'] * r['launches'] for r in conv) / max(conv_launches, 1)
+        traffic, traffic_source = load_traffic(args)
+        mfma_busy, mfma_busy_source = load_mfma_busy(args)
+        k_loop_clock, k_loop_clock_source = load_kloop_clock(args, in_flight)
+        peak = {'bf16': PEAK_BF16_TFLOPS, 'fp16': PEAK_F16_TFLOPS, 'fp32': PEAK_F32_TFLOPS, 'f16x3': PEAK_F16X3_TFLOPS}[args.dtype]
 
     if rank == 0:
         total_images = world * args.batch * args.steps
@@ -477,35 +518,36 @@ def main():
                        'gflop_per_image': net.flops_per_image() / 1e9,
                        'conv_stack_tflops_per_gpu': net.flops_per_image() * args.batch * args.steps / dt / 1e12,
                        'mean_detections_per_image': float(det.count.float().mean().item())},
-            'roofline': {'bound': 'mfma', 'kernel': 'conv kernels: conv_igemm_kernel (+ its grouped form conv_igemm_group_kernel), conv3x3_patch_kernel and conv3x3_c64_kernel', 'achieved': achieved, 'peak': peak,
-                         'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': traffic, 'traffic_source': traffic_source,
-                         'mfma_busy': mfma_busy, 'mfma_busy_source': mfma_busy_source,
-                         'k_loop_clock': k_loop_clock, 'k_loop_clock_source': k_loop_clock_source,
-                         'basis': basis,
-                         # the per-kernel definition: conv FLOPs per launch / that launch's own duration, one launch at a
-                         # time (3 steps after the timed region when several batches were in flight during it)
-                         'per_kernel_tflops': per_kernel_tflops, 'per_kernel_frac': per_kernel_tflops / peak,
-                         'per_kernel_avg_launch_us': solo_ms / max(solo_launches, 1) * 1e3,
-                         'per_launch_tflops': per_launch_tflops,
-                         'concurrency': conv_ms / max(profiled_steps, 1) / (dt / args.steps * 1e3) if in_flight > 1 else 1.0,
-                         'algorithmic_bytes_per_launch': algo_bytes,
-                         'avg_launch_us': conv_ms / max(conv_launches, 1) * 1e3,
-                         'launches_per_step': conv_launches // max(profiled_steps, 1),
-                         'profiled_steps': profiled_steps,
-                         'kernel_time_share': conv_ms / max(profiled_steps, 1) / (dt / args.steps * 1e3)},
         }
+        out['weights'] = {'synthesis_s': weights_s, 'how': weights_how + (' (shared through /dev/shm by local rank 0)' if use_dist and world > 1 else '')}
+        if gather_check is not None:
+            out['gather_check'] = gather_check
+    if args.full and rank == 0:
+        out['roofline'] = {'bound': 'mfma', 'kernel': 'conv kernels: conv_igemm_kernel (+ its grouped form conv_igemm_group_kernel), conv3x3_patch_kernel and conv3x3_c64_kernel', 'achieved': achieved, 'peak': peak,
+                           'unit': 'TFLOP/s', 'frac': achieved / peak, 'traffic': traffic, 'traffic_source': traffic_source,
+                           'mfma_busy': mfma_busy, 'mfma_busy_source': mfma_busy_source,
+                           'k_loop_clock': k_loop_clock, 'k_loop_clock_source': k_loop_clock_source,
+                           'basis': basis,
+                           # the per-kernel definition: conv FLOPs per launch / that launch's own duration, one launch at a
+                           # time (3 steps after the timed region when several batches were in flight during it)
+                           'per_kernel_tflops': per_kernel_tflops, 'per_kernel_frac': per_kernel_tflops / peak,
+                           'per_kernel_avg_launch_us': solo_ms / max(solo_launches, 1) * 1e3,
+                           'per_launch_tflops': per_launch_tflops,
+                           'concurrency': conv_ms / max(profiled_steps, 1) / (dt / args.steps * 1e3) if in_flight > 1 else 1.0,
+                           'algorithmic_bytes_per_launch': algo_bytes,
+                           'avg_launch_us': conv_ms / max(conv_launches, 1) * 1e3,
+                           'launches_per_step': conv_launches // max(profiled_steps, 1),
+                           'profiled_steps': profiled_steps,
+                           'kernel_time_share': conv_ms / max(profiled_steps, 1) / (dt / args.steps * 1e3)}
         if sustained is not None:
             sustained['conv_stack_tflops_per_gpu'] = net.flops_per_image() * sustained['images_per_s'] / world / 1e12
             sustained['roofline_frac'] = sustained['conv_stack_tflops_per_gpu'] / peak
             out['sustained'] = sustained
-        if gather_check is not None:
-            out['gather_check'] = gather_check
         if use_dist:
             per_rank = [args.batch * args.steps / t for t in res['rank_dt']]
             out['ranks_seen'] = ranks_seen
             out['per_rank_images_per_s'] = {'min': min(per_rank), 'max': max(per_rank)}
             out['gather_ms'] = res['gather_ms']
-        out['weights'] = {'synthesis_s': weights_s, 'how': weights_how + (' (shared through /dev/shm by local rank 0)' if use_dist and world > 1 else '')}
         if world == 1 and not args.no_cpu_baseline:
             from ron_tensorflow_amd.metrics import detection_agreement
             n1 = max(1, min(args.cpu_images, args.batch))
@@ -537,6 +579,7 @@ def main():
                     us = r['total_ms'] / r['launches'] * 1e3
                     tf = r['gflop_per_image'] * args.batch / (us * 1e-6) / 1e3 if us > 0 else 0
                     f.write('%-28s %9.3f %10.1f %9.1f %9.2f\n' % (r['name'], r['gflop_per_image'], us, tf, 100 * r['total_ms'] / tot))
+    if rank == 0:
         print(json.dumps(out))
     if use_dist:
         dist.destroy_process_group()

@@ -5,7 +5,7 @@
 set -u
 export GPU_MAX_HW_QUEUES=8
 OUT=$1; shift
-python3 bench.py --no-cpu-baseline --no-parity-mode --sustained-seconds 8 "$@" > $OUT.bench.json 2> /dev/null &
+python3 bench.py --full --no-cpu-baseline --no-parity-mode --sustained-seconds 8 "$@" > $OUT.bench.json 2> /dev/null &
 BP=$!
 : > $OUT
 while kill -0 $BP 2>/dev/null; do
