@@ -374,6 +374,18 @@ int ron_end_point_copy(ron_ctx* ctx, const char* name, int n, float* d_out, void
 int ron_detect(ron_ctx* ctx, const float* d_images, int n, const ron_post_cfg* cfg,
                ron_detections* out, void* stream);
 
+/* Fused: forward + TF-evaluation post-processing (what eval_ron_network.py:209-236 runs: net -> bboxes_decode -> objectness
+ * gate -> detected_bboxes), one enqueue, the results of ron_forward followed by ron_post_tfe on raw heads bit for bit.
+ *   scores [n, C-1, keep_top_k], bboxes [n, C-1, keep_top_k, 4]: device fp32, caller-owned, the layout ron_post_tfe writes.
+ * cfg is checked as ron_post_tfe checks it, before anything is enqueued; cfg->input_flags is ignored (the context's raw heads go
+ * in).  The objectness gate applies when the network has objectness heads (RON), not for SSD-512.  Runs in the post-processing
+ * workspace ron_detect uses (no allocation); ron_detect and ron_detect_tfe may alternate on one context in any order and with
+ * any n, on one stream as ron_detect's calls.  Its lists' counters clean themselves like ron_detect's; the first ron_detect_tfe
+ * after a ron_detect zeroes them once (a memset of (C-1) ints per image of max_batch) because ron_detect's keys share their
+ * bytes.  Profiling: the post stage is the last ron_profile_get index, as for ron_detect. */
+int ron_detect_tfe(ron_ctx* ctx, const float* d_images, int n, const ron_tfe_cfg* cfg,
+                   float* scores, float* bboxes, void* stream);
+
 /* Algorithmic work of one image through the conv stack (2*MAC of conv + deconv). */
 double ron_flops_per_image(const ron_ctx* ctx);
 

@@ -126,6 +126,7 @@ SIGNATURES = {
     'ron_end_point_shape': (C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_int64)]),
     'ron_end_point_copy': (C.c_int, [_P, C.c_char_p, C.c_int, _P, _P]),
     'ron_detect': (C.c_int, [_P, _P, C.c_int, C.POINTER(PostCfg), C.POINTER(Detections), _P]),
+    'ron_detect_tfe': (C.c_int, [_P, _P, C.c_int, C.POINTER(TfeCfg), _P, _P, _P]),
     'ron_flops_per_image': (C.c_double, [_P]),
     'ron_profile_enable': (C.c_int, [_P, C.c_int]),
     'ron_num_grouped_launches': (C.c_int, [_P]),

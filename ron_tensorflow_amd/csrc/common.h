@@ -77,6 +77,14 @@ struct PerDeviceOnce {
 // ron_post_np leaves them zero (topk_nms_kernel cleans up after itself) - set by ron_detect for its context-owned workspace only
 constexpr unsigned kPostWsClean = 0x40000000u;
 
+// ron_tfe_cfg checks of ron_post_tfe (postproc.hip): RON_OK or RON_ERR_INVALID with the message set
+int tfe_cfg_check(const ron_tfe_cfg* cfg);
+// ron_detect_tfe's post stage (postproc.hip): the TF-evaluation lists of the context's raw heads (`heads`, n images) in the
+// context's ron_post_np workspace (sized for max_batch), behind the np counters, its own counters laid out for max_batch and
+// self-cleaning; zero_counters: they may hold something else (ron_detect wrote keys there since) and are zeroed first.
+int post_tfe_ctx(const ron_heads* heads, int n, int max_batch, const ron_tfe_cfg* cfg, void* workspace, int64_t workspace_bytes,
+                 bool zero_counters, float* scores, float* bboxes, hipStream_t stream);
+
 // class ids the post-processing kernels group and encode (a power of two: label masks, anchor * kMaxClasses + label keys)
 constexpr int kMaxClasses = RON_MAX_CLASSES;
 static_assert((kMaxClasses & (kMaxClasses - 1)) == 0, "kMaxClasses must be a power of two");

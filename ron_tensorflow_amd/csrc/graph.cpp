@@ -118,7 +118,8 @@ struct ron_ctx {
   float* d_head[3][RON_MAX_LAYERS] = {};
   void* d_post_ws = nullptr;
   int64_t post_ws_bytes = 0;
-  bool post_ws_dirty = false;     // a ron_detect call failed after its select pass may have run: the self-cleaning counters are re-zeroed on the next call
+  bool post_ws_dirty = false;     // a ron_detect / ron_detect_tfe call failed after its select pass may have run: the self-cleaning counters are re-zeroed on the next call
+  bool tfe_counters_stale = false;  // ron_detect ran since the last ron_detect_tfe: its keys may sit on the TF counters (postproc.hip, post_tfe_ctx)
   void* d_stem_w = nullptr;             // conv1_1 fragments + bias for the dedicated stem kernel (bf16 / f16)
   float* d_stem_b = nullptr;
   float stem_oscale = 1.f;              // split precision: 2^-k of the stem weights' scale
@@ -1384,27 +1385,25 @@ extern "C" int ron_end_point_copy(ron_ctx* c, const char* name, int n, float* d_
   return launch_unpack(c->view(idx - 1, n), c->cfg.dtype, 0, d_out, (hipStream_t)stream);
 }
 
-extern "C" int ron_detect(ron_ctx* c, const float* d_images, int n, const ron_post_cfg* cfg, ron_detections* out, void* stream) {
-  RON_REQUIRE(c && cfg && out, "NULL argument");
-  RON_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "batch %d outside [1, max_batch=%d]", n, c->cfg.max_batch);
-  const int mb = c->cfg.max_batch;
-  ron_heads hd;
-  memset(&hd, 0, sizeof(hd));
+// forward + one post-processing stage on the context's head buffers and workspace, the stage timed as the last ron_profile_get
+// index when this call is profiled.  `post` enqueues the stage on the heads; a stage that fails leaves the workspace dirty.
+template <class Post>
+static int detect_with(ron_ctx* c, const float* d_images, int n, void* stream, Post post) {
   DeviceGuard on_device(c->cfg.device);
   RON_HIP_CHECK(on_device.err);
   if (!c->finalized) { ron::set_error("ron_detect before ron_finalize_weights"); return RON_ERR_STATE; }
-  (void)mb;
+  ron_heads hd;
+  memset(&hd, 0, sizeof(hd));
   // (head buffers and workspace: slot_resources, at ron_finalize_weights / ron_clone)
   for (int i = 0; i < c->n_feat; ++i) { hd.cls[i] = c->d_head[0][i]; hd.obj[i] = c->d_head[1][i]; hd.loc[i] = c->d_head[2][i]; }
   if (c->post_ws_dirty) {
     // an earlier call failed between its select pass and the pass that zeroes the counters again: start from a clean workspace
     RON_HIP_CHECK(ron::dev_memset_async(c->d_post_ws, 0, (size_t)c->post_ws_bytes, (hipStream_t)stream));
     c->post_ws_dirty = false;
+    c->tfe_counters_stale = false;
   }
   int rc = ron_forward(c, d_images, n, &hd, stream);
   if (rc) return rc;
-  ron_post_cfg pc = *cfg;
-  pc.input_flags = ron::kPostWsClean;      // logits + raw offsets straight from the conv stack; self-cleaning workspace (common.h)
   const bool prof = !c->pending.empty() && !c->pending_ops.back().empty() && c->pending_ops.back().back() <= -1 &&
                     c->pending_ops.back().back() != -3 && c->pending_ops.back().back() != -2;   // this call was recorded
   auto post_stamp = [&](int what) -> int {
@@ -1417,8 +1416,34 @@ extern "C" int ron_detect(ron_ctx* c, const float* d_images, int n, const ron_po
     return RON_OK;
   };
   if (prof && (rc = post_stamp(-2))) return rc;
-  rc = ron_post_np(&hd, n, &pc, c->d_post_ws, c->post_ws_bytes, out, nullptr, nullptr, stream);
+  rc = post(hd);
   if (rc != RON_OK) c->post_ws_dirty = true;
   if (rc == RON_OK && prof) rc = post_stamp(-3);
   return rc;
+}
+
+extern "C" int ron_detect(ron_ctx* c, const float* d_images, int n, const ron_post_cfg* cfg, ron_detections* out, void* stream) {
+  RON_REQUIRE(c && cfg && out, "NULL argument");
+  RON_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "batch %d outside [1, max_batch=%d]", n, c->cfg.max_batch);
+  return detect_with(c, d_images, n, stream, [&](ron_heads& hd) {
+    ron_post_cfg pc = *cfg;
+    pc.input_flags = ron::kPostWsClean;      // logits + raw offsets straight from the conv stack; self-cleaning workspace (common.h)
+    c->tfe_counters_stale = true;
+    return ron_post_np(&hd, n, &pc, c->d_post_ws, c->post_ws_bytes, out, nullptr, nullptr, stream);
+  });
+}
+
+extern "C" int ron_detect_tfe(ron_ctx* c, const float* d_images, int n, const ron_tfe_cfg* cfg, float* scores, float* bboxes,
+                              void* stream) {
+  RON_REQUIRE(c && cfg && scores && bboxes, "NULL argument");
+  RON_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "batch %d outside [1, max_batch=%d]", n, c->cfg.max_batch);
+  int rc = ron::tfe_cfg_check(cfg);         // before anything is enqueued: a rejected cfg leaves the context as it was
+  if (rc != RON_OK) return rc;
+  if (!c->finalized) { ron::set_error("ron_detect_tfe before ron_finalize_weights"); return RON_ERR_STATE; }
+  return detect_with(c, d_images, n, stream, [&](ron_heads& hd) {
+    const int r = ron::post_tfe_ctx(&hd, n, c->cfg.max_batch, cfg, c->d_post_ws, c->post_ws_bytes, c->tfe_counters_stale, scores,
+                                    bboxes, (hipStream_t)stream);
+    if (r == RON_OK) c->tfe_counters_stale = false;
+    return r;
+  });
 }

@@ -891,6 +891,18 @@ int to_det_dev(const ron_detections* d, DetDev* out, int top_k, const char* what
   return RON_OK;
 }
 
+// = ron_post_np_workspace_bytes for k images of `cap` candidates each
+int64_t np_bytes_for(int64_t cap, int64_t k) {
+  return 2 * ron::align_up(k * kCountStride * 4, 256) + k * cap * 8 + k * kPartChunks * kMaxTopK * 8;
+}
+// images a self-cleaning workspace (kPostWsClean) lays its counters out for: the most it holds, not n, so that the counters stay
+// where they are for calls of any n (laid out for n, a batch of 1 wrote its keys over the counters of a later batch of 32)
+int np_clean_layout_images(int64_t cap, int n, int64_t workspace_bytes) {
+  int k = n;
+  while (np_bytes_for(cap, k + 1) <= workspace_bytes) ++k;
+  return k;
+}
+
 }  // namespace
 
 extern "C" int64_t ron_post_np_workspace_bytes(const ron_heads* heads, int n) {
@@ -898,7 +910,7 @@ extern "C" int64_t ron_post_np_workspace_bytes(const ron_heads* heads, int n) {
   if (build_heads_dev(heads, &hd, false) != RON_OK || n <= 0) return -1;
   const int64_t cap = (int64_t)hd.anchor_base[RON_MAX_LAYERS] * (heads->num_classes - 1);
   // [candidate counts][survivor counts of the partial pass][keys][survivors]
-  return 2 * ron::align_up((int64_t)n * kCountStride * 4, 256) + (int64_t)n * cap * 8 + (int64_t)n * kPartChunks * kMaxTopK * 8;
+  return np_bytes_for(cap, n);
 }
 
 extern "C" int ron_post_np(const ron_heads* heads, int n, const ron_post_cfg* cfg, void* workspace,
@@ -922,15 +934,9 @@ extern "C" int ron_post_np(const ron_heads* heads, int n, const ron_post_cfg* cf
   for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->bbox_img[i]; pc.ps[i] = cfg->prior_scaling[i]; }
   hipStream_t s = (hipStream_t)stream;
   // Layout: [counts][part_total][keys of n images][partial keys].  A self-cleaning workspace (kPostWsClean) is reused by calls of
-  // different n and must keep its counters where they are: they are laid out for the largest batch the workspace holds, not for n
-  // (laid out for n, a batch of 1 wrote its keys over the counters of a later batch of 32)
+  // different n and must keep its counters where they are (np_clean_layout_images)
   const int cap = hd.anchor_base[RON_MAX_LAYERS] * (hd.num_classes - 1);
-  auto bytes_for = [&](int64_t k) {           // = ron_post_np_workspace_bytes(heads, k)
-    return 2 * ron::align_up(k * kCountStride * 4, 256) + k * cap * 8 + k * kPartChunks * kMaxTopK * 8;
-  };
-  int n_layout = n;
-  if (cfg->input_flags & ron::kPostWsClean)
-    while (bytes_for(n_layout + 1) <= workspace_bytes) ++n_layout;
+  const int n_layout = (cfg->input_flags & ron::kPostWsClean) ? np_clean_layout_images(cap, n, workspace_bytes) : n;
   const int64_t cnt_bytes = ron::align_up((int64_t)n_layout * kCountStride * 4, 256);
   int* counts = (int*)workspace;
   int* part_total = (int*)((char*)workspace + cnt_bytes);
@@ -1150,6 +1156,8 @@ __global__ __launch_bounds__(kTopkThreads) void tfe_topk_nms_kernel(HeadsDev hd,
     lds.anchor[r] = anchor;
   }
   __syncthreads();
+  // self-cleaning counters (ron_detect_tfe's workspace): every thread took its list's count at the top and has passed barriers since
+  if ((pc.flags & ron::kPostWsClean) && tid == 0) const_cast<int*>(counts)[list] = 0;
   nms_scan(lds, n, pc.nms_thr, pc.nms_mode == 1 ? 2 : 1, pc.keep_top_k);
   float* os = out_scores + list * pc.keep_top_k;
   float* ob = out_boxes + list * pc.keep_top_k * 4;
@@ -1162,6 +1170,87 @@ __global__ __launch_bounds__(kTopkThreads) void tfe_topk_nms_kernel(HeadsDev hd,
       os[pos] = lds.score[i];
 #pragma unroll
       for (int q = 0; q < 4; ++q) ob[pos * 4 + q] = lds.box[i][q];
+    }
+  }
+}
+
+// The select of ron_detect_tfe: the context's raw heads (logits, objectness logit pairs or none, raw offsets), the scores of
+// tfe_select_kernel bit for bit, leaner:
+//   - the row's C exponentials are computed once and kept in its own LDS slots (tfe_select_kernel computes 2 C), then divided by
+//     the sum: expf(x_c - m) / s with m and s taken in softmax_last_kernel's order;
+//   - an anchor whose best class logit stays below the background's by more than -log(select_threshold) + 1e-2 selects nothing
+//     (select_kernel's bound: score_c <= exp(x_c - m)) and skips its exponentials; never for select_threshold 0;
+//   - the box of an anchor that lists something is decoded once, by all such lanes of the wave together;
+//   - one atomic per (wave, class) that has passing lanes, each lane's slot by prefix popcount of the wave's ballot (list order
+//     does not matter: keys carry the anchor index and are sorted), instead of one per (anchor, class).
+// Counters: one int per (image, class) list, zero on entry; tfe_topk_nms_kernel zeroes them again (kPostWsClean).
+__global__ __launch_bounds__(kSelectThreads) void tfe_select_raw_kernel(HeadsDev hd, TfeDev pc, u64* keys, int* counts, int cap) {
+  extern __shared__ __attribute__((aligned(16))) float stage[];
+  const int img = blockIdx.y;
+  const int tid = threadIdx.x, lane = tid & 63;
+  int layer = 0;
+#pragma unroll
+  for (int l = 1; l < RON_MAX_LAYERS; ++l)
+    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) layer = l;
+  const int C = hd.num_classes;
+  const int n_anchor_layer = hd.cells[layer] * hd.num_anchors[layer];
+  const int first = ((int)blockIdx.x - hd.block_base[layer]) * kSelectThreads;
+  const int n_here = min(kSelectThreads, n_anchor_layer - first);
+  const float* cls = hd.cls[layer] + ((size_t)img * n_anchor_layer + first) * C;
+  for (int i = tid; i < n_here * C; i += kSelectThreads) stage[i] = cls[i];
+  __syncthreads();
+  const int local = first + tid;
+  bool live = tid < n_here;
+  if (live && hd.obj[layer] != nullptr) {      // eval_ron_network.py:227-229, objness = softmax(pair)[1] as softmax_last_kernel
+    const float2 o = *reinterpret_cast<const float2*>(hd.obj[layer] + ((size_t)img * n_anchor_layer + local) * 2);
+    const float m = fmaxf(o.x, o.y);
+    const float e0 = expf(o.x - m), e1 = expf(o.y - m);
+    live = e1 / (e0 + e1) > pc.obj_thr;
+  }
+  float* row = stage + tid * C;
+  float s = 1.f;
+  if (live) {
+    float mx = row[0], mx1 = -INFINITY;
+    for (int c = 1; c < C; ++c) { mx = fmaxf(mx, row[c]); mx1 = fmaxf(mx1, row[c]); }
+    if (mx1 - mx < logf(pc.sel_thr) - 1e-2f) live = false;
+    if (live) {
+      s = 0.f;
+      for (int c = 0; c < C; ++c) {
+        const float e = expf(row[c] - mx);
+        row[c] = e;
+        s += e;
+      }
+    }
+  }
+  // an anchor with a passing class: decode, clip with repair, bboxes_filter_min (ron_vgg_320.py:222-225), all lanes of the wave
+  // at once (decoded in the class loop, lanes whose first passing class differs would wait for their loads one after another)
+  if (live) {
+    bool any = false;
+    for (int c = 1; c < C && !any; ++c) any = row[c] / s > pc.sel_thr;
+    live = any;
+  }
+  if (live) {
+    float box[4];
+    tfe_box(hd, pc, img, layer, local, box);
+    if (pc.min_size >= 0.f && !((box[3] - box[1]) > pc.min_size && (box[2] - box[0]) > pc.min_size)) live = false;
+  }
+  const u64 below = (1ull << lane) - 1ull;
+  const unsigned anchor = (unsigned)(hd.anchor_base[layer] + local);
+  const int C1 = C - 1;
+  // (every branch below that a ballot or shuffle follows is wave-uniform: the lanes stay converged)
+  if (__ballot(live) == 0ull) return;
+  for (int c = 1; c < C; ++c) {
+    const float sc = live ? row[c] / s : 0.f;
+    const bool pass = live && sc > pc.sel_thr;
+    const u64 bal = __ballot(pass);
+    if (bal == 0ull) continue;
+    const int leader = __ffsll((long long)bal) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&counts[(size_t)img * C1 + (c - 1)], __popcll(bal));
+    base = __shfl(base, leader, 64);
+    if (pass) {
+      const int pos = base + __popcll(bal & below);
+      if (pos < cap) keys[((size_t)img * C1 + (c - 1)) * cap + pos] = make_key(sc, anchor);
     }
   }
 }
@@ -1539,24 +1628,36 @@ extern "C" int64_t ron_post_tfe_workspace_bytes(const ron_heads* heads, int n) {
   return ron::align_up(lists * 4, 256) + lists * hd.anchor_base[RON_MAX_LAYERS] * 8;
 }
 
-extern "C" int ron_post_tfe(const ron_heads* heads, int n, const ron_tfe_cfg* cfg, void* workspace,
-                            int64_t workspace_bytes, float* scores, float* bboxes, void* stream) {
-  RON_REQUIRE(cfg != nullptr && n > 0 && scores != nullptr && bboxes != nullptr, "bad argument");
+int ron::tfe_cfg_check(const ron_tfe_cfg* cfg) {
+  RON_REQUIRE(cfg != nullptr, "bad argument");
   RON_REQUIRE(cfg->top_k >= 1 && cfg->top_k <= kMaxTopK, "top_k %d not in [1, %d]", cfg->top_k, kMaxTopK);
   RON_REQUIRE(cfg->keep_top_k >= 1 && cfg->keep_top_k <= cfg->top_k, "keep_top_k %d not in [1, top_k]", cfg->keep_top_k);
   RON_REQUIRE(cfg->nms_mode == 0 || cfg->nms_mode == 1, "unknown mode to use for nms.");
   RON_REQUIRE(cfg->select_threshold >= 0.f, "select_threshold must be >= 0");
+  return RON_OK;
+}
+
+static TfeDev tfe_dev(const ron_tfe_cfg* cfg, unsigned flags) {
+  TfeDev pc;
+  pc.obj_thr = cfg->objectness_thres; pc.sel_thr = cfg->select_threshold; pc.nms_thr = cfg->nms_threshold;
+  pc.top_k = cfg->top_k; pc.keep_top_k = cfg->keep_top_k; pc.nms_mode = cfg->nms_mode; pc.clip = cfg->clip;
+  pc.min_size = cfg->min_size; pc.flags = flags;
+  for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->clipping_bbox[i]; pc.ps[i] = cfg->prior_scaling[i]; }
+  return pc;
+}
+
+extern "C" int ron_post_tfe(const ron_heads* heads, int n, const ron_tfe_cfg* cfg, void* workspace,
+                            int64_t workspace_bytes, float* scores, float* bboxes, void* stream) {
+  RON_REQUIRE(cfg != nullptr && n > 0 && scores != nullptr && bboxes != nullptr, "bad argument");
+  int rc = ron::tfe_cfg_check(cfg);
+  if (rc != RON_OK) return rc;
   HeadsDev hd;
-  int rc = build_heads_dev(heads, &hd, (cfg->input_flags & RON_IN_LOC_DECODED) == 0);
+  rc = build_heads_dev(heads, &hd, (cfg->input_flags & RON_IN_LOC_DECODED) == 0);
   if (rc != RON_OK) return rc;
   const int64_t need = ron_post_tfe_workspace_bytes(heads, n);
   RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace too small: %lld < %lld",
               (long long)workspace_bytes, (long long)need);
-  TfeDev pc;
-  pc.obj_thr = cfg->objectness_thres; pc.sel_thr = cfg->select_threshold; pc.nms_thr = cfg->nms_threshold;
-  pc.top_k = cfg->top_k; pc.keep_top_k = cfg->keep_top_k; pc.nms_mode = cfg->nms_mode; pc.clip = cfg->clip;
-  pc.min_size = cfg->min_size; pc.flags = cfg->input_flags;
-  for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->clipping_bbox[i]; pc.ps[i] = cfg->prior_scaling[i]; }
+  const TfeDev pc = tfe_dev(cfg, cfg->input_flags);
   hipStream_t s = (hipStream_t)stream;
   const int C1 = hd.num_classes - 1;
   const int64_t lists = (int64_t)n * C1;
@@ -1571,6 +1672,40 @@ extern "C" int ron_post_tfe(const ron_heads* heads, int n, const ron_tfe_cfg* cf
   }
   RON_LAUNCH(tfe_select_kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys,
                      counts, cap);
+  RON_LAUNCH(tfe_topk_nms_kernel, dim3(C1, n), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, scores, bboxes);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+// ron_detect_tfe's post stage.  Workspace (the context's, sized by ron_post_np_workspace_bytes for max_batch):
+//   [np counters: untouched][TF counters: max_batch x (C-1) ints][TF keys: n x (C-1) lists x anchors]
+// The np counters keep the zeros ron_detect left there (TF keys never land on them), and the TF counters sit where ron_detect's
+// keys may land: the caller says so with zero_counters, and only then are they zeroed first.  After a TF call every TF counter is
+// zero again (tfe_topk_nms_kernel), so back-to-back calls pay no memset.
+int ron::post_tfe_ctx(const ron_heads* heads, int n, int max_batch, const ron_tfe_cfg* cfg, void* workspace, int64_t workspace_bytes,
+                      bool zero_counters, float* scores, float* bboxes, hipStream_t s) {
+  RON_REQUIRE(n >= 1 && n <= max_batch && scores != nullptr && bboxes != nullptr && workspace != nullptr, "bad argument");
+  int rc = tfe_cfg_check(cfg);
+  if (rc != RON_OK) return rc;
+  HeadsDev hd;
+  if ((rc = build_heads_dev(heads, &hd, true)) != RON_OK) return rc;
+  const int C1 = hd.num_classes - 1;
+  const int cap = hd.anchor_base[RON_MAX_LAYERS];
+  const int64_t np_cnt = 2 * ron::align_up((int64_t)np_clean_layout_images((int64_t)cap * C1, 1, workspace_bytes) * kCountStride * 4, 256);
+  const int64_t cnt_bytes = ron::align_up((int64_t)max_batch * C1 * 4, 256);
+  const int64_t need = np_cnt + cnt_bytes + (int64_t)max_batch * C1 * cap * 8;
+  RON_REQUIRE(workspace_bytes >= need, "ron_detect_tfe: workspace too small for the TF lists: %lld < %lld", (long long)workspace_bytes,
+              (long long)need);
+  int* counts = (int*)((char*)workspace + np_cnt);
+  u64* keys = (u64*)((char*)workspace + np_cnt + cnt_bytes);
+  const TfeDev pc = tfe_dev(cfg, ron::kPostWsClean);     // raw heads: logits, objectness logit pairs, offsets
+  if (zero_counters) RON_HIP_CHECK(ron::dev_memset_async(counts, 0, (size_t)cnt_bytes, s));
+  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
+  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
+    static ron::PerDeviceOnce once;
+    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&tfe_select_raw_kernel), (int)lds));
+  }
+  RON_LAUNCH(tfe_select_raw_kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys, counts, cap);
   RON_LAUNCH(tfe_topk_nms_kernel, dim3(C1, n), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, scores, bboxes);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;

@@ -42,6 +42,8 @@ def main(argv=None):
     ap.add_argument('--images', default='', help='.npy [N,320,320,3] pre-whitened float32; synthetic if empty')
     ap.add_argument('--dtype', default='bf16')
     ap.add_argument('--variant', default='reducedfc', help="what RONNet.net builds in the reference (nets/ron_vgg_320.py:144)")
+    ap.add_argument('--fused_detect', type=int, default=0,
+                    help='1: lines 209-236 as one RONNet.detect_tfe call (ron_detect_tfe), same detections; 0: the reference\'s calls')
     FLAGS = ap.parse_args(argv)
 
     # Get the RON network and its anchors.                                eval_ron_network.py:147-152
@@ -84,17 +86,24 @@ def main(argv=None):
             b_image = ssd_vgg_preprocessing.preprocess_for_eval_batch(data[i:i + FLAGS.batch_size], out_shape=ron_shape,
                                                                       resize=ssd_vgg_preprocessing.Resize.WARP_RESIZE,
                                                                       device=ron_net.device)
-        with ron_net.arg_scope(weight_decay=0.0005, is_training=False, data_format='NHWC'):                  # :204-208
-            predictions, logits, objness_pred, objness_logits, localisations, end_points = \
-                ron_net.net(b_image, is_training=False, end_points=())                                          # :209-210
-        localisations = ron_net.bboxes_decode(localisations, ron_anchors)                                      # :226
-        filtered_predictions = [(objness > FLAGS.objectness_thres).to(torch.float32) * predictions[k]
-                                for k, objness in enumerate(objness_pred)]                                      # :227-229
-        rscores, rbboxes = ron_net.detected_bboxes(filtered_predictions, localisations,
-                                                   select_threshold=FLAGS.select_threshold,
-                                                   nms_threshold=FLAGS.nms_threshold,
-                                                   clipping_bbox=[0., 0., 1., 1.],
-                                                   top_k=FLAGS.select_top_k, keep_top_k=FLAGS.keep_top_k)     # :230-236
+        if FLAGS.fused_detect:                                                                                 # :204-236, one enqueue
+            with ron_net.arg_scope(weight_decay=0.0005, is_training=False, data_format='NHWC'):
+                rscores, rbboxes = ron_net.detect_tfe(b_image, objectness_thres=FLAGS.objectness_thres,
+                                                      select_threshold=FLAGS.select_threshold,
+                                                      nms_threshold=FLAGS.nms_threshold, clipping_bbox=[0., 0., 1., 1.],
+                                                      top_k=FLAGS.select_top_k, keep_top_k=FLAGS.keep_top_k)
+        else:
+            with ron_net.arg_scope(weight_decay=0.0005, is_training=False, data_format='NHWC'):              # :204-208
+                predictions, logits, objness_pred, objness_logits, localisations, end_points = \
+                    ron_net.net(b_image, is_training=False, end_points=())                                      # :209-210
+            localisations = ron_net.bboxes_decode(localisations, ron_anchors)                                  # :226
+            filtered_predictions = [(objness > FLAGS.objectness_thres).to(torch.float32) * predictions[k]
+                                    for k, objness in enumerate(objness_pred)]                                  # :227-229
+            rscores, rbboxes = ron_net.detected_bboxes(filtered_predictions, localisations,
+                                                       select_threshold=FLAGS.select_threshold,
+                                                       nms_threshold=FLAGS.nms_threshold,
+                                                       clipping_bbox=[0., 0., 1., 1.],
+                                                       top_k=FLAGS.select_top_k, keep_top_k=FLAGS.keep_top_k)  # :230-236
         sl = slice(i, i + FLAGS.batch_size)
         num_gbboxes, tp, fp = tfe_metrics.bboxes_matching_batch(rscores.keys(), rscores, rbboxes, g_labels[sl], g_bboxes[sl],
                                                                 g_difficults[sl], matching_threshold=FLAGS.matching_threshold)  # :237-241

@@ -312,6 +312,31 @@ class RONNet(object):
         check(lib().ron_detect(self._context(), ptr(inputs), n, C.byref(cfg), C.byref(oc), current_stream()))
         return out
 
+    def detect_tfe(self, inputs, objectness_thres=0.03, select_threshold=None, nms_threshold=0.5, clipping_bbox=None, top_k=400,
+                   keep_top_k=200, nms_mode='min', out=None):
+        """forward + TF-evaluation post-processing in one enqueue (ron_detect_tfe): what the reference's driver runs as net ->
+        bboxes_decode -> objectness gate -> detected_bboxes (eval_ron_network.py:209-236), same results.  Returns the reference's
+        (dict_scores, dict_bboxes), class -> [N, keep_top_k] / [N, keep_top_k, 4], views of the dense tensors of `out` (a
+        tfe.TfeBuffers of N images and keep_top_k rows; allocated when not given)."""
+        return self._detect_tfe(inputs, objectness_thres, select_threshold, nms_threshold, clipping_bbox, top_k, keep_top_k,
+                                nms_mode, 0.03, out).as_dicts()
+
+    def _detect_tfe(self, inputs, objectness_thres, select_threshold, nms_threshold, clipping_bbox, top_k, keep_top_k, nms_mode,
+                    min_size, out):
+        from .. import tfe
+        if getattr(self, '_data_format', 'NHWC') == 'NCHW':
+            inputs = inputs.permute(0, 2, 3, 1)
+        inputs = inputs.to(self.device, torch.float32).contiguous()
+        n = inputs.shape[0]
+        cfg = tfe.tfe_cfg(objectness_thres, select_threshold, nms_threshold, clipping_bbox, top_k, keep_top_k, nms_mode, min_size,
+                          self.params.prior_scaling)
+        if out is None:
+            out = tfe.TfeBuffers(n, self.params.num_classes, keep_top_k, self.device)
+        assert out.n == n and out.keep_top_k == keep_top_k and out.num_classes == self.params.num_classes
+        check(lib().ron_detect_tfe(self._context(), ptr(inputs), n, C.byref(cfg), ptr(out.scores), ptr(out.bboxes),
+                                   current_stream()))
+        return out
+
 
 # ---------------------------------------------------------------------- the reference's function entries
 # nets_factory.networks_map / arg_scopes_map point at module-level functions (nets/nets_factory.py:34-52): ron_net builds the graph

@@ -120,6 +120,13 @@ class SSDNet(RONNet):
         return RONNet.detect(self, inputs, objectness_thres=0.0, select_threshold=select_threshold,
                              nms_threshold=nms_threshold, top_k=top_k, bbox_img=bbox_img, out=out)
 
+    def detect_tfe(self, inputs, select_threshold=None, nms_threshold=0.5, clipping_bbox=None, top_k=400, keep_top_k=200,
+                   nms_mode='min', out=None):
+        """forward + detected_bboxes in one enqueue (ron_detect_tfe), as SSDNet.detected_bboxes: no objectness gate, no size
+        filter, `clipping_bbox` accepted and ignored."""
+        return self._detect_tfe(inputs, 0.0, select_threshold, nms_threshold, None, top_k, keep_top_k, nms_mode, None,
+                                out).as_dicts()
+
 
 # ---------------------------------------------------------------------- the reference's function entries (nets_factory.networks_map)
 def ssd_net(inputs, num_classes=SSDNet.default_params.num_classes, feat_layers=SSDNet.default_params.feat_layers,

@@ -76,10 +76,16 @@ class DetectPipeline(object):
     without holding the slot's next batch back.  Reuse is safe by construction, see Ticket.
 
     Needs one hardware queue per stream: GPU_MAX_HW_QUEUES >= slots + 3, read by the HIP runtime when it initialises (the package
-    sets 8 at import; an application that touches the GPU before importing it exports the variable itself)."""
+    sets 8 at import; an application that touches the GPU before importing it exports the variable itself).
 
-    def __init__(self, net, slots=2, top_k=400, buffers_per_slot=2, max_queued=8):
+    ``post``: 'np' runs ``net.detect`` (np_methods post-processing, tickets carry ops.DetectionBuffers); 'tfe' runs
+    ``net.detect_tfe`` (TF-evaluation post-processing, tickets carry tfe.TfeBuffers of ``keep_top_k`` rows per class)."""
+
+    def __init__(self, net, slots=2, top_k=400, buffers_per_slot=2, max_queued=8, post='np', keep_top_k=200):
         assert slots >= 1 and buffers_per_slot >= 1
+        if post not in ('np', 'tfe'):
+            raise ValueError("post must be 'np' or 'tfe', not %r" % (post,))
+        self.post, self.keep_top_k = post, keep_top_k
         # max_queued: submit() blocks the HOST while that many submitted batches have not finished on the GPU (0 = never).  Nothing
         # makes a host that enqueues faster than the GPU executes stop by itself: it piles up thousands of launches and events, and the
         # runtime then stalls it in bursts - round 6, batch 32, two slots: the driver's 20 timed steps 8 440 / 8 476 images/s unbounded,
@@ -97,7 +103,11 @@ class DetectPipeline(object):
             self.streams = [torch.cuda.Stream(device=net.device) for _ in self.slots]
         self.ready = [torch.cuda.Event() for _ in self.slots]
         n_sets = len(self.slots) * buffers_per_slot
-        self.buffers = [ops.DetectionBuffers(net.max_batch, top_k, net.device) for _ in range(n_sets)]
+        if post == 'tfe':
+            from . import tfe
+            self.buffers = [tfe.TfeBuffers(net.max_batch, net.params.num_classes, keep_top_k, net.device) for _ in range(n_sets)]
+        else:
+            self.buffers = [ops.DetectionBuffers(net.max_batch, top_k, net.device) for _ in range(n_sets)]
         for b, buf in enumerate(self.buffers):
             buf.record_stream(self.streams[b % len(self.slots)])
         self._tickets = [None] * n_sets
@@ -127,7 +137,10 @@ class DetectPipeline(object):
                 ev.record(prev._consumer)
                 s.wait_event(ev)
         with torch.cuda.stream(s):
-            self.slots[i].detect(images, top_k=self.top_k, out=out, **detect_args)
+            if self.post == 'tfe':
+                self.slots[i].detect_tfe(images, top_k=self.top_k, keep_top_k=self.keep_top_k, out=out, **detect_args)
+            else:
+                self.slots[i].detect(images, top_k=self.top_k, out=out, **detect_args)
             done = torch.cuda.Event()
             done.record(s)
         t = Ticket(out, done)
