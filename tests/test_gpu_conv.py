@@ -9,6 +9,7 @@ import pytest
 torch = pytest.importorskip('torch')
 pytestmark = pytest.mark.gpu
 
+import conv_bounds as cb  # noqa: E402
 from oracle import ron_forward as orf  # noqa: E402
 
 # f16x3 = split precision (two f16 planes per value, three f16 MFMAs per product): graded like fp32
@@ -32,6 +33,16 @@ def _check(got, ref, dtype):
     scale = float(np.abs(ref).max()) + 1e-6
     err = np.abs(got - ref).max() / scale
     assert err <= OUT_EPS[dtype] * 1.5, 'max err / scale = %g' % err
+
+
+def _check_elements(got, dtype, x, w, b=None, res=None, out_dtype=None, **op):
+    """Beside _check: every element against the float64 reference under the derived per-element bound (tests/conv_bounds.py;
+    all kernel families: tests/test_gpu_conv_exact.py)."""
+    rnd = ROUND[dtype]
+    ref, S, K = cb.conv_op(rnd(x), rnd(w), b, None if res is None else rnd(res), **op)
+    top, at = cb.worst(cb.ratio(got, ref, S, K, dtype, out_dtype))
+    print('%s K=%d: largest error / bound %.3f at %s' % (dtype, K, top, at))
+    assert top <= 1.0, 'error / bound = %.3f at %s: got %r, float64 %r' % (top, at, float(got[at]), float(ref[at]))
 
 
 CONV_SHAPES = [
@@ -62,6 +73,7 @@ def test_conv2d(ops, dev, shape, dtype):
                           dtype=dtype).cpu().numpy()
     assert got.shape == ref.shape
     _check(got, ref, dtype)
+    _check_elements(got, dtype, x, wt, b, stride=stride, rate=rate)
 
 
 @pytest.mark.parametrize('dtype', ['fp32', 'bf16', 'f16x3'])
@@ -82,6 +94,7 @@ def test_taps_innermost_orders_with_stride_rate_and_large_filters(ops, dev, shap
                           splitk=1).cpu().numpy()
     assert got.shape == ref.shape
     _check(got, ref, dtype)
+    _check_elements(got, dtype, x, wt, b, stride=stride, rate=rate)
 
 
 @pytest.mark.parametrize('dtype', ['fp32', 'bf16', 'f16x3'])
@@ -168,6 +181,7 @@ def test_conv_stem_3_channels(ops, dev, dtype, hw):
     ref = np.maximum(orf.conv2d_np(rnd(x), rnd(wt)) + b, 0)
     got = ops.conv2d_nhwc(torch.from_numpy(x).to(dev), wt, b, relu=True, dtype=dtype).cpu().numpy()
     _check(got, ref, dtype)
+    _check_elements(got, dtype, x, wt, b)
 
 
 @pytest.mark.parametrize('dtype', ['fp32', 'bf16', 'fp16', 'f16x3'])
@@ -398,6 +412,7 @@ def test_weight_heavy_layer_runs_its_tiles_row_fastest(ops, dev, cfg, dtype):
     got = ops.conv2d_nhwc(xd, wt, b, relu=True, dtype=dtype, tile_cfg=cfg, splitk=1).cpu().numpy()
     _check(got, ref, dtype)
     _check(ops.conv2d_nhwc(xd, wt, b, relu=True, dtype=dtype, tile_cfg=cfg, splitk=4).cpu().numpy(), ref, dtype)
+    _check_elements(got, dtype, x, wt, b)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -624,6 +639,7 @@ def test_two_head_outputs_from_one_convolution(ops, dev, heads, cfg, splitk, dty
     assert tuple(y1.shape) == (2, 8, 8, n_cls) and tuple(y2.shape) == (2, 8, 8, n_loc)
     _check(y1.cpu().numpy(), ref[..., :n_cls], dtype)
     _check(y2.cpu().numpy(), ref[..., n_cls:], dtype)
+    _check_elements(np.concatenate([y1.cpu().numpy(), y2.cpu().numpy()], axis=3), dtype, x, wt, b, out_dtype='fp32', relu=False)
 
 
 @pytest.mark.parametrize('dtype', ['bf16', 'f16x3'])
@@ -647,3 +663,4 @@ def test_panel_tile_orders_cover_every_tile(ops, dev, case, dtype):
     ref = np.maximum(orf.conv2d_np(rnd(x), rnd(wt)) + b, 0)
     got = ops.conv2d_nhwc(torch.from_numpy(x).to(dev), wt, b, relu=True, dtype=dtype, tile_cfg=0, splitk=1, center_from=center_from).cpu().numpy()
     _check(got, ref, dtype)
+    _check_elements(got, dtype, x, wt, b)

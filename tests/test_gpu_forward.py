@@ -556,4 +556,11 @@ def test_fused_stem_vs_oracle_at_full_size(pkg, dev, weights_reduced, images, dt
         got = net.end_point(name, 2).cpu().numpy()[:1]
         assert got.shape == col[name].shape
         assert _rel_err(got, col[name]) < tol, name
+    # pool1 per element: float64 conv -> conv -> pool under the two-layer bound of tests/conv_bounds.py (both images)
+    import conv_bounds as cb
+    w = {k: np.asarray(weights_reduced['ron_320_vgg/conv1/' + k], np.float32) for k in ('conv1_1/weights', 'conv1_1/biases', 'conv1_2/weights', 'conv1_2/biases')}
+    ref, S, K, extra = cb.stem2_op(rnd(images), rnd(w['conv1_1/weights']), w['conv1_1/biases'], rnd(w['conv1_2/weights']), w['conv1_2/biases'], dtype)
+    top, at = cb.worst(cb.ratio(net.end_point('pool1', 2).cpu().numpy(), ref, S, K, dtype, extra=extra))
+    print('stem2 %s pool1: largest error / bound %.3f at %s' % (dtype, top, at))
+    assert top <= 1.0, (top, at)
     net.close()
