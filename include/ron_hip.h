@@ -50,8 +50,10 @@ typedef enum {
   RON_ERR_UNSUPPORTED = -5
 } ron_status;
 
-/* REDUCEDFC / FULL: RON-320 bodies (nets/ron_vgg_320.py:510-580 / :434-508); SSD512: nets/ssd_vgg_512.py:364-460 */
-typedef enum { RON_VARIANT_REDUCEDFC = 0, RON_VARIANT_FULL = 1, RON_VARIANT_SSD512 = 2 } ron_variant;
+/* REDUCEDFC / FULL: RON-320 bodies (nets/ron_vgg_320.py:510-580 / :434-508); SSD512: nets/ssd_vgg_512.py:364-460 (512 x 512
+ * inputs only); SSD300: nets/ssd_vgg_300.py:434-523 (300 x 300 inputs only: the maps are 300 / 150 / 75 / 38 / 19 / 10 / 5 / 3 / 1,
+ * the 2x2 pools are SAME, i.e. ceil) */
+typedef enum { RON_VARIANT_REDUCEDFC = 0, RON_VARIANT_FULL = 1, RON_VARIANT_SSD512 = 2, RON_VARIANT_SSD300 = 3 } ron_variant;
 /* Arithmetic of the conv stack (activations + weights in HBM, what the MFMAs consume); accumulation is fp32 in all of them.
  *   F32   : v_mfma_f32_16x16x4_f32, exact fp32 products (parity mode, 157 TFLOP/s matrix peak)
  *   BF16  : v_mfma_f32_16x16x32_bf16 (benchmark mode of BASELINE config 2)
@@ -342,6 +344,10 @@ typedef struct {
  * would select without the level rule (A/B tests; same results up to the order of the fp32 partial sums). */
 #define RON_CFG_LEVEL_GROUPS 32u
 #define RON_CFG_BATCH_GROUPS 64u
+/* With RON_CFG_FUSE_POOLS a pool on an ODD map (SSD-300: conv3_3 75 x 75 -> pool3 38 x 38) is fused like the others: the last row /
+ * column of windows then holds tile rows that are no pixel of the map.  This flag keeps such a pool a launch of its own (A/B tests:
+ * tools/bench_ssd300.py --ab-pool3; same results bit for bit). */
+#define RON_CFG_NO_ODD_POOL_FUSE 128u
 
 int ron_create(ron_ctx** out, const ron_config* cfg);
 int ron_destroy(ron_ctx* ctx);
@@ -400,7 +406,8 @@ double ron_flops_per_image(const ron_ctx* ctx);
 int ron_profile_enable(ron_ctx* ctx, int enable);
 int ron_profile_num_ops(const ron_ctx* ctx);
 /* Grouped launches in the plan of this context: RON-320 10 (max_batch >= 24), 7 (13..23), 6 (the level plan, <= 12 or
- * RON_CFG_LEVEL_GROUPS); SSD-512 5; 0 with RON_CFG_NO_GROUPS / RON_CFG_MULTI_STREAM. */
+ * RON_CFG_LEVEL_GROUPS); SSD-512 5; SSD-300 4 (the heads of block8 .. block11, each with the next block's 1x1 where there is one);
+ * 0 with RON_CFG_NO_GROUPS / RON_CFG_MULTI_STREAM. */
 int ron_num_grouped_launches(const ron_ctx* ctx);
 int ron_profile_get(ron_ctx* ctx, int i, const char** name, int* is_conv, double* flops_per_image,
                     double* total_ms, int* launches, double* act_bytes_per_image, double* weight_bytes);
@@ -427,13 +434,17 @@ typedef struct {
                                anything else, or one that does not cover this conv, is RON_ERR_INVALID             */
   int32_t in_cstride;       /* tooling: input laid out as a channel slice: elements per pixel (0 = cin) ...   */
   int32_t in_coff;          /* ... and first channel of the slice                                              */
-  int32_t pool;             /* fuse a 2x2 stride-2 max-pool into the epilogue: y is [n, h/2, w/2, cout]        */
+  int32_t pool;             /* fuse a 2x2 stride-2 SAME max-pool into the epilogue: y is [n, ceil(h/2), ceil(w/2), cout] */
   int32_t splitk;           /* split-K factor: -1 = by grid size, 1 = off                                      */
   int32_t center_from;      /* > 0: output channels >= center_from have weights in the centre tap only (the caller's w is
                              * zero elsewhere): their column tiles run that tap's K steps alone.  0 = none              */
 } ron_conv_desc;
 int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* bias,
                     const float* residual, float* y, void* stream);
+/* d->pool != 0 with the un-pooled map as a second output of the same launch (what the graph does for conv4_3 / conv5_3 under
+ * RON_CFG_FUSE_POOLS): y_pooled [n, ceil(h/2), ceil(w/2), cout], y_full [n, h, w, cout].  Row-gather tiles only. */
+int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* bias, float* y_pooled,
+                          float* y_full, void* stream);
 /* How ron_conv2d_nhwc would run `d`, without running it (tests, tools): out = {tile configuration (csrc/conv_mfma.h kCfg*),
  * split-K factor, tile order (0 = column tiles fastest inside an XCD's run, 1 = row tiles fastest, P >= 2 = panels of P column tiles
  * walked row by row), K order (1 = taps innermost)}.  Allocates and frees the operands like ron_conv2d_nhwc does. */
@@ -445,6 +456,8 @@ int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]);
  * ron_conv2d_nhwc. */
 int ron_conv2d_heads_nhwc(const ron_conv_desc* d, int split_first, const float* x, const float* w, const float* bias,
                           float* y_first, float* y_second, void* stream);
+/* slim.max_pool2d [2, 2] stride 2, padding SAME: y is [n, ceil(h/2), ceil(w/2), c]; the last window of an odd map holds one row /
+ * column.  ron_conv2d_nhwc with `pool` produces the same map from the convolution's accumulators. */
 int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, int dtype, float* y, void* stream);
 /* Tooling: time the conv kernel alone on random data (ms per launch, HIP events, default stream, synchronises). */
 int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, float* ms_per_launch);

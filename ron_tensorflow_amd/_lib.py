@@ -27,10 +27,11 @@ RON_CFG_NO_GROUPS = 8
 RON_CFG_NO_HALO_SKIP = 16
 RON_CFG_LEVEL_GROUPS = 32
 RON_CFG_BATCH_GROUPS = 64
+RON_CFG_NO_ODD_POOL_FUSE = 128
 
 DTYPES = {'fp32': 0, 'f32': 0, 'float32': 0, 'bf16': 1, 'bfloat16': 1, 'fp16': 2, 'f16': 2, 'float16': 2,
           'f16x3': 3, 'fp16x3': 3}     # f16x3: split precision (two f16 planes per value, 3 MFMAs per product; include/ron_hip.h)
-VARIANTS = {'reducedfc': 0, 'full': 1, 'ssd512': 2}
+VARIANTS = {'reducedfc': 0, 'full': 1, 'ssd512': 2, 'ssd300': 3}
 
 
 class RonError(RuntimeError):
@@ -135,6 +136,7 @@ SIGNATURES = {
                                   C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     'ron_profile_reset': (C.c_int, [_P]),
     'ron_conv2d_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
+    'ron_conv2d_pool2_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     'ron_conv_plan': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
     'ron_conv2d_heads_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, _P, _P]),
     'ron_maxpool2x2_nhwc': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -218,7 +218,13 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, const unsigne
     int img, oy, ox, off;
     bool valid;
     if (p.pool) {
-      const int pw = p.Wo >> 1, ph = p.Ho >> 1;
+      // SAME pool: ceil(Ho / 2) x ceil(Wo / 2) windows, M = 4 x their number (plan_conv).  On an odd map the last row / column of
+      // windows has tile rows that are no pixel of the map.  Computed where they point, such a row would be relu(bias + the taps that
+      // reach back into the map), which is not zero and can win the max; instead it gathers the window's own last row / column again
+      // (oy, ox clamped: the clamped pixel is in the same window), so the window's four registers hold its real pixels, some twice - a
+      // max does not see a duplicate, whatever the sign of the values - and the epilogue needs nothing extra.  The un-pooled second
+      // output does not store those rows.
+      const int pw = (p.Wo + 1) >> 1, ph = (p.Ho + 1) >> 1;
       int P = (m0 >> 2) + (r >> 2);                 // pooled pixel of this window
       valid = P < (p.M >> 2);
       P = valid ? P : (p.M >> 2) - 1;
@@ -227,9 +233,12 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, const unsigne
       const int py = rem / pw, px = rem - (rem / pw) * pw;
       oy = 2 * py + ((r >> 1) & 1);
       ox = 2 * px + (r & 1);
+      const bool pixel = oy < p.Ho && ox < p.Wo;
+      oy = min(oy, p.Ho - 1);
+      ox = min(ox, p.Wo - 1);
       off = ((img * p.out_Hp + py + p.out_pad) * p.out_Wp + px + p.out_pad) * p.out_cstride + p.out_coff;
       if (p.out2 != nullptr)
-        s_out2_off[r] = valid ? ((img * p.out2_Hp + oy + p.out2_pad) * p.out2_Wp + ox + p.out2_pad) * p.out2_cstride + p.out2_coff : -1;
+        s_out2_off[r] = valid && pixel ? ((img * p.out2_Hp + oy + p.out2_pad) * p.out2_Wp + ox + p.out2_pad) * p.out2_cstride + p.out2_coff : -1;
     } else {
       int m = m0 + r;
       valid = m < p.M;

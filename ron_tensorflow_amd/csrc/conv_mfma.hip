@@ -309,13 +309,15 @@ static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out) {
   if (c.up > 0) RON_REQUIRE(c.up_cout % BN == 0, "transposed conv: channels per tap %d not a multiple of %d", c.up_cout, BN);
   fill_conv_args(c, &a);
   a.tiles_n = c.Npad / BN;
-  a.tiles_total = ((M + BM - 1) / BM) * a.tiles_n;
-  a.splitk = 1; a.kt_split = a.KT; a.partial = nullptr;
   if (c.pool) {
-    RON_REQUIRE(c.up == 0 && c.res == nullptr && !c.out_f32 && c.Ho % 2 == 0 && c.Wo % 2 == 0 && c.stride == 1,
-                "conv + fused pool: plain stride-1 conv on an even map only");
-    RON_REQUIRE(c.out.H == c.Ho / 2 && c.out.W == c.Wo / 2, "conv + fused pool: output view must be the pooled map");
+    // SAME pool: tile rows are the windows' four positions, ceil(Ho / 2) x ceil(Wo / 2) windows per image (an odd map's last windows
+    // hold positions that are no pixel: conv_igemm_tile)
+    RON_REQUIRE(c.up == 0 && c.res == nullptr && !c.out_f32 && c.stride == 1, "conv + fused pool: plain stride-1 conv only");
+    RON_REQUIRE(c.out.H == (c.Ho + 1) / 2 && c.out.W == (c.Wo + 1) / 2, "conv + fused pool: output view must be the pooled map");
+    a.M = 4 * c.in.N * c.out.H * c.out.W;
   }
+  a.tiles_total = ((a.M + BM - 1) / BM) * a.tiles_n;
+  a.splitk = 1; a.kt_split = a.KT; a.partial = nullptr;
   if (c.split_n > 0) {
     RON_REQUIRE(c.out_f32 && !c.pool && c.up == 0 && c.res == nullptr && c.center_from == 0, "conv: two head outputs from a plain fp32-output convolution only");
     RON_REQUIRE(c.split_n % 8 == 0 && c.split_first > 0 && c.split_first <= c.split_n && c.split_n < c.Cout,

@@ -501,7 +501,8 @@ static int patch_args(const ConvLaunch& c, int cfg, PatchArgs* out, int* grid) {
   PatchArgs a = PatchArgs();
   fill_conv_args(c, &a.c);
   RON_REQUIRE((int64_t)c.Npad * a.c.K * esz == c.wgt_bytes, "conv: packed weight size mismatch");
-  if (c.pool) RON_REQUIRE(c.res == nullptr && !c.out_f32 && c.out.H == c.Ho / 2 && c.out.W == c.Wo / 2, "conv + fused pool: bad output view");
+  // (SAME pool: ceil, as plan_conv of conv_mfma.hip; patch_geom only tiles even maps for a fused pool, where the two agree)
+  if (c.pool) RON_REQUIRE(c.res == nullptr && !c.out_f32 && c.out.H == (c.Ho + 1) / 2 && c.out.W == (c.Wo + 1) / 2, "conv + fused pool: bad output view");
   PatchGeom g;
   patch_geom(c.in.N, c.in.H, c.in.W, c.in.pad, c.pool != 0, &g);
   a.flat = g.flat; a.TH = g.TH; a.TW = g.TW;

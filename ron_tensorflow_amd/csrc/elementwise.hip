@@ -127,7 +127,10 @@ __device__ __forceinline__ long long view_off(const ViewDev& v, long long img, i
   return ((img * v.Hp + y + v.pad) * v.Wp + x + v.pad) * v.cstride + v.coff;
 }
 
-// slim.max_pool2d [2,2] stride 2 (nets/ron_vgg_320.py:456..475); all RON maps are even so SAME == VALID.
+// slim.max_pool2d [2,2] stride 2, padding SAME (nets/ron_vgg_320.py:456..475, nets/ssd_vgg_300.py:450..462): the output is
+// ceil(H/2) x ceil(W/2).  On an even map SAME == VALID; on an odd one (SSD-300: 75 -> 38) the last window holds one row / column, and
+// the taps that do not exist re-read the window's own last row / column - a max is unchanged by a duplicate - so nothing is read
+// from the halo, the next row or the next image, whatever their contents.
 template <class T>
 __global__ void maxpool2x2_kernel(ViewDev in, ViewDev out) {
   IO<T>::mode_on();
@@ -141,12 +144,13 @@ __global__ void maxpool2x2_kernel(ViewDev in, ViewDev out) {
     const int oy = (int)((pix / out.W) % out.H);
     const long long img = pix / ((long long)out.W * out.H);
     const long long o00 = view_off(in, img, 2 * oy, 2 * ox) + g * V;
-    const long long rowstep = (long long)in.Wp * in.cstride;
+    const long long rowstep = 2 * oy + 1 < in.H ? (long long)in.Wp * in.cstride : 0;
+    const long long colstep = 2 * ox + 1 < in.W ? in.cstride : 0;
     float a[V], b[V], c[V], d[V], o[V];
     IO<T>::load(in.base, o00, a);
-    IO<T>::load(in.base, o00 + in.cstride, b);
+    IO<T>::load(in.base, o00 + colstep, b);
     IO<T>::load(in.base, o00 + rowstep, c);
-    IO<T>::load(in.base, o00 + rowstep + in.cstride, d);
+    IO<T>::load(in.base, o00 + rowstep + colstep, d);
 #pragma unroll
     for (int e = 0; e < V; ++e) o[e] = fmaxf(fmaxf(a[e], b[e]), fmaxf(c[e], d[e]));
     IO<T>::store(out.base, view_off(out, img, oy, ox) + g * V, o);
@@ -287,7 +291,7 @@ int launch_im2col_c3(const float* x, int n, int h, int w, int dtype, void* out, 
 
 int launch_maxpool2x2(const TensorView& in, const TensorView& out, int dtype, hipStream_t s) {
   const int V = vec_elems(dtype);
-  RON_REQUIRE(in.H == 2 * out.H && in.W == 2 * out.W && in.C == out.C && in.N == out.N, "maxpool: shape mismatch");
+  RON_REQUIRE((in.H + 1) / 2 == out.H && (in.W + 1) / 2 == out.W && in.C == out.C && in.N == out.N, "maxpool: shape mismatch");
   RON_REQUIRE(out.C % V == 0 && in.cstride % V == 0 && out.cstride % V == 0 && in.coff % V == 0 && out.coff % V == 0,
               "maxpool: channels must be a multiple of %d", V);
   const long long total = (long long)out.N * out.H * out.W * (out.C / V);

@@ -98,12 +98,12 @@ struct ron_ctx {
   int c6 = 0;                 // fc6 / fc7 channels
   int num_anchors = 10;                 // RON: anchors per cell on every scale
   int feat[4] = {0, 0, 0, 0};
-  // head layers, generic (RON: 4 scales x 10 anchors + objectness; SSD-512: 7 scales, 4/6 anchors, no objectness)
+  // head layers, generic (RON: 4 scales x 10 anchors + objectness; SSD-512 / SSD-300: 7 / 6 scales, 4/6 anchors, no objectness)
   int n_feat = 4;
   int feat_h[RON_MAX_LAYERS] = {}, feat_w[RON_MAX_LAYERS] = {}, feat_A[RON_MAX_LAYERS] = {};
   bool has_obj = true;
-  bool is_ssd() const { return cfg.variant == RON_VARIANT_SSD512; }
-  const char* scope() const { return is_ssd() ? "ssd_512_vgg" : "ron_320_vgg"; }
+  bool is_ssd() const { return cfg.variant == RON_VARIANT_SSD512 || cfg.variant == RON_VARIANT_SSD300; }
+  const char* scope() const { return cfg.variant == RON_VARIANT_SSD512 ? "ssd_512_vgg" : (cfg.variant == RON_VARIANT_SSD300 ? "ssd_300_vgg" : "ron_320_vgg"); }
   float* d_l2_gamma = nullptr;          // SSD block4 L2Normalization scale
   std::vector<Var> vars;
   std::map<std::string, int> var_index;
@@ -376,16 +376,54 @@ int pack_inception(ron_ctx* c, const std::string& I) {
 
 
 // ---------------------------------------------------------------------------------------------------------
-// SSD-512 (nets/ssd_vgg_512.py:364-460, multibox heads nets/ssd_vgg_300.py:403-431)
+// SSD (nets/ssd_vgg_512.py:364-460, nets/ssd_vgg_300.py:434-523; multibox heads nets/ssd_vgg_300.py:403-431): one description per
+// variant, read by declare_variables_ssd, declare_tensors_ssd, make_anchors_ssd, the op list of ron_finalize_weights and plan_groups.
 // ---------------------------------------------------------------------------------------------------------
-const char* kSsdFeat[7] = {"block4", "block7", "block8", "block9", "block10", "block11", "block12"};
-const int kSsdAnchors[7] = {4, 6, 6, 6, 6, 4, 4};       // len(sizes) + len(ratios), nets/ssd_vgg_512.py:86-99
-const int kSsdFeatC[7] = {512, 1024, 512, 256, 256, 256, 256};
-// Feature layers whose loc + cls convolutions run as one two-output launch (block4: 64 x 64, block7: 32 x 32).  The small maps'
-// heads stay two members of a grouped launch with the next block's 1x1 (plan_groups).
+constexpr int kSsdMaxFeat = 7, kSsdMaxExtra = 5;
+struct SsdExtra { int mid, outc, k, stride, cpad; };      // block8 ...: 1x1 to `mid` channels, then k x k (stride, zero padding cpad) to `outc`
+struct SsdSpec {
+  const char* scope;
+  int img;                                // the one input size of the variant (square)
+  int n_feat;
+  const char* feat[kSsdMaxFeat];          // feature layers: block4 (L2-normalised), block7 (= conv7), then the extra blocks
+  int anchors[kSsdMaxFeat];               // per cell: len(sizes) + len(ratios); 4 = ratios {2, 1/2}, 6 = {2, 1/2, 3, 1/3}
+  int feat_c[kSsdMaxFeat];
+  int n_extra;
+  SsdExtra extra[kSsdMaxExtra];           // pad2d(1) + VALID of the reference = cpad 1; plain VALID = cpad 0
+  double sizes[kSsdMaxFeat][2], steps[kSsdMaxFeat];      // SSDNet.default_params
+};
+// nets/ssd_vgg_512.py:79-102, :395-458: blocks 8-11 are 1x1 then pad 1 + 3x3 stride 2, block12 1x1 then pad 1 + 4x4
+const SsdSpec kSsd512 = {
+    "ssd_512_vgg", 512, 7,
+    {"block4", "block7", "block8", "block9", "block10", "block11", "block12"},
+    {4, 6, 6, 6, 6, 4, 4},
+    {512, 1024, 512, 256, 256, 256, 256},
+    5, {{256, 512, 3, 2, 1}, {128, 256, 3, 2, 1}, {128, 256, 3, 2, 1}, {128, 256, 3, 2, 1}, {128, 256, 4, 1, 1}},
+    {{20.48, 51.2}, {51.2, 133.12}, {133.12, 215.04}, {215.04, 296.96}, {296.96, 378.88}, {378.88, 460.8}, {460.8, 542.72}},
+    {8, 16, 32, 64, 128, 256, 512}};
+// nets/ssd_vgg_300.py:94-124, :466-503: blocks 8 / 9 are 1x1 then pad 1 + 3x3 stride 2 (19 -> 10 -> 5), blocks 10 / 11 1x1 then 3x3
+// VALID (5 -> 3 -> 1); 8732 anchors
+const SsdSpec kSsd300 = {
+    "ssd_300_vgg", 300, 6,
+    {"block4", "block7", "block8", "block9", "block10", "block11"},
+    {4, 6, 6, 6, 4, 4},
+    {512, 1024, 512, 256, 256, 256},
+    4, {{256, 512, 3, 2, 1}, {128, 256, 3, 2, 1}, {128, 256, 3, 1, 0}, {128, 256, 3, 1, 0}},
+    {{21., 45.}, {45., 99.}, {99., 153.}, {153., 207.}, {207., 261.}, {261., 315.}},
+    {8, 16, 32, 64, 100, 300}};
+const SsdSpec* ssd_spec(int variant) {
+  return variant == RON_VARIANT_SSD512 ? &kSsd512 : (variant == RON_VARIANT_SSD300 ? &kSsd300 : nullptr);
+}
+std::string ssd_extra_conv(const SsdExtra& e) { return "conv" + std::to_string(e.k) + "x" + std::to_string(e.k); }
+// slim.max_pool2d [2, 2] stride 2 SAME; a k x k convolution with stride s over a map zero-padded by p
+int pool2_out(int h) { return (h + 1) / 2; }
+int conv_out(int h, int k, int stride, int p) { return (h + 2 * p - k) / stride + 1; }
+// Feature layers whose loc + cls convolutions run as one two-output launch (block4: 64 x 64 / 38 x 38, block7: 32 x 32 / 19 x 19).
+// The small maps' heads stay two members of a grouped launch with the next block's 1x1 (plan_groups).
 const int kSsdPairedHeads = 2;
 
 void declare_variables_ssd(ron_ctx* c) {
+  const SsdSpec& S = *ssd_spec(c->cfg.variant);
   const int nc = c->cfg.num_classes;
   const int widths[5] = {64, 128, 256, 512, 512};
   const int reps[5] = {2, 2, 3, 3, 3};
@@ -401,65 +439,68 @@ void declare_variables_ssd(ron_ctx* c) {
   c->add_var("conv6/biases", {1024});
   c->add_var("conv7/weights", {1, 1, 1024, 1024});
   c->add_var("conv7/biases", {1024});
-  const int mid[5] = {256, 128, 128, 128, 128}, outc[5] = {512, 256, 256, 256, 256}, inc[5] = {1024, 512, 256, 256, 256};
-  for (int b = 0; b < 5; ++b) {
+  int inc = 1024;
+  for (int b = 0; b < S.n_extra; ++b) {
+    const SsdExtra& e = S.extra[b];
     const std::string B = "block" + std::to_string(8 + b);
-    c->add_var(B + "/conv1x1/weights", {1, 1, inc[b], mid[b]});
-    c->add_var(B + "/conv1x1/biases", {mid[b]});
-    const int k = b == 4 ? 4 : 3;
-    c->add_var(B + (b == 4 ? "/conv4x4" : "/conv3x3") + "/weights", {k, k, mid[b], outc[b]});
-    c->add_var(B + (b == 4 ? "/conv4x4" : "/conv3x3") + "/biases", {outc[b]});
+    c->add_var(B + "/conv1x1/weights", {1, 1, inc, e.mid});
+    c->add_var(B + "/conv1x1/biases", {e.mid});
+    c->add_var(B + "/" + ssd_extra_conv(e) + "/weights", {e.k, e.k, e.mid, e.outc});
+    c->add_var(B + "/" + ssd_extra_conv(e) + "/biases", {e.outc});
+    inc = e.outc;
   }
-  for (int i = 0; i < 7; ++i) {
-    const std::string L = std::string(kSsdFeat[i]) + "_box";
+  for (int i = 0; i < S.n_feat; ++i) {
+    const std::string L = std::string(S.feat[i]) + "_box";
     if (i == 0) c->add_var(L + "/L2Normalization/gamma", {512});
-    c->add_var(L + "/conv_loc/weights", {3, 3, kSsdFeatC[i], kSsdAnchors[i] * 4});
-    c->add_var(L + "/conv_loc/biases", {kSsdAnchors[i] * 4});
-    c->add_var(L + "/conv_cls/weights", {3, 3, kSsdFeatC[i], kSsdAnchors[i] * nc});
-    c->add_var(L + "/conv_cls/biases", {kSsdAnchors[i] * nc});
+    c->add_var(L + "/conv_loc/weights", {3, 3, S.feat_c[i], S.anchors[i] * 4});
+    c->add_var(L + "/conv_loc/biases", {S.anchors[i] * 4});
+    c->add_var(L + "/conv_cls/weights", {3, 3, S.feat_c[i], S.anchors[i] * nc});
+    c->add_var(L + "/conv_cls/biases", {S.anchors[i] * nc});
   }
 }
 
 void declare_tensors_ssd(ron_ctx* c) {
+  const SsdSpec& S = *ssd_spec(c->cfg.variant);
   const int H = c->cfg.img_h, W = c->cfg.img_w;
   c->add_tensor("im2col", H, W, conv_k_chunk(c->cfg.dtype), 0);
   const int widths[5] = {64, 128, 256, 512, 512};
   const int reps[5] = {2, 2, 3, 3, 3};
   int h = H, w = W;
+  int fh[kSsdMaxFeat], fw[kSsdMaxFeat];
   for (int b = 0; b < 5; ++b) {
     for (int r = 0; r < reps[b]; ++r)
       c->add_tensor("conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1), h, w, widths[b], 1);
-    if (b < 4) { h /= 2; w /= 2; }
+    if (b == 3) { fh[0] = h; fw[0] = w; }                                                     // block4 = conv4_3
+    if (b < 4) { h = pool2_out(h); w = pool2_out(w); }                                        // pool5: 3x3 stride 1
     c->add_tensor("pool" + std::to_string(b + 1), h, w, widths[b], b == 4 ? 6 : 1);   // pool5 feeds the rate-6 conv
   }
-  c->add_tensor("block4_norm", H / 8, W / 8, 512, 1);
+  c->add_tensor("block4_norm", fh[0], fw[0], 512, 1);
   c->add_tensor("conv6", h, w, 1024, 0);
   c->add_tensor("conv7", h, w, 1024, 1);
-  const int mid[5] = {256, 128, 128, 128, 128}, outc[5] = {512, 256, 256, 256, 256};
-  for (int b = 0; b < 5; ++b) {
+  fh[1] = h; fw[1] = w;
+  for (int b = 0; b < S.n_extra; ++b) {
+    const SsdExtra& e = S.extra[b];
     const std::string B = "block" + std::to_string(8 + b);
-    c->add_tensor(B + "_mid", h, w, mid[b], 1);            // pad2d(1) of the reference = the halo
-    if (b < 4) { h /= 2; w /= 2; } else { h = 1; w = 1; }
-    c->add_tensor(B, h, w, outc[b], 1);
+    c->add_tensor(B + "_mid", h, w, e.mid, 1);             // pad2d(1) of the reference = the halo (unused by the VALID blocks)
+    h = conv_out(h, e.k, e.stride, e.cpad); w = conv_out(w, e.k, e.stride, e.cpad);
+    c->add_tensor(B, h, w, e.outc, 1);
+    fh[2 + b] = h; fw[2 + b] = w;
   }
-  c->n_feat = 7;
+  c->n_feat = S.n_feat;
   c->has_obj = false;
-  const int fh[7] = {H / 8, H / 16, H / 32, H / 64, H / 128, H / 256, 1}, fw[7] = {W / 8, W / 16, W / 32, W / 64, W / 128, W / 256, 1};
-  for (int i = 0; i < 7; ++i) { c->feat_h[i] = fh[i]; c->feat_w[i] = fw[i]; c->feat_A[i] = kSsdAnchors[i]; }
+  for (int i = 0; i < S.n_feat; ++i) { c->feat_h[i] = fh[i]; c->feat_w[i] = fw[i]; c->feat_A[i] = S.anchors[i]; }
 }
 
-// SSDNet.default_params anchors (nets/ssd_vgg_512.py:79-102) with ssd_anchor_one_layer (:286-338): anchors per cell are
-// [s0 square, sqrt(s0*s1) square, s0 at each ratio]; centres as in the RON version.
+// SSDNet.default_params anchors (nets/ssd_vgg_512.py:79-102, nets/ssd_vgg_300.py:94-124) with ssd_anchor_one_layer (:286-338):
+// anchors per cell are [s0 square, sqrt(s0*s1) square, s0 at each ratio]; centres as in the RON version.
 int make_anchors_ssd(ron_ctx* c) {
+  const SsdSpec& S = *ssd_spec(c->cfg.variant);
   const int H = c->cfg.img_h, W = c->cfg.img_w;
-  const double sizes[7][2] = {{20.48, 51.2}, {51.2, 133.12}, {133.12, 215.04}, {215.04, 296.96}, {296.96, 378.88}, {378.88, 460.8}, {460.8, 542.72}};
-  const double ratios[7][4] = {{2, .5, 0, 0}, {2, .5, 3, 1. / 3}, {2, .5, 3, 1. / 3}, {2, .5, 3, 1. / 3}, {2, .5, 3, 1. / 3}, {2, .5, 0, 0}, {2, .5, 0, 0}};
-  const int n_ratios[7] = {2, 4, 4, 4, 4, 2, 2};
-  const double steps[7] = {8, 16, 32, 64, 128, 256, 512};
-  for (int i = 0; i < 7; ++i) {
+  const double ratios[4] = {2, .5, 3, 1. / 3};
+  for (int i = 0; i < S.n_feat; ++i) {
     const int fh = c->feat_h[i], fw = c->feat_w[i], A = c->feat_A[i];
     std::vector<float> y(fh * fw), x(fh * fw), hh(A), ww(A);
-    int rc = ron_ssd_anchor_one_layer(H, W, fh, fw, sizes[i], 2, ratios[i], n_ratios[i], steps[i], 0.5, y.data(), x.data(), hh.data(), ww.data());
+    int rc = ron_ssd_anchor_one_layer(H, W, fh, fw, S.sizes[i], 2, ratios, A - 2, S.steps[i], 0.5, y.data(), x.data(), hh.data(), ww.data());
     if (rc) return rc;
     const std::vector<float>* src[4] = {&y, &x, &hh, &ww};
     for (int k = 0; k < 4; ++k) {
@@ -476,23 +517,27 @@ int make_anchors_ssd(ron_ctx* c) {
 // HISTORY.md (rounds 2-3: T64 / T128 groups by dependency level) and DESIGN.md 3.2 (round 4: mixed-width groups with carriers).
 void plan_groups(ron_ctx* c) {
   if (c->cfg.flags & (RON_CFG_MULTI_STREAM | RON_CFG_NO_GROUPS)) return;
-  struct Slot { int cfg; std::vector<const char*> names; };     // cfg < 0: launches of their own
+  struct Slot { int cfg; std::vector<std::string> names; };     // cfg < 0: launches of their own
   const int T64 = kCfgIgemm128x64;     // tiny convolutions (Npad = 64)
   // SSD-512 (nets/ssd_vgg_512.py:395-458): blocks 8-12 are a chain of 1x1 -> 3x3 stride-2 convolutions on 16x16 ... 1x1 maps,
   // each a 13-20 us launch at batch 16; the two box convolutions of a block only need that block's output, so they share a
   // launch with the next block's 1x1 (20 small launches -> 11).  The block4 / block7 heads are real work and stay alone (round 4:
   // as carriers of the chain's small launches in mixed-width groups they measured -0.8 % images/s - block4_box_conv_loc then leaves
   // the halo-patch kernel: 114 us for {block8_conv1x1, block4_box_conv_loc} where the two take 40 + 45 us on their own).
-  const std::vector<Slot> ssd_order = {
-      {-1, {"conv6"}}, {-1, {"conv7"}},
-      {-1, {"block8_conv1x1"}}, {-1, {"block8_conv3x3"}},
-      {T64, {"block8_box_conv_loc", "block8_box_conv_cls", "block9_conv1x1"}}, {-1, {"block9_conv3x3"}},
-      {T64, {"block9_box_conv_loc", "block9_box_conv_cls", "block10_conv1x1"}}, {-1, {"block10_conv3x3"}},
-      {T64, {"block10_box_conv_loc", "block10_box_conv_cls", "block11_conv1x1"}}, {-1, {"block11_conv3x3"}},
-      {T64, {"block11_box_conv_loc", "block11_box_conv_cls", "block12_conv1x1"}}, {-1, {"block12_conv4x4"}},
-      {T64, {"block12_box_conv_loc", "block12_box_conv_cls"}},
-      {-1, {"block4_l2norm"}}, {-1, {"block4_box_conv_cls_loc"}}, {-1, {"block7_box_conv_cls_loc"}},
-  };
+  // SSD-300 has the same chain on 19x19 ... 1x1 maps, one block shorter (16 small launches -> 9).
+  std::vector<Slot> ssd_order;
+  if (const SsdSpec* S = ssd_spec(c->cfg.variant)) {
+    ssd_order = {{-1, {"conv6"}}, {-1, {"conv7"}}, {-1, {"block8_conv1x1"}}};
+    for (int b = 0; b < S->n_extra; ++b) {
+      const std::string B = "block" + std::to_string(8 + b);
+      ssd_order.push_back({-1, {B + "_" + ssd_extra_conv(S->extra[b])}});
+      Slot g{T64, {B + "_box_conv_loc", B + "_box_conv_cls"}};
+      if (b + 1 < S->n_extra) g.names.push_back("block" + std::to_string(9 + b) + "_conv1x1");
+      ssd_order.push_back(g);
+    }
+    ssd_order.push_back({-1, {"block4_l2norm"}});
+    for (int i = 0; i < kSsdPairedHeads; ++i) ssd_order.push_back({-1, {std::string(S->feat[i]) + "_box_conv_cls_loc"}});
+  }
   // RON heads.  Dependencies after the round-4 re-formulation of the reverse connection (the LEFT conv of a scale reads a backbone
   // map only; the transposed conv adds its half in place, ron_finalize_weights):
   //   conv_left(i)                       <- backbone (fc7 / fc6 / conv5_3 / conv4_3)        i = block7, 6, 5, 4
@@ -568,10 +613,10 @@ void plan_groups(ron_ctx* c) {
   for (size_t i = 0; i < c->ops.size(); ++i) at[c->ops[i].name] = (int)i;
   size_t first_head = c->ops.size(), n_named = 0;
   for (const Slot& s : order)
-    for (const char* nm : s.names) {
+    for (const std::string& nm : s.names) {
       auto it = at.find(nm);
       if (it == at.end()) {                               // not the graph this plan was written for: keep the plain order, loudly
-        fprintf(stderr, "libron_hip: grouped launch plan names op '%s' which the graph does not have: one launch per convolution\n", nm);
+        fprintf(stderr, "libron_hip: grouped launch plan names op '%s' which the graph does not have: one launch per convolution\n", nm.c_str());
         return;
       }
       first_head = std::min(first_head, (size_t)it->second);
@@ -585,7 +630,7 @@ void plan_groups(ron_ctx* c) {
   std::vector<Op> planned(c->ops.begin(), c->ops.begin() + first_head);
   int gid = 0;
   for (const Slot& s : order) {
-    for (const char* nm : s.names) {
+    for (const std::string& nm : s.names) {
       Op o = c->ops[at[nm]];
       if (s.cfg >= 0) { o.group = gid; o.group_cfg = s.cfg; }
       planned.push_back(o);
@@ -610,10 +655,12 @@ double conv_flops(const Var& w, int out_pixels) { return 2.0 * (double)w.numel()
 // ------------------------------------------------------------------------------------------
 extern "C" int ron_create(ron_ctx** out, const ron_config* cfg) {
   RON_REQUIRE(out && cfg, "NULL argument");
-  RON_REQUIRE(cfg->variant >= RON_VARIANT_REDUCEDFC && cfg->variant <= RON_VARIANT_SSD512, "unknown variant %d", cfg->variant);
+  RON_REQUIRE(cfg->variant >= RON_VARIANT_REDUCEDFC && cfg->variant <= RON_VARIANT_SSD300, "unknown variant %d", cfg->variant);
   RON_REQUIRE(cfg->dtype >= 0 && cfg->dtype <= RON_DTYPE_F16X3, "unknown dtype %d", cfg->dtype);
-  RON_REQUIRE(cfg->img_h > 0 && cfg->img_h % 64 == 0 && cfg->img_w > 0 && cfg->img_w % 64 == 0, "image size must be a multiple of 64");
-  if (cfg->variant == RON_VARIANT_SSD512) RON_REQUIRE(cfg->img_h == 512 && cfg->img_w == 512, "SSD-512 runs on 512 x 512 inputs");
+  if (const SsdSpec* S = ssd_spec(cfg->variant))
+    RON_REQUIRE(cfg->img_h == S->img && cfg->img_w == S->img, "SSD-%d runs on %d x %d inputs", S->img, S->img, S->img);
+  else
+    RON_REQUIRE(cfg->img_h > 0 && cfg->img_h % 64 == 0 && cfg->img_w > 0 && cfg->img_w % 64 == 0, "image size must be a multiple of 64");
   RON_REQUIRE(cfg->num_classes >= 2 && cfg->num_classes <= RON_MAX_CLASSES, "num_classes %d out of range [2, %d]", cfg->num_classes, RON_MAX_CLASSES);
   RON_REQUIRE(cfg->max_batch >= 1, "max_batch must be >= 1");
   RON_HIP_CHECK(ron::dev_set_device(cfg->device));
@@ -657,7 +704,8 @@ extern "C" int ron_create(ron_ctx** out, const ron_config* cfg) {
   }
   for (auto& t : c->tensors) {
     if (t.name == "im2col" && cfg->dtype != RON_DTYPE_F32) continue;      // bf16 / f16 / f16x3 use the stem kernel
-    if ((cfg->flags & RON_CFG_FUSE_POOLS) && (t.name == "conv1_2" || t.name == "conv2_2" || t.name == "conv3_3")) continue;
+    if ((cfg->flags & RON_CFG_FUSE_POOLS) && (t.name == "conv1_2" || t.name == "conv2_2" || t.name == "conv3_3") &&
+        !((cfg->flags & RON_CFG_NO_ODD_POOL_FUSE) && ((t.H | t.W) & 1))) continue;
     if ((cfg->flags & RON_CFG_FUSE_POOLS) && !(cfg->flags & RON_CFG_NO_STEM2) && dtype_is_half(cfg->dtype) && H % 8 == 0 &&
         W % 32 == 0 && t.name == "conv1_1") continue;         // conv1_1 + conv1_2 + pool1 run fused (stem2_kernel)
     t.bytes = TensorView::halo_pixels(cfg->max_batch, t.H, t.W, t.pad) * t.cstride * c->esz();     // shared halos, conv_mfma.h
@@ -802,7 +850,8 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
       prev = T(pname);
       continue;
     }
-    if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && b < 3 && c->ops.back().kind == OP_CONV) {
+    if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && b < 3 && c->ops.back().kind == OP_CONV &&
+        !((c->cfg.flags & RON_CFG_NO_ODD_POOL_FUSE) && ((h | w) & 1))) {
       c->ops.back().pool = 1;                 // block1..3 feed nothing but their pool: never written at full size
       c->ops.back().out = T(pname);
       c->ops.back().name += "+" + pname;
@@ -826,15 +875,16 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
         c->ops.push_back(f);
       }
     } else {
-      if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && c->ops.back().kind == OP_CONV) c->ops.back().fuse_next_pool = 1;
+      if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && b >= 3 && c->ops.back().kind == OP_CONV) c->ops.back().fuse_next_pool = 1;
       Op p; p.kind = OP_POOL; p.name = pname; p.in = prev; p.out = T(p.name);
       c->ops.push_back(p);
     }
     prev = T(pname);
-    h /= 2; w /= 2;
+    h = pool2_out(h); w = pool2_out(w);
   }
   if (c->is_ssd()) {
-    // ---- conv6 (3x3 rate 6), conv7 (1x1), blocks 8-12 (1x1 then pad2d(1) + 3x3 stride 2 VALID; block12: 4x4 VALID) ----
+    const SsdSpec& S = *ssd_spec(c->cfg.variant);
+    // ---- conv6 (3x3 rate 6), conv7 (1x1), extra blocks (1x1, then SsdExtra: pad 1 + 3x3 stride 2 / pad 1 + 4x4 / 3x3 VALID) ----
     PACK(pack_plain(c, "conv6", false));
     { Op o = conv_op("conv6", prev, T("conv6"), rc, 3, 6, 1, h, w); o.dil = 6; c->ops.push_back(o); }
     flops += conv_flops(c->var("conv6/weights"), h * w); ATTR();
@@ -842,16 +892,17 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
     c->ops.push_back(conv_op("conv7", T("conv6"), T("conv7"), rc, 1, 0, 1, h, w));
     flops += conv_flops(c->var("conv7/weights"), h * w); ATTR();
     int src = T("conv7");
-    for (int b = 0; b < 5; ++b) {
+    for (int b = 0; b < S.n_extra; ++b) {
+      const SsdExtra& e = S.extra[b];
       const std::string B = "block" + std::to_string(8 + b);
       PACK(pack_plain(c, B + "/conv1x1", false));
       c->ops.push_back(conv_op(B + "_conv1x1", src, T(B + "_mid"), rc, 1, 0, 1, h, w));
       flops += conv_flops(c->var(B + "/conv1x1/weights"), h * w); ATTR();
-      const std::string cs = B + (b == 4 ? "/conv4x4" : "/conv3x3");
+      const std::string cs = B + "/" + ssd_extra_conv(e);
       PACK(pack_plain(c, cs, false));
-      const int ho = b == 4 ? 1 : h / 2, wo = b == 4 ? 1 : w / 2;
-      Op o = conv_op(B + (b == 4 ? "_conv4x4" : "_conv3x3"), T(B + "_mid"), T(B), rc, b == 4 ? 4 : 3, 1, 1, ho, wo);
-      o.stride = b == 4 ? 1 : 2;
+      const int ho = conv_out(h, e.k, e.stride, e.cpad), wo = conv_out(w, e.k, e.stride, e.cpad);
+      Op o = conv_op(B + "_" + ssd_extra_conv(e), T(B + "_mid"), T(B), rc, e.k, e.cpad, 1, ho, wo);
+      o.stride = e.stride;
       c->ops.push_back(o);
       flops += conv_flops(c->var(cs + "/weights"), ho * wo); ATTR();
       src = T(B); h = ho; w = wo;
@@ -864,24 +915,24 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
       Op o; o.kind = OP_L2NORM; o.name = "block4_l2norm"; o.in = T("conv4_3"); o.out = T("block4_norm");
       c->ops.push_back(o);
     }
-    const char* feat_src[7] = {"block4_norm", "conv7", "block8", "block9", "block10", "block11", "block12"};
-    for (int i = 0; i < 7; ++i) {
-      const std::string L = std::string(kSsdFeat[i]) + "_box";
+    for (int i = 0; i < S.n_feat; ++i) {
+      const std::string L = std::string(S.feat[i]) + "_box";
+      const std::string feat_src = i == 0 ? "block4_norm" : (i == 1 ? "conv7" : S.feat[i]);
       const int fh = c->feat_h[i], fw = c->feat_w[i];
       if (i < kSsdPairedHeads) {
         // the two large maps: loc and cls as one launch with two outputs (pack_box_pair)
         PACK(pack_box_pair(c, L));
-        Op o = conv_op(L + "_conv_cls_loc", T(feat_src[i]), -2, rc, 3, 1, 0, fh, fw);
+        Op o = conv_op(L + "_conv_cls_loc", T(feat_src), -2, rc, 3, 1, 0, fh, fw);
         o.head_kind = 0; o.head_kind2 = 2; o.head_layer = i;
         c->ops.push_back(o);
         flops += conv_flops(c->var(L + "/conv_loc/weights"), fh * fw) + conv_flops(c->var(L + "/conv_cls/weights"), fh * fw); ATTR();
         continue;
       }
       PACK(pack_plain(c, L + "/conv_loc", false));
-      { Op o = conv_op(L + "_conv_loc", T(feat_src[i]), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 2; o.head_layer = i; c->ops.push_back(o); }
+      { Op o = conv_op(L + "_conv_loc", T(feat_src), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 2; o.head_layer = i; c->ops.push_back(o); }
       flops += conv_flops(c->var(L + "/conv_loc/weights"), fh * fw); ATTR();
       PACK(pack_plain(c, L + "/conv_cls", false));
-      { Op o = conv_op(L + "_conv_cls", T(feat_src[i]), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 0; o.head_layer = i; c->ops.push_back(o); }
+      { Op o = conv_op(L + "_conv_cls", T(feat_src), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 0; o.head_layer = i; c->ops.push_back(o); }
       flops += conv_flops(c->var(L + "/conv_cls/weights"), fh * fw); ATTR();
     }
   } else {
@@ -986,7 +1037,7 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
     const int cin = o.in_C > 0 ? o.in_C : ti.C;
     const double out_esz = o.out == -2 ? 4.0 : (double)c->esz();
     const int os = o.up > 0 ? o.up * o.up : 1;
-    const double out_px = o.pool ? (double)o.Ho * o.Wo / 4 : (double)o.Ho * o.Wo * os;
+    const double out_px = o.pool ? (double)pool2_out(o.Ho) * pool2_out(o.Wo) : (double)o.Ho * o.Wo * os;
     const double out_ch = o.up > 0 ? (double)o.up_cout : (double)(pk.Cout - (pk.split_n - pk.split_first));
     o.act_bytes = (double)ti.H * ti.W * cin * c->esz() + out_px * out_ch * out_esz + (o.res >= 0 ? out_px * out_ch * c->esz() : 0.0);
     o.wgt_bytes = (double)pk.w_bytes;

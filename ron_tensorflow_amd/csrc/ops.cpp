@@ -111,7 +111,7 @@ int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool w
   if ((rc = S->d_in.alloc(c.in.bytes, true))) return rc;
   c.in.base = S->d_in.p;
   c.pool = d->pool;
-  if (d->pool) { S->ho /= 2; S->wo /= 2; }
+  if (d->pool) { S->ho = (S->ho + 1) / 2; S->wo = (S->wo + 1) / 2; }     // SAME pool: ceil
   // halo 1: exercises padded stores.  Split precision: pixels are whole 32-element (128-byte) chunks
   c.out = make_view(nullptr, d->n, S->ho, S->wo, d->dtype == RON_DTYPE_F16X3 ? round_up(d->cout, 32) : d->cout, 1, esz);
   c.out.C = d->cout;
@@ -142,10 +142,21 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
   ConvSetup S;
   int rc;
   if ((rc = setup_conv(d, w, bias, residual != nullptr, &S))) return rc;
-  if (S.is_c3 && dtype_is_half(d->dtype) && d->cout == 64 && d->w % 32 == 0 && d->relu && !residual) {
-    // conv1_1 through the dedicated stem kernel (what the graph runs for bf16 / f16)
+  // conv1_1 through the dedicated stem kernel (what the graph runs for bf16 / f16 / f16x3):
+  //   * widths that are a multiple of 32 keep the routing they always had here: bf16 / f16 take the stem kernel, f16x3 im2col + GEMM
+  //     (the comparison path of the tests);
+  //   * a ragged width (which the stem kernel used to refuse, so it went to im2col + GEMM) takes the stem kernel in all three dtypes
+  //     unless the caller forces a tile configuration, which selects im2col + GEMM;
+  //   * with `pool` set the launch is im2col + GEMM with the fused pool (the stem kernel has no pool; this branch once ignored the flag).
+  const bool stem_shape = S.is_c3 && d->cout == 64 && d->relu && !residual && !d->pool;
+  const bool full_tiles = d->w % 32 == 0;
+  const bool stem_dtype = full_tiles ? dtype_is_half(d->dtype) : (dtype_is_half(d->dtype) || d->dtype == RON_DTYPE_F16X3);
+  const bool stem_forced_off = !full_tiles && d->tile_cfg >= 0;
+  if (stem_shape && stem_dtype && !stem_forced_off) {
     std::vector<uint16_t> frags;
-    stem_pack_weights(w, d->dtype, &frags);
+    float oscale = 1.f;
+    if (d->dtype == RON_DTYPE_F16X3) oscale = stem_pack_weights_split(w, &frags);
+    else stem_pack_weights(w, d->dtype, &frags);
     std::vector<float> b64(64, 0.f);
     if (bias) memcpy(b64.data(), bias, 64 * sizeof(float));
     DevBuf d_f, d_bb;
@@ -153,7 +164,7 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
     if ((rc = d_bb.alloc(64 * 4, false))) return rc;
     RON_HIP_CHECK(hipMemcpy(d_f.p, frags.data(), frags.size() * 2, hipMemcpyHostToDevice));
     RON_HIP_CHECK(hipMemcpy(d_bb.p, b64.data(), 64 * 4, hipMemcpyHostToDevice));
-    if ((rc = launch_stem_conv(x, d->n, d->h, d->w, d->dtype, d_f.p, (const float*)d_bb.p, S.c.out, s))) return rc;
+    if ((rc = launch_stem_conv(x, d->n, d->h, d->w, d->dtype, d_f.p, (const float*)d_bb.p, S.c.out, s, oscale))) return rc;
     if ((rc = launch_unpack(S.c.out, d->dtype, 0, y, s))) return rc;
     RON_HIP_CHECK(hipStreamSynchronize(s));
     return RON_OK;
@@ -170,6 +181,31 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
   }
   if ((rc = launch_conv(S.c, s))) return rc;
   if ((rc = launch_unpack(S.c.out, d->dtype, 0, y, s))) return rc;
+  RON_HIP_CHECK(hipStreamSynchronize(s));
+  return RON_OK;
+}
+
+// conv + fused SAME pool with the un-pooled map as the launch's second output (ConvLaunch::out2): what the graph does for conv4_3 /
+// conv5_3 under RON_CFG_FUSE_POOLS, as a single operator for the parity tests.
+extern "C" int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* bias, float* y_pooled,
+                                     float* y_full, void* stream) {
+  using namespace ron;
+  RON_REQUIRE(d && x && w && y_pooled && y_full, "NULL argument");
+  RON_REQUIRE(d->pool && !d->transpose && d->stride == 1 && d->cin % conv_k_chunk(d->dtype) == 0, "two-output pooled convolution: a plain stride-1 convolution with pool set");
+  hipStream_t s = (hipStream_t)stream;
+  ConvSetup S;
+  int rc;
+  if ((rc = setup_conv(d, w, bias, false, &S))) return rc;
+  ConvLaunch& c = S.c;
+  DevBuf d_full;
+  c.out2 = make_view(nullptr, d->n, d->h, d->w, c.out.cstride, 1, (int)dtype_size(d->dtype));
+  c.out2.C = d->cout;
+  if ((rc = d_full.alloc(c.out2.bytes, true))) return rc;
+  c.out2.base = d_full.p;
+  if ((rc = launch_pack_input(x, c.in, d->dtype, s))) return rc;
+  if ((rc = launch_conv(c, s))) return rc;
+  if ((rc = launch_unpack(c.out, d->dtype, 0, y_pooled, s))) return rc;
+  if ((rc = launch_unpack(c.out2, d->dtype, 0, y_full, s))) return rc;
   RON_HIP_CHECK(hipStreamSynchronize(s));
   return RON_OK;
 }
@@ -279,11 +315,11 @@ extern "C" int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, f
 
 extern "C" int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, int dtype, float* y, void* stream) {
   using namespace ron;
-  RON_REQUIRE(x && y && n > 0 && h > 0 && w > 0 && c > 0 && h % 2 == 0 && w % 2 == 0, "bad argument");
+  RON_REQUIRE(x && y && n > 0 && h > 0 && w > 0 && c > 0, "bad argument");
   hipStream_t s = (hipStream_t)stream;
   const int esz = (int)dtype_size(dtype);
   TensorView vin = make_view(nullptr, n, h, w, c, 1, esz);
-  TensorView vout = make_view(nullptr, n, h / 2, w / 2, c, 3, esz);
+  TensorView vout = make_view(nullptr, n, (h + 1) / 2, (w + 1) / 2, c, 3, esz);     // SAME: ceil
   DevBuf d_in, d_out;
   int rc;
   if ((rc = d_in.alloc(vin.bytes, true))) return rc;

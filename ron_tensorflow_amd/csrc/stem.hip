@@ -3,7 +3,8 @@
 //
 // K = 27 is too thin for the LDS-DMA implicit-GEMM kernel (its rows are 128-byte chunks), so this layer is its own
 // kernel: HBM-bound on the 128 B/pixel output (13 MB/image), the 4 MFMAs per 32 pixels are noise.
-//   * one wave = 32 consecutive pixels of one image row; it stages the 3 x 34 x 3 fp32 input patch in its private LDS
+//   * one wave = 32 consecutive pixels of one image row (fewer in the last tile of a row whose width is not a multiple of 32: the
+//     staging is zero beyond the image and the stores of the pixels that do not exist are masked); it stages the 3 x 34 x 3 fp32 input patch in its private LDS
 //     slice (zero outside the image), then every lane gathers its 16 A values (pixel r = lane & 31, k = 8h+j and
 //     16+8h+j, k = ty*9 + tx*3 + c, zero for k >= 27) with stride-3 LDS reads (conflict free) and packs them to bf16;
 //   * B (weights, [64][32] after padding K) lives in 4 registers per lane for the whole kernel;
@@ -83,7 +84,7 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
       a_off[s][j] = k < 27 ? ty * kPatchW + r * 3 + rem : -1;
     }
   float* patch = s_in[wave];
-  const int tiles_per_row = W / 32;
+  const int tiles_per_row = (W + 31) / 32;      // the last tile of a row is ragged when W % 32 != 0 (SSD-300: 12 columns): masked stores
   const long long n_tiles = (long long)n_img * H * tiles_per_row;
   for (long long tile = (long long)blockIdx.x * 4 + wave; tile < n_tiles; tile += (long long)gridDim.x * 4) {
     const int tx = (int)(tile % tiles_per_row);
@@ -121,11 +122,12 @@ __global__ __launch_bounds__(256) void stem_conv_kernel(const float* __restrict_
     }
     // pixel row p = (e & 3) + 8 * (e >> 2) + 4 * h ; lanes r = 0..31 cover channels 0..63 as dwords
     const long long obase = ((img * out_Hp + y + out_pad) * (long long)out_Wp + x0 + out_pad) * 32;   // in dwords (64 ch * 2 B)
+    const int n_px = min(32, W - x0);          // pixels of this tile that exist (the staged patch is zero beyond the image)
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
       const int p = (e & 3) + 8 * (e >> 2) + 4 * h;
       const unsigned lo = Tr::cvt(fmaxf(acc[0][e] + b0, 0.f)), hi = Tr::cvt(fmaxf(acc[1][e] + b1, 0.f));
-      out[obase + (long long)p * 32 + r] = lo | (hi << 16);
+      if (p < n_px) out[obase + (long long)p * 32 + r] = lo | (hi << 16);
     }
     __builtin_amdgcn_wave_barrier();          // patch is rewritten by the next iteration
   }
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(256) void stem_conv_split_kernel(const float* __res
       a_off[s][j] = k < 27 ? ty * kPatchW + r * 3 + rem : -1;
     }
   float* patch = s_in[wave];
-  const int tiles_per_row = W / 32;
+  const int tiles_per_row = (W + 31) / 32;      // the last tile of a row is ragged when W % 32 != 0 (SSD-300: 12 columns): masked stores
   const long long n_tiles = (long long)n_img * H * tiles_per_row;
   for (long long tile = (long long)blockIdx.x * 4 + wave; tile < n_tiles; tile += (long long)gridDim.x * 4) {
     const int tx = (int)(tile % tiles_per_row);
@@ -209,6 +211,7 @@ __global__ __launch_bounds__(256) void stem_conv_split_kernel(const float* __res
     }
     // a pixel = 64 dwords: channel pair r (channels 2r, 2r + 1) -> chunk r / 16: hi dword at chunk * 32 + r % 16, lo dword 16 further
     const long long obase = ((img * out_Hp + y + out_pad) * (long long)out_Wp + x0 + out_pad) * 64;
+    const int n_px = min(32, W - x0);
     const int od = (r >> 4) * 32 + (r & 15);
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
@@ -216,6 +219,7 @@ __global__ __launch_bounds__(256) void stem_conv_split_kernel(const float* __res
       const float v0 = fmaxf(fmaf(acc[0][e], oscale, b0), 0.f), v1 = fmaxf(fmaf(acc[1][e], oscale, b1), 0.f);
       const _Float16 h0 = (_Float16)v0, h1 = (_Float16)v1;
       const _Float16 l0 = (_Float16)(v0 - (float)h0), l1 = (_Float16)(v1 - (float)h1);
+      if (p >= n_px) continue;
       out[obase + (long long)p * 64 + od] = (unsigned)__builtin_bit_cast(unsigned short, h0) | ((unsigned)__builtin_bit_cast(unsigned short, h1) << 16);
       out[obase + (long long)p * 64 + od + 16] = (unsigned)__builtin_bit_cast(unsigned short, l0) | ((unsigned)__builtin_bit_cast(unsigned short, l1) << 16);
     }
@@ -479,8 +483,8 @@ float stem_pack_weights_split(const float* hwio, std::vector<uint16_t>* frags) {
 int launch_stem_conv(const float* x, int n, int h, int w, int dtype, const void* d_wfrag, const float* d_bias,
                      const TensorView& out, hipStream_t s, float oscale) {
   RON_REQUIRE(dtype == RON_DTYPE_BF16 || dtype == RON_DTYPE_F16 || dtype == RON_DTYPE_F16X3, "stem kernel: bf16 / f16 / f16x3 only");
-  RON_REQUIRE(w % 32 == 0 && out.C == 64 && out.cstride == 64 && out.coff == 0 && out.H == h && out.W == w, "stem kernel: bad shape");
-  const long long tiles = (long long)n * h * (w / 32);
+  RON_REQUIRE(w > 0 && out.C == 64 && out.cstride == 64 && out.coff == 0 && out.H == h && out.W == w, "stem kernel: bad shape");
+  const long long tiles = (long long)n * h * ((w + 31) / 32);
   const int grid = (int)std::min<long long>((tiles + 3) / 4, 256 * 8);
   if (dtype == RON_DTYPE_F16X3)
     RON_LAUNCH(stem_conv_split_kernel, dim3(grid), dim3(256), 0, s, x, n, h, w, (const u32x4*)d_wfrag, d_bias, oscale,

@@ -93,6 +93,7 @@ class RONNet(object):
                               (_lib.RON_CFG_NO_STEM2 if getattr(self, 'no_stem2', False) else 0) |
                               (_lib.RON_CFG_NO_GROUPS if getattr(self, 'no_groups', False) else 0) |
                               (_lib.RON_CFG_NO_HALO_SKIP if getattr(self, 'no_halo_skip', False) else 0) |
+                              (_lib.RON_CFG_NO_ODD_POOL_FUSE if getattr(self, 'no_odd_pool_fuse', False) else 0) |
                               {None: 0, 'level': _lib.RON_CFG_LEVEL_GROUPS, 'batch': _lib.RON_CFG_BATCH_GROUPS}[getattr(self, 'head_plan', None)])
             h = C.c_void_p()
             check(lib().ron_create(C.byref(h), C.byref(cfg)))

@@ -38,11 +38,13 @@ class SSDNet(RONNet):
         normalizations=[20, -1, -1, -1, -1, -1, -1],
         prior_scaling=[0.1, 0.1, 0.2, 0.2])
 
+    _variant = 'ssd512'        # _lib.VARIANTS key of the context this class builds (ssd_vgg_300.SSDNet: 'ssd300')
+
     def __init__(self, params=None, dtype='bf16', max_batch=16, device=None, fuse_pools=False):
-        self.params = params if isinstance(params, SSDParams) else SSDNet.default_params
+        self.params = params if isinstance(params, SSDParams) else type(self).default_params
         if dtype not in _lib.DTYPES:
             raise ValueError('Unknown dtype %s' % dtype)
-        self.variant, self.dtype, self.max_batch, self.fuse_pools = 'ssd512', dtype, max_batch, fuse_pools
+        self.variant, self.dtype, self.max_batch, self.fuse_pools = self._variant, dtype, max_batch, fuse_pools
         self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
         self._ctx = None
         self._anchors_dev = None
@@ -129,21 +131,28 @@ class SSDNet(RONNet):
 
 
 # ---------------------------------------------------------------------- the reference's function entries (nets_factory.networks_map)
+def _ssd_net_fn(cls, inputs, num_classes, feat_layers, anchor_sizes, anchor_ratios, normalizations, is_training, dropout_keep_prob,
+                prediction_fn, reuse, scope, weights, dtype, max_batch):
+    """ssd_net of either SSD module: a scope name owns one network object of class `cls`, like ron_vgg_320.ron_net."""
+    params = cls.default_params._replace(num_classes=num_classes, feat_layers=list(feat_layers), anchor_sizes=list(anchor_sizes),
+                                         anchor_ratios=list(anchor_ratios), normalizations=list(normalizations))
+    dev = inputs.device if inputs.is_cuda else torch.device('cuda', torch.cuda.current_device())
+    key = (scope, cls._variant, num_classes, dtype, str(dev))
+    net = ron_vgg_320._scoped_net(key, lambda: cls(params, dtype=dtype, max_batch=max(max_batch, inputs.shape[0]), device=dev), weights, reuse)
+    fmt = ron_vgg_320._ARG_SCOPE_FORMAT[-1] if ron_vgg_320._ARG_SCOPE_FORMAT else 'NHWC'
+    with ron_vgg_320._DataFormatScope([net], fmt):
+        return net.net(inputs, is_training=is_training, update_feat_shapes=False, dropout_keep_prob=dropout_keep_prob,
+                       prediction_fn=prediction_fn, reuse=reuse, scope=scope)
+
+
 def ssd_net(inputs, num_classes=SSDNet.default_params.num_classes, feat_layers=SSDNet.default_params.feat_layers,
             anchor_sizes=SSDNet.default_params.anchor_sizes, anchor_ratios=SSDNet.default_params.anchor_ratios,
             normalizations=SSDNet.default_params.normalizations, is_training=True, dropout_keep_prob=0.5, prediction_fn=None,
             reuse=None, scope='ssd_512_vgg', weights=None, dtype='bf16', max_batch=16):
     """SSD net definition (nets/ssd_vgg_512.py:364-460): (predictions, localisations, logits, end_points).  A scope name owns one
     network object, like ron_vgg_320.ron_net: the first call needs `weights=`."""
-    params = SSDNet.default_params._replace(num_classes=num_classes, feat_layers=list(feat_layers), anchor_sizes=list(anchor_sizes),
-                                            anchor_ratios=list(anchor_ratios), normalizations=list(normalizations))
-    dev = inputs.device if inputs.is_cuda else torch.device('cuda', torch.cuda.current_device())
-    key = (scope, 'ssd512', num_classes, dtype, str(dev))
-    net = ron_vgg_320._scoped_net(key, lambda: SSDNet(params, dtype=dtype, max_batch=max(max_batch, inputs.shape[0]), device=dev), weights, reuse)
-    fmt = ron_vgg_320._ARG_SCOPE_FORMAT[-1] if ron_vgg_320._ARG_SCOPE_FORMAT else 'NHWC'
-    with ron_vgg_320._DataFormatScope([net], fmt):
-        return net.net(inputs, is_training=is_training, update_feat_shapes=False, dropout_keep_prob=dropout_keep_prob,
-                       prediction_fn=prediction_fn, reuse=reuse, scope=scope)
+    return _ssd_net_fn(SSDNet, inputs, num_classes, feat_layers, anchor_sizes, anchor_ratios, normalizations, is_training,
+                       dropout_keep_prob, prediction_fn, reuse, scope, weights, dtype, max_batch)
 
 
 ssd_net.default_image_size = 512

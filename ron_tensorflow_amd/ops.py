@@ -241,12 +241,27 @@ def conv2d_nhwc(x, w, bias=None, residual=None, stride=1, dilation=1, relu=True,
     d = _lib.ConvDesc(n, h, wd, cin, cout, kh, kw, stride, dilation, int(relu), int(transpose), _lib.DTYPES[dtype], tile_cfg, in_cstride, in_coff, int(pool), splitk, center_from)
     ho, wo = (h * stride, wd * stride) if transpose else (h // stride, wd // stride)
     if pool:
-        ho, wo = ho // 2, wo // 2
+        ho, wo = (ho + 1) // 2, (wo + 1) // 2         # SAME: ceil
     y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
     b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
     r = None if residual is None else residual.contiguous()
     check(lib().ron_conv2d_nhwc(C.byref(d), ptr(x), ptr(w), ptr(b), ptr(r), ptr(y), current_stream()))
     return y
+
+
+def conv2d_pool2_nhwc(x, w, bias=None, relu=True, dtype='bf16', tile_cfg=-1):
+    """3x3-style stride-1 convolution with the fused SAME 2x2 pool AND the un-pooled map from the same launch (ron_conv2d_pool2_nhwc:
+    what the graph does for conv4_3 / conv5_3 with fuse_pools): (pooled [N,ceil(H/2),ceil(W/2),Cout], full [N,H,W,Cout])."""
+    x = x.contiguous()
+    w = np.ascontiguousarray(w, dtype=np.float32)
+    n, h, wd, cin = x.shape
+    kh, kw, _, cout = w.shape
+    d = _lib.ConvDesc(n, h, wd, cin, cout, kh, kw, 1, 1, int(relu), 0, _lib.DTYPES[dtype], tile_cfg, 0, 0, 1, 1, 0)
+    yp = torch.empty((n, (h + 1) // 2, (wd + 1) // 2, cout), dtype=torch.float32, device=x.device)
+    yf = torch.empty((n, h, wd, cout), dtype=torch.float32, device=x.device)
+    b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    check(lib().ron_conv2d_pool2_nhwc(C.byref(d), ptr(x), ptr(w), ptr(b), ptr(yp), ptr(yf), current_stream()))
+    return yp, yf
 
 
 def conv_plan(n, h, w, cin, cout, k=3, stride=1, dilation=1, dtype='bf16', tile_cfg=-1, splitk=-1, pool=False, center_from=0, transpose=False):
@@ -273,8 +288,9 @@ def conv2d_heads_nhwc(x, w, split_first, bias=None, dilation=1, relu=False, dtyp
 
 
 def maxpool2x2_nhwc(x, dtype='bf16'):
+    """slim.max_pool2d [2, 2] stride 2 SAME: [N, ceil(H/2), ceil(W/2), C] (an odd map's last window holds one row / column)."""
     x = x.contiguous()
     n, h, w, c = x.shape
-    y = torch.empty((n, h // 2, w // 2, c), dtype=torch.float32, device=x.device)
+    y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=x.device)
     check(lib().ron_maxpool2x2_nhwc(ptr(x), n, h, w, c, _lib.DTYPES[dtype], ptr(y), current_stream()))
     return y

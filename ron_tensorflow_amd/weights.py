@@ -58,13 +58,13 @@ SSD_ANCHORS = [4, 6, 6, 6, 6, 4, 4]
 SSD_FEAT_CHANNELS = [512, 1024, 512, 256, 256, 256, 256]
 
 
-def ssd_variable_shapes(num_classes=21):
-    """(tf_name, shape) of SSD-512 (nets/ssd_vgg_512.py:364-460, multibox layer nets/ssd_vgg_300.py:403-431)."""
+def _ssd_shapes(scope, feat_layers, anchors, feat_channels, extra, num_classes):
+    """(tf_name, shape) of an SSD graph: VGG-16 body, conv6 / conv7, the extra blocks [(cin, mid, cout, k)], the multibox heads."""
     out = []
 
-    def conv(scope, k, cin, cout):
-        out.append(('%s/%s/weights' % (SSD_SCOPE, scope), (k, k, cin, cout)))
-        out.append(('%s/%s/biases' % (SSD_SCOPE, scope), (cout,)))
+    def conv(name, k, cin, cout):
+        out.append(('%s/%s/weights' % (scope, name), (k, k, cin, cout)))
+        out.append(('%s/%s/biases' % (scope, name), (cout,)))
 
     cin = 3
     for b, (reps, width) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)]):
@@ -73,22 +73,21 @@ def ssd_variable_shapes(num_classes=21):
             cin = width
     conv('conv6', 3, 512, 1024)
     conv('conv7', 1, 1024, 1024)
-    for b, (inc, mid, outc) in enumerate([(1024, 256, 512), (512, 128, 256), (256, 128, 256), (256, 128, 256), (256, 128, 256)]):
+    for b, (inc, mid, outc, k) in enumerate(extra):
         conv('block%d/conv1x1' % (8 + b), 1, inc, mid)
-        conv('block%d/%s' % (8 + b, 'conv4x4' if b == 4 else 'conv3x3'), 4 if b == 4 else 3, mid, outc)
-    for i, layer in enumerate(SSD_FEAT_LAYERS):
+        conv('block%d/conv%dx%d' % (8 + b, k, k), k, mid, outc)
+    for i, layer in enumerate(feat_layers):
         if i == 0:
-            out.append(('%s/%s_box/L2Normalization/gamma' % (SSD_SCOPE, layer), (512,)))
-        conv(layer + '_box/conv_loc', 3, SSD_FEAT_CHANNELS[i], SSD_ANCHORS[i] * 4)
-        conv(layer + '_box/conv_cls', 3, SSD_FEAT_CHANNELS[i], SSD_ANCHORS[i] * num_classes)
+            out.append(('%s/%s_box/L2Normalization/gamma' % (scope, layer), (512,)))
+        conv(layer + '_box/conv_loc', 3, feat_channels[i], anchors[i] * 4)
+        conv(layer + '_box/conv_cls', 3, feat_channels[i], anchors[i] * num_classes)
     return out
 
 
-def ssd_synthetic_weights(num_classes=21, seed=5, bg=6.0, input_scale=1.0 / 64.0):
-    """Seeded He-normal weights for SSD-512; +bg on every background logit; L2-norm scale 20 (the reference's init)."""
+def _ssd_synthetic(shapes, num_classes, seed, bg, input_scale):
     rs = np.random.RandomState(seed)
     w = {}
-    for name, shape in ssd_variable_shapes(num_classes):
+    for name, shape in shapes:
         leaf = name.rsplit('/', 1)[1]
         if leaf == 'weights':
             a = rs.standard_normal(int(np.prod(shape))).astype(np.float32).reshape(shape)
@@ -107,6 +106,37 @@ def ssd_synthetic_weights(num_classes=21, seed=5, bg=6.0, input_scale=1.0 / 64.0
             raise AssertionError(name)
         w[name] = a
     return w
+
+
+def ssd_variable_shapes(num_classes=21):
+    """(tf_name, shape) of SSD-512 (nets/ssd_vgg_512.py:364-460, multibox layer nets/ssd_vgg_300.py:403-431)."""
+    return _ssd_shapes(SSD_SCOPE, SSD_FEAT_LAYERS, SSD_ANCHORS, SSD_FEAT_CHANNELS,
+                       [(1024, 256, 512, 3), (512, 128, 256, 3), (256, 128, 256, 3), (256, 128, 256, 3), (256, 128, 256, 4)], num_classes)
+
+
+def ssd_synthetic_weights(num_classes=21, seed=5, bg=6.0, input_scale=1.0 / 64.0):
+    """Seeded He-normal weights for SSD-512; +bg on every background logit; L2-norm scale 20 (the reference's init)."""
+    return _ssd_synthetic(ssd_variable_shapes(num_classes), num_classes, seed, bg, input_scale)
+
+
+SSD300_SCOPE = 'ssd_300_vgg'
+SSD300_FEAT_LAYERS = ['block4', 'block7', 'block8', 'block9', 'block10', 'block11']
+SSD300_ANCHORS = [4, 6, 6, 6, 4, 4]
+SSD300_FEAT_CHANNELS = [512, 1024, 512, 256, 256, 256]
+SSD300_FEAT_SHAPES = [(38, 38), (19, 19), (10, 10), (5, 5), (3, 3), (1, 1)]
+
+
+def ssd300_variable_shapes(num_classes=21):
+    """(tf_name, shape) of SSD-300 (nets/ssd_vgg_300.py:434-523): blocks 8-11 are 1x1 then 3x3."""
+    return _ssd_shapes(SSD300_SCOPE, SSD300_FEAT_LAYERS, SSD300_ANCHORS, SSD300_FEAT_CHANNELS,
+                       [(1024, 256, 512, 3), (512, 128, 256, 3), (256, 128, 256, 3), (256, 128, 256, 3)], num_classes)
+
+
+def ssd300_synthetic_weights(num_classes=21, seed=6, bg=6.0, input_scale=1.0 / 64.0):
+    """Seeded He-normal weights for SSD-300, as ssd_synthetic_weights.  bg = 6 (the SSD-512 value): a score passes select 0.01 when its
+    logit is ~1.4 above the others' mean - a few thousand of the 8732 x 20, well above the 400 the sort keeps and far from all of them
+    (tests/test_ssd300_cpu.py counts them on the CPU reference; with bg = 4 four scores in five pass)."""
+    return _ssd_synthetic(ssd300_variable_shapes(num_classes), num_classes, seed, bg, input_scale)
 
 
 def synthetic_weights(variant='reducedfc', num_classes=21, num_anchors=10, seed=1, bg=8.0, ob=-4.0,

@@ -40,7 +40,7 @@ static int run(int variant, int dtype, uint32_t flags, int max_batch, bool detec
   ron_config cfg;
   memset(&cfg, 0, sizeof(cfg));
   cfg.variant = variant; cfg.dtype = dtype;
-  cfg.img_h = cfg.img_w = variant == RON_VARIANT_SSD512 ? 512 : 320;
+  cfg.img_h = cfg.img_w = variant == RON_VARIANT_SSD512 ? 512 : (variant == RON_VARIANT_SSD300 ? 300 : 320);
   cfg.num_classes = 21; cfg.max_batch = max_batch; cfg.device = 0; cfg.flags = flags;
   ron_ctx* c = nullptr;
   CHECK(ron_create(&c, &cfg));
@@ -113,6 +113,20 @@ int main(int argc, char** argv) {
     if (quick && mb != 32) continue;
     if (run(RON_VARIANT_FULL, RON_DTYPE_BF16, RON_CFG_FUSE_POOLS, mb, true)) return 1;
     ++runs;
+  }
+  // SSD-300 (odd maps: SAME pools 75 -> 38, the ragged stem tile, VALID 3x3 blocks): with and without the fused pools and the grouped
+  // tail; --quick keeps three contexts (the sweep's time limit)
+  for (uint32_t flags : {(uint32_t)RON_CFG_FUSE_POOLS, 0u, (uint32_t)(RON_CFG_FUSE_POOLS | RON_CFG_NO_GROUPS), (uint32_t)RON_CFG_NO_HALO_SKIP}) {
+    for (int mb : {1, 4, 13, 16, 32}) {
+      for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16X3, (int)RON_DTYPE_F32}) {
+        if (dtype != RON_DTYPE_BF16 && (flags & ~(uint32_t)RON_CFG_FUSE_POOLS) != 0u) continue;
+        if (dtype == RON_DTYPE_F32 && mb > 4) continue;
+        if (quick && !((dtype == RON_DTYPE_BF16 && flags == RON_CFG_FUSE_POOLS && (mb == 1 || mb == 32)) ||
+                       (dtype == RON_DTYPE_F32 && flags == 0u && mb == 1))) continue;
+        if (run(RON_VARIANT_SSD300, dtype, flags, mb, true)) return 1;
+        ++runs;
+      }
+    }
   }
   if (!quick) {
     if (run(RON_VARIANT_REDUCEDFC, RON_DTYPE_F32, 0u, 4, true)) return 1;
