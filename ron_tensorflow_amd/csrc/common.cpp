@@ -29,6 +29,10 @@ hipError_t dev_memset_async(void* p, int v, size_t bytes, hipStream_t s) { retur
 hipError_t dev_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   return plan_only() ? hipSuccess : hipMemcpy(dst, src, bytes, kind);
 }
+hipError_t dev_upload(DevBuf* b, const void* host, size_t bytes) {
+  const hipError_t e = dev_malloc(b->put(), bytes);
+  return e != hipSuccess ? e : dev_memcpy(b->p, host, bytes, hipMemcpyHostToDevice);
+}
 hipError_t dev_set_device(int device) { return plan_only() ? hipSuccess : hipSetDevice(device); }
 hipError_t launch_error() { return plan_only() ? hipSuccess : hipGetLastError(); }
 }  // namespace ron

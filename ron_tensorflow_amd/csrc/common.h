@@ -48,6 +48,30 @@ hipError_t dev_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind ki
 hipError_t dev_set_device(int device);
 hipError_t launch_error();                     // hipGetLastError(), hipSuccess in a dry run
 template <class T> hipError_t dev_malloc(T** p, size_t bytes) { return dev_malloc(reinterpret_cast<void**>(p), bytes); }
+
+// Owner of one HIP object - a device allocation, a stream, an event: move-only, released by the destructor, so that an early return
+// (RON_HIP_CHECK) or a destroyed context cannot leak it and nothing is released twice.
+template <class T, hipError_t (*Release)(T)>
+struct Owned {
+  T p = nullptr;
+  Owned() = default;
+  Owned(Owned&& o) noexcept : p(o.p) { o.p = nullptr; }
+  Owned& operator=(Owned&& o) noexcept {
+    if (this != &o) { reset(); p = o.p; o.p = nullptr; }
+    return *this;
+  }
+  Owned(const Owned&) = delete;
+  Owned& operator=(const Owned&) = delete;
+  ~Owned() { reset(); }
+  void reset() { if (p) (void)Release(p); p = nullptr; }
+  T* put() { reset(); return &p; }      // for the call that creates the object: dev_malloc(b.put(), bytes), hipEventCreate(e.put())
+  operator T() const { return p; }
+  template <class U> U* as() const { return static_cast<U*>(p); }
+};
+using DevBuf = Owned<void*, dev_free>;
+using Stream = Owned<hipStream_t, hipStreamDestroy>;
+using Event = Owned<hipEvent_t, hipEventDestroy>;
+hipError_t dev_upload(DevBuf* b, const void* host, size_t bytes);      // a new allocation of `bytes` bytes holding the host data
 #define RON_LAUNCH(...)                                          \
   do {                                                           \
     if (!ron::plan_only()) hipLaunchKernelGGL(__VA_ARGS__);      \

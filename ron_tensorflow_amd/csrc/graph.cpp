@@ -15,6 +15,10 @@
 //   * head logits are written as fp32 straight into the caller's buffers.
 // Every activation lives in HBM as NHWC with a zero halo (conv_mfma.h); all buffers are
 // allocated once for max_batch images (activations of the full variant: ~150 MB / image).
+//
+// The four networks (RON-320 reducedfc / full, SSD-512, SSD-300) are one VGG-16 body (VggBody) and one of two tails: the reverse
+// connections of RON, or the extra blocks + multibox heads of SSD (SsdSpec).  Variables, tensors and ops of each are declared by
+// the same three steps, body first.
 #include <math.h>
 
 #include <array>
@@ -47,18 +51,30 @@ struct Tensor {
   int H, W, C, pad;
   int cstride = 0;           // elements per pixel in memory (>= C): wide tensors get +64 so that the pixel stride
                              // is not a power of two (4 KiB strides serialise on a few L2 channels)
-  void* d = nullptr;
+  DevBuf d;
   int64_t bytes = 0;
 };
 
 struct PackedConv {
-  void* d_w = nullptr;
+  DevBuf w;
   int64_t w_bytes = 0;
-  void* d_w_c64 = nullptr;    // 3x3 on 64 input channels (conv2_1): the weights once more as LDS images for conv_c64.hip
-  float* d_bias = nullptr;
+  DevBuf w_c64;               // 3x3 on 64 input channels (conv2_1): the weights once more as LDS images for conv_c64.hip
+  DevBuf bias;
   float oscale = 1.f;         // accumulator scale of the epilogue (split-precision weights are stored times a power of two)
   int Npad = 0, Cout = 0;
   int split_n = 0, split_first = 0;   // two head convolutions packed side by side (pack_box_pair): ConvLaunch::split_n
+};
+
+// What ron_finalize_weights puts on the device.  The context that packed it owns it; an execution slot (ron_clone) points at its
+// owner's, so nothing here is ever listed buffer by buffer.
+struct Weights {
+  std::vector<PackedConv> packed;
+  DevBuf l2_gamma;            // SSD block4 L2Normalization scale
+  DevBuf stem_w, stem_b;      // conv1_1 fragments + bias for the dedicated stem kernel (bf16 / f16)
+  float stem_oscale = 1.f;    // split precision: 2^-k of the stem weights' scale
+  DevBuf stem2_w;             // conv1_2 weights as the LDS image of stem2_kernel (conv1_1 + conv1_2 + pool1 fused)
+  DevBuf stem2_w1;            // conv1_1 weights as 16x16x32 fragments for stem2_kernel
+  DevBuf stem2_b;
 };
 
 enum OpKind { OP_IM2COL, OP_CONV, OP_POOL, OP_STEM, OP_POOL3, OP_L2NORM, OP_STEM2 };
@@ -68,7 +84,6 @@ struct Op {
   std::string name;
   int in = -1, out = -1, res = -1;      // tensor indices; out == -2: caller head buffer
   int in_coff = 0, in_C = 0;            // channel slice of the input
-  int out_coff = 0, out_C = 0;          // channel slice of the output (out_C = 0: the whole tensor)
   int packed = -1;
   int kh = 1, kw = 1, stride = 1, dil = 1, cpad = 0, relu = 0;
   int up = 0, up_cout = 0, pool = 0;
@@ -91,46 +106,43 @@ struct OpTiming {
   int launches = 0;
 };
 
+// What a profiling stamp marks (ron_ctx::pending_ops): an op index >= 0 (the op's start), or one of these.  The end of side lane l is
+// kStampLaneEnd - 10 * l.
+constexpr int kStampLaneEnd = -1, kStampPostStart = -2, kStampPostEnd = -3;
+
 }  // namespace
 
 struct ron_ctx {
   ron_config cfg;
   int c6 = 0;                 // fc6 / fc7 channels
   int num_anchors = 10;                 // RON: anchors per cell on every scale
-  int feat[4] = {0, 0, 0, 0};
   // head layers, generic (RON: 4 scales x 10 anchors + objectness; SSD-512 / SSD-300: 7 / 6 scales, 4/6 anchors, no objectness)
-  int n_feat = 4;
+  int n_feat = 0;
   int feat_h[RON_MAX_LAYERS] = {}, feat_w[RON_MAX_LAYERS] = {}, feat_A[RON_MAX_LAYERS] = {};
   bool has_obj = true;
   bool is_ssd() const { return cfg.variant == RON_VARIANT_SSD512 || cfg.variant == RON_VARIANT_SSD300; }
   const char* scope() const { return cfg.variant == RON_VARIANT_SSD512 ? "ssd_512_vgg" : (cfg.variant == RON_VARIANT_SSD300 ? "ssd_300_vgg" : "ron_320_vgg"); }
-  float* d_l2_gamma = nullptr;          // SSD block4 L2Normalization scale
   std::vector<Var> vars;
   std::map<std::string, int> var_index;
   std::vector<Tensor> tensors;
   std::map<std::string, int> tensor_index;
-  std::vector<PackedConv> packed;
+  Weights own;                          // filled by ron_finalize_weights; empty in an execution slot
+  const Weights* wts = &own;            // ron_clone: the owner's
   std::vector<Op> ops;
   bool finalized = false;
   double flops_per_image = 0;
   // anchors (device) + head buffers / workspace for ron_detect
-  float* d_anchor[RON_MAX_LAYERS][4] = {};
-  float* d_head[3][RON_MAX_LAYERS] = {};
-  void* d_post_ws = nullptr;
+  DevBuf anchor[RON_MAX_LAYERS][4];
+  DevBuf head[3][RON_MAX_LAYERS];
+  DevBuf post_ws;
   int64_t post_ws_bytes = 0;
   bool post_ws_dirty = false;     // a ron_detect / ron_detect_tfe call failed after its select pass may have run: the self-cleaning counters are re-zeroed on the next call
   bool tfe_counters_stale = false;  // ron_detect ran since the last ron_detect_tfe: its keys may sit on the TF counters (postproc.hip, post_tfe_ctx)
-  void* d_stem_w = nullptr;             // conv1_1 fragments + bias for the dedicated stem kernel (bf16 / f16)
-  float* d_stem_b = nullptr;
-  float stem_oscale = 1.f;              // split precision: 2^-k of the stem weights' scale
-  void* d_stem2_w = nullptr;            // conv1_2 weights as the LDS image of stem2_kernel (conv1_1 + conv1_2 + pool1 fused)
-  void* d_stem2_w1 = nullptr;           // conv1_1 weights as 16x16x32 fragments for stem2_kernel
-  float* d_stem2_b = nullptr;
-  void* d_splitk[4] = {};               // fp32 slabs of the split-K launches, one set per stream lane
+  DevBuf splitk[4];                     // fp32 slabs of the split-K launches, one set per stream lane
   int64_t splitk_bytes[4] = {};
   // RON_CFG_MULTI_STREAM: the heads of the three coarse scales run on side streams beside the main chain
-  hipStream_t side[4] = {};
-  hipEvent_t lane_ready[4] = {}, lane_done[4] = {};
+  Stream side[4];
+  Event lane_ready[4], lane_done[4];
   // optional per-launch timing (ron_profile_*): event pairs recorded on the caller's stream
   int profiling = 0;                    // calls still to be recorded (ron_profile_enable)
   std::vector<OpTiming> timing;                       // ops.size() + 1 (last = post-processing)
@@ -142,10 +154,9 @@ struct ron_ctx {
   // conv4_3 / conv5_3 with their pool from the same launch (Op::fuse_next_pool): decided once per (op, batch) - the answer is "the
   // two-output launch would not split K", which takes a tile-configuration pick: [op index] -> [batch] -> -1 unknown / 0 / 1
   std::map<int, std::vector<signed char>> fuse_pool_ok;
-  std::vector<std::vector<hipEvent_t>> pending;       // per recorded call: one event per stamp ...
-  std::vector<std::vector<int>> pending_ops;          // ... and what it marks: op index (its start), -1 = end of a lane,
-                                                      //     -2 / -3 = start / end of the post-processing stage
-  std::vector<hipEvent_t> event_pool;
+  std::vector<std::vector<Event>> pending;            // per recorded call: one event per stamp ...
+  std::vector<std::vector<int>> pending_ops;          // ... and what it marks: op index or kStamp*
+  std::vector<Event> event_pool;
   // ron_clone: an execution slot that borrows the packed weights of `weights_owner` (its own activations, scratch, streams)
   ron_ctx* weights_owner = nullptr;
   int clones = 0;                       // live slots that borrow this context's weights
@@ -155,10 +166,11 @@ struct ron_ctx {
     Tensor t;
     t.name = name; t.H = H; t.W = W; t.C = C; t.pad = pad;
     t.cstride = C >= 1024 ? C + 64 : C;
-    tensors.push_back(t);
+    tensors.push_back(std::move(t));
     tensor_index[name] = (int)tensors.size() - 1;
     return (int)tensors.size() - 1;
   }
+  int T(const std::string& name) const { return tensor_index.at(name); }
   void add_var(const std::string& rel, std::vector<int64_t> shape) {
     Var v;
     v.name = std::string(scope()) + "/" + rel;
@@ -166,6 +178,11 @@ struct ron_ctx {
     var_index[v.name] = (int)vars.size();
     vars.push_back(v);
   }
+  void add_conv_vars(const std::string& rel, int k, int cin, int cout) {      // a convolution with a bias
+    add_var(rel + "/weights", {k, k, cin, cout});
+    add_var(rel + "/biases", {cout});
+  }
+  void add_feat(int h, int w, int A) { feat_h[n_feat] = h; feat_w[n_feat] = w; feat_A[n_feat] = A; ++n_feat; }
   const Var& var(const std::string& rel) const { return vars[var_index.at(std::string(scope()) + "/" + rel)]; }
   TensorView view(int t, int n, int coff = 0, int C = -1) const {
     const Tensor& T = tensors[t];
@@ -178,206 +195,56 @@ struct ron_ctx {
 
 namespace {
 
-void add_bn_vars(ron_ctx* c, const std::string& scope, int ch) {
-  for (const char* n : {"beta", "gamma", "moving_mean", "moving_variance"}) c->add_var(scope + "/BatchNorm/" + n, {ch});
-}
-
-// The variable list (names/shapes as TensorFlow stores them; SURVEY.md 8b weight contract).
-void declare_variables(ron_ctx* c) {
-  const int nc = c->cfg.num_classes, A = c->num_anchors, c6 = c->c6;
+// ---------------------------------------------------------------------------------------------------------
+// The VGG-16 body, conv1_1 ... pool5: the same thirteen convolutions in all four networks.  What differs per family is below
+// (VggBody); how conv1_1 / conv1_2 / the pools are launched depends on the dtype and the RON_CFG_* flags alone (stem_kernel,
+// pool_fused, stem2_fused).
+// ---------------------------------------------------------------------------------------------------------
+struct BodyConv {
+  int block;                 // 0 .. 4
+  bool last;                 // the block's last convolution: its pool follows
+  int cin, cout;
+  std::string name, scope;   // "conv4_3", "conv4/conv4_3"
+};
+std::vector<BodyConv> vgg_body_convs() {
   const int widths[5] = {64, 128, 256, 512, 512};
   const int reps[5] = {2, 2, 3, 3, 3};
+  std::vector<BodyConv> v;
   int cin = 3;
   for (int b = 0; b < 5; ++b)
     for (int r = 0; r < reps[b]; ++r) {
-      const std::string s = "conv" + std::to_string(b + 1) + "/conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1);
-      c->add_var(s + "/weights", {3, 3, cin, widths[b]});
-      c->add_var(s + "/biases", {widths[b]});
+      const std::string blk = "conv" + std::to_string(b + 1), nm = blk + "_" + std::to_string(r + 1);
+      v.push_back({b, r == reps[b] - 1, cin, widths[b], nm, blk + "/" + nm});
       cin = widths[b];
     }
-  const int k6 = c->cfg.variant == RON_VARIANT_FULL ? 7 : 3;
-  c->add_var("fc6/weights", {k6, k6, 512, c6});
-  c->add_var("fc6/biases", {c6});
-  c->add_var("fc7/weights", {1, 1, c6, c6});
-  c->add_var("fc7/biases", {c6});
-  for (int i = 0; i < 4; ++i) {
-    const std::string L = std::string("reverse_module/") + kFeatLayers[i] + "_reverse";
-    const int left_c = i < 2 ? c6 : 512;
-    const int k = i == 0 ? 2 : 3;
-    c->add_var(L + "_conv_left/weights", {k, k, left_c, 512});
-    add_bn_vars(c, L + "_conv_left", 512);
-    if (i > 0) {
-      c->add_var(L + "_deconv_right/weights", {2, 2, 512, 512});
-      c->add_var(L + "_deconv_right/biases", {512});
-    }
-    c->add_var(L + "_objectness/weights", {3, 3, 512, 512});
-    add_bn_vars(c, L + "_objectness", 512);
-    c->add_var(L + "_objectness_score/weights", {3, 3, 512, 2 * A});
-    c->add_var(L + "_objectness_score/biases", {2 * A});
-    for (int blk = 1; blk <= 2; ++blk) {
-      const std::string I = L + "_inception" + std::to_string(blk);
-      const int ic = blk == 1 ? 512 : 1024;
-      c->add_var(I + "/Branch_0/Conv2d_3x3/weights", {3, 3, ic, 512});
-      c->add_var(I + "/Branch_0/Conv2d_3x3/biases", {512});
-      c->add_var(I + "/Branch_1/Conv2d_1x1/weights", {1, 1, ic, 512});
-      c->add_var(I + "/Branch_1/Conv2d_1x1/biases", {512});
-      add_bn_vars(c, I, 1024);
-    }
-    c->add_var(L + "_inception2/Conv2d_pred_3x3/weights", {3, 3, 1024, A * nc});
-    c->add_var(L + "_inception2/Conv2d_pred_3x3/biases", {A * nc});
-    c->add_var(L + "/Conv2d_0_3x3/weights", {3, 3, 512, 512});
-    add_bn_vars(c, L + "/Conv2d_0_3x3", 512);
-    c->add_var(L + "/Conv2d_1_3x3/weights", {3, 3, 512, 4 * A});
-    c->add_var(L + "/Conv2d_1_3x3/biases", {4 * A});
-  }
+  return v;
 }
-
-// ---- weight assembly: fp32 rows [npad][K] + bias [npad] -----------------------------------
-struct Rows {
-  int K = 0, npad = 0, kh = 0, kw = 0, cin = 0;
-  std::vector<float> w, b;
-  void init(int kh_, int kw_, int cin_, int n_real, int ntile) {
-    kh = kh_; kw = kw_; cin = cin_; K = kh * kw * cin; npad = round_up(n_real, ntile);
-    w.assign((size_t)npad * K, 0.f);
-    b.assign(npad, 0.f);
-  }
-  // place an HWIO filter (fh x fw, centred) at output rows [n_off, n_off + cout)
-  void place(const Var& wv, int n_off) {
-    const int fh = (int)wv.shape[0], fw = (int)wv.shape[1], ci = (int)wv.shape[2], co = (int)wv.shape[3];
-    const int oy = (kh - fh) / 2, ox = (kw - fw) / 2;
-    for (int y = 0; y < fh; ++y)
-      for (int x = 0; x < fw; ++x)
-        for (int c = 0; c < ci; ++c) {
-          const float* src = &wv.data[(((size_t)y * fw + x) * ci + c) * co];
-          const size_t k = ((size_t)(y + oy) * kw + (x + ox)) * cin + c;
-          for (int n = 0; n < co; ++n) w[(size_t)(n_off + n) * K + k] = src[n];
-        }
-  }
-  void add_bias(const Var& bv, int n_off) { for (size_t n = 0; n < bv.data.size(); ++n) b[n_off + n] += bv.data[n]; }
-  // y = gamma * (x - mean) / sqrt(var + eps) + beta  folded into rows [n_off, n_off + ch)
-  void fold_bn(const ron_ctx* c, const std::string& scope, int n_off, int ch, int bn_off = 0) {
-    const Var& be = c->var(scope + "/BatchNorm/beta"); const Var& ga = c->var(scope + "/BatchNorm/gamma");
-    const Var& mu = c->var(scope + "/BatchNorm/moving_mean"); const Var& va = c->var(scope + "/BatchNorm/moving_variance");
-    for (int n = 0; n < ch; ++n) {
-      const int q = bn_off + n;
-      const float s = ga.data[q] / sqrtf(va.data[q] + kBnEps);
-      float* row = &w[(size_t)(n_off + n) * K];
-      for (int k = 0; k < K; ++k) row[k] *= s;
-      b[n_off + n] = (b[n_off + n] - mu.data[q]) * s + be.data[q];
-    }
-  }
+struct VggBody {
+  int early_last_pad;        // halo of conv1_2 / conv2_2 / conv3_3, which feed nothing but their pool (RON: none)
+  OpKind pool5;              // OP_POOL: 2x2 stride 2 like pool1-4 (RON); OP_POOL3: 3x3 stride 1 (SSD, nets/ssd_vgg_512.py:391)
+  int pool5_pad;             // halo of pool5 = the reach of what reads it: fc6 (7x7, or 3x3 at rate 3), conv6 (3x3 at rate 6)
 };
+const VggBody kRonBody = {0, OP_POOL, 3}, kSsdBody = {1, OP_POOL3, 6};
+const VggBody& vgg_body(const ron_ctx* c) { return c->is_ssd() ? kSsdBody : kRonBody; }
 
-int upload(ron_ctx* c, const Rows& r, int cout) {
-  PackedConv p;
-  std::vector<uint8_t> bytes = pack_conv_weights(r.w, r.npad, c->cfg.dtype, &p.oscale);
-  p.w_bytes = (int64_t)bytes.size();
-  p.Npad = r.npad; p.Cout = cout;
-  RON_HIP_CHECK(ron::dev_malloc(&p.d_w, bytes.size()));
-  RON_HIP_CHECK(ron::dev_memcpy(p.d_w, bytes.data(), bytes.size(), hipMemcpyHostToDevice));
-  if (dtype_is_half(c->cfg.dtype) && r.kh == 3 && r.kw == 3 && r.cin == 64 && r.npad == cout && cout % 64 == 0) {
-    const std::vector<uint8_t> img = pack_conv_c64_weights(r.w, r.npad, c->cfg.dtype);
-    RON_HIP_CHECK(ron::dev_malloc(&p.d_w_c64, img.size()));
-    RON_HIP_CHECK(ron::dev_memcpy(p.d_w_c64, img.data(), img.size(), hipMemcpyHostToDevice));
-  }
-  RON_HIP_CHECK(ron::dev_malloc((void**)&p.d_bias, r.b.size() * sizeof(float)));
-  RON_HIP_CHECK(ron::dev_memcpy(p.d_bias, r.b.data(), r.b.size() * sizeof(float), hipMemcpyHostToDevice));
-  c->packed.push_back(p);
-  return (int)c->packed.size() - 1;
+// slim.max_pool2d [2, 2] stride 2 SAME; a k x k convolution with stride s over a map zero-padded by p
+int pool2_out(int h) { return (h + 1) / 2; }
+int conv_out(int h, int k, int stride, int p) { return (h + 2 * p - k) / stride + 1; }
+
+bool stem_kernel(const ron_config& cfg) { return cfg.dtype != RON_DTYPE_F32; }      // bf16 / f16 / f16x3; fp32: conv1_1 as im2col + GEMM
+// blocks 1..3 feed nothing but their pool: with RON_CFG_FUSE_POOLS the h x w map of the block's last conv is never written
+bool pool_fused(const ron_config& cfg, int h, int w) {
+  return (cfg.flags & RON_CFG_FUSE_POOLS) && !((cfg.flags & RON_CFG_NO_ODD_POOL_FUSE) && ((h | w) & 1));
 }
-
-// returns packed index (>= 0) or negative status
-int pack_plain(ron_ctx* c, const std::string& scope, bool bn) {
-  const Var& w = c->var(scope + "/weights");
-  const int cout = (int)w.shape[3];
-  Rows r;
-  r.init((int)w.shape[0], (int)w.shape[1], (int)w.shape[2], cout, conv_n_tile(cout));
-  r.place(w, 0);
-  if (bn) r.fold_bn(c, scope, 0, cout); else r.add_bias(c->var(scope + "/biases"), 0);
-  return upload(c, r, cout);
+// conv1_1 + conv1_2 + pool1 as one kernel (stem.hip): neither full-resolution 64-channel map touches HBM
+bool stem2_fused(const ron_config& cfg) {
+  return (cfg.flags & RON_CFG_FUSE_POOLS) && !(cfg.flags & RON_CFG_NO_STEM2) && dtype_is_half(cfg.dtype) && cfg.img_h % 8 == 0 &&
+         cfg.img_w % 32 == 0;
 }
-
-// The class and box convolutions of an SSD feature layer (nets/ssd_vgg_300.py:403-431: both 3x3 over the same map) as ONE
-// convolution: rows [0, A*classes) conv_cls, rows [split_n, split_n + 4A) conv_loc, split_n = A*classes rounded up to 8 (a lane's
-// vector of adjacent channels then never straddles the two outputs).  The input is staged once instead of twice and the box
-// columns ride in what would be padding of the class convolution's last column tile (block4: 84 + 16 -> 104 of 128 columns).
-int pack_box_pair(ron_ctx* c, const std::string& L) {
-  const Var& wc = c->var(L + "/conv_cls/weights");
-  const Var& wl = c->var(L + "/conv_loc/weights");
-  const int n_cls = (int)wc.shape[3], n_loc = (int)wl.shape[3], split_n = round_up(n_cls, 8);
-  Rows r;
-  r.init((int)wc.shape[0], (int)wc.shape[1], (int)wc.shape[2], split_n + n_loc, conv_n_tile(split_n + n_loc));
-  r.place(wc, 0);
-  r.add_bias(c->var(L + "/conv_cls/biases"), 0);
-  r.place(wl, split_n);
-  r.add_bias(c->var(L + "/conv_loc/biases"), split_n);
-  const int idx = upload(c, r, split_n + n_loc);
-  if (idx >= 0) { c->packed[idx].split_n = split_n; c->packed[idx].split_first = n_cls; }
-  return idx;
-}
-
-int pack_stem(ron_ctx* c, const std::string& scope) {
-  const Var& w = c->var(scope + "/weights");
-  const int cout = (int)w.shape[3], chunk = conv_k_chunk(c->cfg.dtype);
-  Rows r;
-  r.init(1, 1, chunk, cout, conv_n_tile(cout));
-  for (int k = 0; k < 27; ++k) for (int n = 0; n < cout; ++n) r.w[(size_t)n * chunk + k] = w.data[(size_t)k * cout + n];
-  r.add_bias(c->var(scope + "/biases"), 0);
-  return upload(c, r, cout);
-}
-
-int pack_deconv(ron_ctx* c, const std::string& scope) {
-  const Var& w = c->var(scope + "/weights");     // [kh, kw, Cout, Cin]
-  const Var& bv = c->var(scope + "/biases");
-  const int taps = (int)(w.shape[0] * w.shape[1]), co = (int)w.shape[2], ci = (int)w.shape[3];
-  Rows r;
-  r.init(1, 1, ci, taps * co, conv_n_tile(taps * co));
-  memcpy(r.w.data(), w.data.data(), w.data.size() * sizeof(float));
-  for (int t = 0; t < taps; ++t) for (int n = 0; n < co; ++n) r.b[t * co + n] = bv.data[n];
-  return upload(c, r, taps * co);
-}
-
-// Everything that reads the reference map of a scale, as ONE convolution with 2048 outputs = the per-scale "hcat" tensor:
-// rows 0..511 objectness hidden (3x3 conv + BN), 512..1023 box hidden (3x3 conv + BN), 1024..1535 inception-1 branch 0 (3x3 + bias,
-// BN channels 0..511 of the concat), 1536..2047 inception-1 branch 1 (1x1 + bias, BN channels 512..1023) -- the 1x1 filter sits in
-// the CENTRE tap of its rows and those column tiles run that tap's K steps only (ConvLaunch::center_from = 1536), so it costs
-// its own MACs, not nine times them.
-int pack_trio3(ron_ctx* c, const std::string& L) {
-  Rows r;
-  r.init(3, 3, 512, 2048, 256);
-  r.place(c->var(L + "_objectness/weights"), 0);
-  r.fold_bn(c, L + "_objectness", 0, 512);
-  r.place(c->var(L + "/Conv2d_0_3x3/weights"), 512);
-  r.fold_bn(c, L + "/Conv2d_0_3x3", 512, 512);
-  r.place(c->var(L + "_inception1/Branch_0/Conv2d_3x3/weights"), 1024);
-  r.add_bias(c->var(L + "_inception1/Branch_0/Conv2d_3x3/biases"), 1024);
-  r.fold_bn(c, L + "_inception1", 1024, 512, 0);
-  r.place(c->var(L + "_inception1/Branch_1/Conv2d_1x1/weights"), 1536);
-  r.add_bias(c->var(L + "_inception1/Branch_1/Conv2d_1x1/biases"), 1536);
-  r.fold_bn(c, L + "_inception1", 1536, 512, 512);
-  return upload(c, r, 2048);
-}
-
-// Both branches of an "inception" block (nets/ron_vgg_320.py:378-397) as one convolution over the block's input: rows 0..511 the 3x3
-// branch, 512..1023 the 1x1 branch in the centre tap (center_from = 512); each conv + bias, then its half of the BatchNorm that
-// follows the concat, ReLU in the kernel epilogue.
-int pack_inception(ron_ctx* c, const std::string& I) {
-  const Var& w3 = c->var(I + "/Branch_0/Conv2d_3x3/weights");
-  Rows r;
-  r.init(3, 3, (int)w3.shape[2], 1024, 256);
-  r.place(w3, 0);
-  r.add_bias(c->var(I + "/Branch_0/Conv2d_3x3/biases"), 0);
-  r.fold_bn(c, I, 0, 512, 0);
-  r.place(c->var(I + "/Branch_1/Conv2d_1x1/weights"), 512);
-  r.add_bias(c->var(I + "/Branch_1/Conv2d_1x1/biases"), 512);
-  r.fold_bn(c, I, 512, 512, 512);
-  return upload(c, r, 1024);
-}
-
 
 // ---------------------------------------------------------------------------------------------------------
 // SSD (nets/ssd_vgg_512.py:364-460, nets/ssd_vgg_300.py:434-523; multibox heads nets/ssd_vgg_300.py:403-431): one description per
-// variant, read by declare_variables_ssd, declare_tensors_ssd, make_anchors_ssd, the op list of ron_finalize_weights and plan_groups.
+// variant, read by declare_ssd_variables, declare_ssd_tensors, make_anchors, build_ssd_tail and head_plan.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int kSsdMaxFeat = 7, kSsdMaxExtra = 5;
 struct SsdExtra { int mid, outc, k, stride, cpad; };      // block8 ...: 1x1 to `mid` channels, then k x k (stride, zero padding cpad) to `outc`
@@ -411,102 +278,471 @@ const SsdSpec kSsd300 = {
     4, {{256, 512, 3, 2, 1}, {128, 256, 3, 2, 1}, {128, 256, 3, 1, 0}, {128, 256, 3, 1, 0}},
     {{21., 45.}, {45., 99.}, {99., 153.}, {153., 207.}, {207., 261.}, {261., 315.}},
     {8, 16, 32, 64, 100, 300}};
+// SSDNet.default_params anchors with ssd_anchor_one_layer (nets/ssd_vgg_512.py:286-338): anchors per cell are [s0 square,
+// sqrt(s0*s1) square, s0 at each of the first A - 2 ratios]
+const double kSsdRatios[4] = {2, .5, 3, 1. / 3};
+// RONNet.default_params (nets/ron_vgg_320.py:97-124), coarse -> fine like kFeatLayers: every size at every ratio
+const struct { double sizes[4][2], ratios[5], steps[4]; } kRonAnchors = {
+    {{224., 256.}, {160., 192.}, {96., 128.}, {32., 64.}}, {1., 2., 3., 1. / 2, 1. / 3}, {64, 32, 16, 8}};
 const SsdSpec* ssd_spec(int variant) {
   return variant == RON_VARIANT_SSD512 ? &kSsd512 : (variant == RON_VARIANT_SSD300 ? &kSsd300 : nullptr);
 }
+std::string ssd_block(int b) { return "block" + std::to_string(8 + b); }
 std::string ssd_extra_conv(const SsdExtra& e) { return "conv" + std::to_string(e.k) + "x" + std::to_string(e.k); }
-// slim.max_pool2d [2, 2] stride 2 SAME; a k x k convolution with stride s over a map zero-padded by p
-int pool2_out(int h) { return (h + 1) / 2; }
-int conv_out(int h, int k, int stride, int p) { return (h + 2 * p - k) / stride + 1; }
 // Feature layers whose loc + cls convolutions run as one two-output launch (block4: 64 x 64 / 38 x 38, block7: 32 x 32 / 19 x 19).
-// The small maps' heads stay two members of a grouped launch with the next block's 1x1 (plan_groups).
+// The small maps' heads stay two members of a grouped launch with the next block's 1x1 (head_plan).
 const int kSsdPairedHeads = 2;
 
-void declare_variables_ssd(ron_ctx* c) {
-  const SsdSpec& S = *ssd_spec(c->cfg.variant);
-  const int nc = c->cfg.num_classes;
-  const int widths[5] = {64, 128, 256, 512, 512};
-  const int reps[5] = {2, 2, 3, 3, 3};
-  int cin = 3;
-  for (int b = 0; b < 5; ++b)
-    for (int r = 0; r < reps[b]; ++r) {
-      const std::string s = "conv" + std::to_string(b + 1) + "/conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1);
-      c->add_var(s + "/weights", {3, 3, cin, widths[b]});
-      c->add_var(s + "/biases", {widths[b]});
-      cin = widths[b];
+// ---- step 1: the variable list (names/shapes as TensorFlow stores them; SURVEY.md 8b weight contract) ----------------------
+void add_bn_vars(ron_ctx* c, const std::string& scope, int ch) {
+  for (const char* n : {"beta", "gamma", "moving_mean", "moving_variance"}) c->add_var(scope + "/BatchNorm/" + n, {ch});
+}
+
+void declare_ron_variables(ron_ctx* c) {
+  const int nc = c->cfg.num_classes, A = c->num_anchors, c6 = c->c6;
+  c->add_conv_vars("fc6", c->cfg.variant == RON_VARIANT_FULL ? 7 : 3, 512, c6);
+  c->add_conv_vars("fc7", 1, c6, c6);
+  for (int i = 0; i < 4; ++i) {
+    const std::string L = std::string("reverse_module/") + kFeatLayers[i] + "_reverse";
+    const int left_c = i < 2 ? c6 : 512;
+    const int k = i == 0 ? 2 : 3;
+    c->add_var(L + "_conv_left/weights", {k, k, left_c, 512});
+    add_bn_vars(c, L + "_conv_left", 512);
+    if (i > 0) c->add_conv_vars(L + "_deconv_right", 2, 512, 512);
+    c->add_var(L + "_objectness/weights", {3, 3, 512, 512});
+    add_bn_vars(c, L + "_objectness", 512);
+    c->add_conv_vars(L + "_objectness_score", 3, 512, 2 * A);
+    for (int blk = 1; blk <= 2; ++blk) {
+      const std::string I = L + "_inception" + std::to_string(blk);
+      const int ic = blk == 1 ? 512 : 1024;
+      c->add_conv_vars(I + "/Branch_0/Conv2d_3x3", 3, ic, 512);
+      c->add_conv_vars(I + "/Branch_1/Conv2d_1x1", 1, ic, 512);
+      add_bn_vars(c, I, 1024);
     }
-  c->add_var("conv6/weights", {3, 3, 512, 1024});
-  c->add_var("conv6/biases", {1024});
-  c->add_var("conv7/weights", {1, 1, 1024, 1024});
-  c->add_var("conv7/biases", {1024});
+    c->add_conv_vars(L + "_inception2/Conv2d_pred_3x3", 3, 1024, A * nc);
+    c->add_var(L + "/Conv2d_0_3x3/weights", {3, 3, 512, 512});
+    add_bn_vars(c, L + "/Conv2d_0_3x3", 512);
+    c->add_conv_vars(L + "/Conv2d_1_3x3", 3, 512, 4 * A);
+  }
+}
+
+void declare_ssd_variables(ron_ctx* c, const SsdSpec& S) {
+  c->add_conv_vars("conv6", 3, 512, 1024);
+  c->add_conv_vars("conv7", 1, 1024, 1024);
   int inc = 1024;
   for (int b = 0; b < S.n_extra; ++b) {
     const SsdExtra& e = S.extra[b];
-    const std::string B = "block" + std::to_string(8 + b);
-    c->add_var(B + "/conv1x1/weights", {1, 1, inc, e.mid});
-    c->add_var(B + "/conv1x1/biases", {e.mid});
-    c->add_var(B + "/" + ssd_extra_conv(e) + "/weights", {e.k, e.k, e.mid, e.outc});
-    c->add_var(B + "/" + ssd_extra_conv(e) + "/biases", {e.outc});
+    c->add_conv_vars(ssd_block(b) + "/conv1x1", 1, inc, e.mid);
+    c->add_conv_vars(ssd_block(b) + "/" + ssd_extra_conv(e), e.k, e.mid, e.outc);
     inc = e.outc;
   }
   for (int i = 0; i < S.n_feat; ++i) {
     const std::string L = std::string(S.feat[i]) + "_box";
     if (i == 0) c->add_var(L + "/L2Normalization/gamma", {512});
-    c->add_var(L + "/conv_loc/weights", {3, 3, S.feat_c[i], S.anchors[i] * 4});
-    c->add_var(L + "/conv_loc/biases", {S.anchors[i] * 4});
-    c->add_var(L + "/conv_cls/weights", {3, 3, S.feat_c[i], S.anchors[i] * nc});
-    c->add_var(L + "/conv_cls/biases", {S.anchors[i] * nc});
+    c->add_conv_vars(L + "/conv_loc", 3, S.feat_c[i], S.anchors[i] * 4);
+    c->add_conv_vars(L + "/conv_cls", 3, S.feat_c[i], S.anchors[i] * c->cfg.num_classes);
   }
 }
 
-void declare_tensors_ssd(ron_ctx* c) {
-  const SsdSpec& S = *ssd_spec(c->cfg.variant);
-  const int H = c->cfg.img_h, W = c->cfg.img_w;
-  c->add_tensor("im2col", H, W, conv_k_chunk(c->cfg.dtype), 0);
-  const int widths[5] = {64, 128, 256, 512, 512};
-  const int reps[5] = {2, 2, 3, 3, 3};
-  int h = H, w = W;
-  int fh[kSsdMaxFeat], fw[kSsdMaxFeat];
-  for (int b = 0; b < 5; ++b) {
-    for (int r = 0; r < reps[b]; ++r)
-      c->add_tensor("conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1), h, w, widths[b], 1);
-    if (b == 3) { fh[0] = h; fw[0] = w; }                                                     // block4 = conv4_3
-    if (b < 4) { h = pool2_out(h); w = pool2_out(w); }                                        // pool5: 3x3 stride 1
-    c->add_tensor("pool" + std::to_string(b + 1), h, w, widths[b], b == 4 ? 6 : 1);   // pool5 feeds the rate-6 conv
+void declare_variables(ron_ctx* c) {
+  for (const BodyConv& bc : vgg_body_convs()) c->add_conv_vars(bc.scope, 3, bc.cin, bc.cout);
+  if (const SsdSpec* S = ssd_spec(c->cfg.variant)) declare_ssd_variables(c, *S);
+  else declare_ron_variables(c);
+}
+
+// ---- step 2: the tensors, and with them the head layers' maps (feat_h / feat_w / feat_A) ------------------------------------
+void declare_body_tensors(ron_ctx* c, const VggBody& body) {
+  int h = c->cfg.img_h, w = c->cfg.img_w;
+  c->add_tensor("im2col", h, w, conv_k_chunk(c->cfg.dtype), 0);
+  for (const BodyConv& bc : vgg_body_convs()) {
+    c->add_tensor(bc.name, h, w, bc.cout, bc.last && bc.block < 3 ? body.early_last_pad : 1);
+    if (!bc.last) continue;
+    const bool pool5 = bc.block == 4;
+    if (!pool5 || body.pool5 == OP_POOL) { h = pool2_out(h); w = pool2_out(w); }
+    c->add_tensor("pool" + std::to_string(bc.block + 1), h, w, bc.cout, pool5 ? body.pool5_pad : 1);
   }
-  c->add_tensor("block4_norm", fh[0], fw[0], 512, 1);
+}
+
+void declare_ron_tensors(ron_ctx* c) {
+  const int H = c->cfg.img_h, W = c->cfg.img_w, p5 = c->T("pool5"), h = c->tensors[p5].H, w = c->tensors[p5].W;
+  c->add_tensor("fc6", h, w, c->c6, 1);
+  c->add_tensor("fc7", h, w, c->c6, 0);
+  for (int i = 0; i < 4; ++i) {
+    const int s_h = (H / 64) << i, s_w = (W / 64) << i;
+    c->add_feat(s_h, s_w, c->num_anchors);
+    const std::string L = kFeatLayers[i];
+    c->add_tensor(L + "_ref", s_h, s_w, 512, 1);
+    c->add_tensor(L + "_hcat", s_h, s_w, 2048, 1);
+    c->add_tensor(L + "_inc2", s_h, s_w, 1024, 1);
+  }
+}
+
+void declare_ssd_tensors(ron_ctx* c, const SsdSpec& S) {
+  const int b4 = c->T("conv4_3"), p5 = c->T("pool5");
+  int h = c->tensors[p5].H, w = c->tensors[p5].W;
+  c->has_obj = false;
+  c->add_feat(c->tensors[b4].H, c->tensors[b4].W, S.anchors[0]);                              // block4 = conv4_3
+  c->add_tensor("block4_norm", c->tensors[b4].H, c->tensors[b4].W, 512, 1);
   c->add_tensor("conv6", h, w, 1024, 0);
   c->add_tensor("conv7", h, w, 1024, 1);
-  fh[1] = h; fw[1] = w;
+  c->add_feat(h, w, S.anchors[1]);
   for (int b = 0; b < S.n_extra; ++b) {
     const SsdExtra& e = S.extra[b];
-    const std::string B = "block" + std::to_string(8 + b);
-    c->add_tensor(B + "_mid", h, w, e.mid, 1);             // pad2d(1) of the reference = the halo (unused by the VALID blocks)
+    c->add_tensor(ssd_block(b) + "_mid", h, w, e.mid, 1);             // pad2d(1) of the reference = the halo (unused by the VALID blocks)
     h = conv_out(h, e.k, e.stride, e.cpad); w = conv_out(w, e.k, e.stride, e.cpad);
-    c->add_tensor(B, h, w, e.outc, 1);
-    fh[2 + b] = h; fw[2 + b] = w;
+    c->add_tensor(ssd_block(b), h, w, e.outc, 1);
+    c->add_feat(h, w, S.anchors[2 + b]);
   }
-  c->n_feat = S.n_feat;
-  c->has_obj = false;
-  for (int i = 0; i < S.n_feat; ++i) { c->feat_h[i] = fh[i]; c->feat_w[i] = fw[i]; c->feat_A[i] = S.anchors[i]; }
 }
 
-// SSDNet.default_params anchors (nets/ssd_vgg_512.py:79-102, nets/ssd_vgg_300.py:94-124) with ssd_anchor_one_layer (:286-338):
-// anchors per cell are [s0 square, sqrt(s0*s1) square, s0 at each ratio]; centres as in the RON version.
-int make_anchors_ssd(ron_ctx* c) {
-  const SsdSpec& S = *ssd_spec(c->cfg.variant);
+void declare_tensors(ron_ctx* c) {
+  declare_body_tensors(c, vgg_body(c));
+  if (const SsdSpec* S = ssd_spec(c->cfg.variant)) declare_ssd_tensors(c, *S);
+  else declare_ron_tensors(c);
+}
+
+// ---- step 3: device memory of the tensors a launch plan of this configuration touches ---------------------------------------
+int allocate_tensors(ron_ctx* c) {
+  const ron_config& cfg = c->cfg;
+  for (auto& t : c->tensors) {
+    if (t.name == "im2col" && stem_kernel(cfg)) continue;
+    if ((t.name == "conv1_2" || t.name == "conv2_2" || t.name == "conv3_3") && pool_fused(cfg, t.H, t.W)) continue;
+    if (t.name == "conv1_1" && stem2_fused(cfg)) continue;
+    t.bytes = TensorView::halo_pixels(cfg.max_batch, t.H, t.W, t.pad) * t.cstride * c->esz();     // shared halos, conv_mfma.h
+    if (t.bytes >= ((int64_t)1 << 32)) {
+      ron::set_error("tensor %s needs %lld bytes for max_batch %d: above the 4 GiB buffer-addressing limit; lower max_batch",
+                     t.name.c_str(), (long long)t.bytes, cfg.max_batch);
+      return RON_ERR_INVALID;
+    }
+    RON_HIP_CHECK(ron::dev_malloc(t.d.put(), (size_t)t.bytes));
+    RON_HIP_CHECK(ron::dev_memset(t.d, 0, (size_t)t.bytes));     // halos stay zero forever: kernels write interiors only
+  }
+  return RON_OK;
+}
+
+// ---- step 4: anchors of the head layers, on the device ---------------------------------------------------------------------
+int make_anchors(ron_ctx* c) {
+  const SsdSpec* S = ssd_spec(c->cfg.variant);
   const int H = c->cfg.img_h, W = c->cfg.img_w;
-  const double ratios[4] = {2, .5, 3, 1. / 3};
-  for (int i = 0; i < S.n_feat; ++i) {
+  for (int i = 0; i < c->n_feat; ++i) {
     const int fh = c->feat_h[i], fw = c->feat_w[i], A = c->feat_A[i];
     std::vector<float> y(fh * fw), x(fh * fw), hh(A), ww(A);
-    int rc = ron_ssd_anchor_one_layer(H, W, fh, fw, S.sizes[i], 2, ratios, A - 2, S.steps[i], 0.5, y.data(), x.data(), hh.data(), ww.data());
+    const int rc = S ? ron_ssd_anchor_one_layer(H, W, fh, fw, S->sizes[i], 2, kSsdRatios, A - 2, S->steps[i], 0.5, y.data(), x.data(),
+                                                hh.data(), ww.data())
+                     : ron_anchor_one_layer(H, W, fh, fw, kRonAnchors.sizes[i], 2, kRonAnchors.ratios, 5, kRonAnchors.steps[i], 0.5,
+                                            y.data(), x.data(), hh.data(), ww.data());
     if (rc) return rc;
     const std::vector<float>* src[4] = {&y, &x, &hh, &ww};
-    for (int k = 0; k < 4; ++k) {
-      RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_anchor[i][k], src[k]->size() * sizeof(float)));
-      RON_HIP_CHECK(ron::dev_memcpy(c->d_anchor[i][k], src[k]->data(), src[k]->size() * sizeof(float), hipMemcpyHostToDevice));
+    for (int k = 0; k < 4; ++k) RON_HIP_CHECK(ron::dev_upload(&c->anchor[i][k], src[k]->data(), src[k]->size() * sizeof(float)));
+  }
+  return RON_OK;
+}
+
+// ---- weight assembly: fp32 rows [npad][K] + bias [npad] -----------------------------------
+struct Rows {
+  int K = 0, npad = 0, kh = 0, kw = 0, cin = 0;
+  int cout = 0;                         // rows that are stored (<= npad)
+  int split_n = 0, split_first = 0;     // pack_box_pair
+  int64_t placed = 0;                   // weights of the variables placed here: the convolution's MACs per output pixel
+  std::vector<float> w, b;
+  Rows(int kh_, int kw_, int cin_, int n_real, int ntile) {
+    kh = kh_; kw = kw_; cin = cin_; K = kh * kw * cin; cout = n_real; npad = round_up(n_real, ntile);
+    w.assign((size_t)npad * K, 0.f);
+    b.assign(npad, 0.f);
+  }
+  // place an HWIO filter (fh x fw, centred) at output rows [n_off, n_off + cout)
+  void place(const Var& wv, int n_off) {
+    const int fh = (int)wv.shape[0], fw = (int)wv.shape[1], ci = (int)wv.shape[2], co = (int)wv.shape[3];
+    const int oy = (kh - fh) / 2, ox = (kw - fw) / 2;
+    for (int y = 0; y < fh; ++y)
+      for (int x = 0; x < fw; ++x)
+        for (int c = 0; c < ci; ++c) {
+          const float* src = &wv.data[(((size_t)y * fw + x) * ci + c) * co];
+          const size_t k = ((size_t)(y + oy) * kw + (x + ox)) * cin + c;
+          for (int n = 0; n < co; ++n) w[(size_t)(n_off + n) * K + k] = src[n];
+        }
+    placed += wv.numel();
+  }
+  void add_bias(const Var& bv, int n_off) { for (size_t n = 0; n < bv.data.size(); ++n) b[n_off + n] += bv.data[n]; }
+  // y = gamma * (x - mean) / sqrt(var + eps) + beta  folded into rows [n_off, n_off + ch)
+  void fold_bn(const ron_ctx* c, const std::string& scope, int n_off, int ch, int bn_off = 0) {
+    const Var& be = c->var(scope + "/BatchNorm/beta"); const Var& ga = c->var(scope + "/BatchNorm/gamma");
+    const Var& mu = c->var(scope + "/BatchNorm/moving_mean"); const Var& va = c->var(scope + "/BatchNorm/moving_variance");
+    for (int n = 0; n < ch; ++n) {
+      const int q = bn_off + n;
+      const float s = ga.data[q] / sqrtf(va.data[q] + kBnEps);
+      float* row = &w[(size_t)(n_off + n) * K];
+      for (int k = 0; k < K; ++k) row[k] *= s;
+      b[n_off + n] = (b[n_off + n] - mu.data[q]) * s + be.data[q];
     }
+  }
+  // a 512-channel branch of an inception block at rows [n_off, n_off + 512): conv + bias, then its channels [bn_off, bn_off + 512) of
+  // the BatchNorm that follows the concat
+  void place_branch(const ron_ctx* c, const std::string& conv, const std::string& bn, int n_off, int bn_off) {
+    place(c->var(conv + "/weights"), n_off);
+    add_bias(c->var(conv + "/biases"), n_off);
+    fold_bn(c, bn, n_off, 512, bn_off);
+  }
+};
+
+Rows pack_plain(const ron_ctx* c, const std::string& scope, bool bn) {
+  const Var& w = c->var(scope + "/weights");
+  const int cout = (int)w.shape[3];
+  Rows r((int)w.shape[0], (int)w.shape[1], (int)w.shape[2], cout, conv_n_tile(cout));
+  r.place(w, 0);
+  if (bn) r.fold_bn(c, scope, 0, cout); else r.add_bias(c->var(scope + "/biases"), 0);
+  return r;
+}
+
+// The class and box convolutions of an SSD feature layer (nets/ssd_vgg_300.py:403-431: both 3x3 over the same map) as ONE
+// convolution: rows [0, A*classes) conv_cls, rows [split_n, split_n + 4A) conv_loc, split_n = A*classes rounded up to 8 (a lane's
+// vector of adjacent channels then never straddles the two outputs).  The input is staged once instead of twice and the box
+// columns ride in what would be padding of the class convolution's last column tile (block4: 84 + 16 -> 104 of 128 columns).
+Rows pack_box_pair(const ron_ctx* c, const std::string& L) {
+  const Var& wc = c->var(L + "/conv_cls/weights");
+  const Var& wl = c->var(L + "/conv_loc/weights");
+  const int n_cls = (int)wc.shape[3], n_loc = (int)wl.shape[3], split_n = round_up(n_cls, 8);
+  Rows r((int)wc.shape[0], (int)wc.shape[1], (int)wc.shape[2], split_n + n_loc, conv_n_tile(split_n + n_loc));
+  r.place(wc, 0);
+  r.add_bias(c->var(L + "/conv_cls/biases"), 0);
+  r.place(wl, split_n);
+  r.add_bias(c->var(L + "/conv_loc/biases"), split_n);
+  r.split_n = split_n; r.split_first = n_cls;
+  return r;
+}
+
+// conv1_1 for the GEMM kernel (fp32 contexts): its 27 taps as the first elements of one K chunk of the im2col tensor
+Rows pack_stem(const ron_ctx* c, const std::string& scope) {
+  const Var& w = c->var(scope + "/weights");
+  const int cout = (int)w.shape[3], chunk = conv_k_chunk(c->cfg.dtype);
+  Rows r(1, 1, chunk, cout, conv_n_tile(cout));
+  for (int k = 0; k < 27; ++k) for (int n = 0; n < cout; ++n) r.w[(size_t)n * chunk + k] = w.data[(size_t)k * cout + n];
+  r.placed = w.numel();
+  r.add_bias(c->var(scope + "/biases"), 0);
+  return r;
+}
+
+Rows pack_deconv(const ron_ctx* c, const std::string& scope) {
+  const Var& w = c->var(scope + "/weights");     // [kh, kw, Cout, Cin]
+  const Var& bv = c->var(scope + "/biases");
+  const int taps = (int)(w.shape[0] * w.shape[1]), co = (int)w.shape[2], ci = (int)w.shape[3];
+  Rows r(1, 1, ci, taps * co, conv_n_tile(taps * co));
+  memcpy(r.w.data(), w.data.data(), w.data.size() * sizeof(float));
+  r.placed = w.numel();
+  for (int t = 0; t < taps; ++t) for (int n = 0; n < co; ++n) r.b[t * co + n] = bv.data[n];
+  return r;
+}
+
+// Everything that reads the reference map of a scale, as ONE convolution with 2048 outputs = the per-scale "hcat" tensor:
+// rows 0..511 objectness hidden (3x3 conv + BN), 512..1023 box hidden (3x3 conv + BN), 1024..1535 inception-1 branch 0 (3x3 + bias,
+// BN channels 0..511 of the concat), 1536..2047 inception-1 branch 1 (1x1 + bias, BN channels 512..1023) -- the 1x1 filter sits in
+// the CENTRE tap of its rows and those column tiles run that tap's K steps only (ConvLaunch::center_from = 1536), so it costs
+// its own MACs, not nine times them.
+Rows pack_trio3(const ron_ctx* c, const std::string& L) {
+  Rows r(3, 3, 512, 2048, 256);
+  r.place(c->var(L + "_objectness/weights"), 0);
+  r.fold_bn(c, L + "_objectness", 0, 512);
+  r.place(c->var(L + "/Conv2d_0_3x3/weights"), 512);
+  r.fold_bn(c, L + "/Conv2d_0_3x3", 512, 512);
+  r.place_branch(c, L + "_inception1/Branch_0/Conv2d_3x3", L + "_inception1", 1024, 0);
+  r.place_branch(c, L + "_inception1/Branch_1/Conv2d_1x1", L + "_inception1", 1536, 512);
+  return r;
+}
+
+// Both branches of an "inception" block (nets/ron_vgg_320.py:378-397) as one convolution over the block's input: rows 0..511 the 3x3
+// branch, 512..1023 the 1x1 branch in the centre tap (center_from = 512); each conv + bias, then its half of the BatchNorm that
+// follows the concat, ReLU in the kernel epilogue.
+Rows pack_inception(const ron_ctx* c, const std::string& I) {
+  const Var& w3 = c->var(I + "/Branch_0/Conv2d_3x3/weights");
+  Rows r(3, 3, (int)w3.shape[2], 1024, 256);
+  r.place_branch(c, I + "/Branch_0/Conv2d_3x3", I, 0, 0);
+  r.place_branch(c, I + "/Branch_1/Conv2d_1x1", I, 512, 512);
+  return r;
+}
+
+// ---- the op list ------------------------------------------------------------------------------------------------------------
+double conv_flops(int64_t weights, int out_pixels) { return 2.0 * (double)weights * out_pixels; }
+
+Op conv_op(const std::string& name, int in, int out, int k, int cpad, int relu, int Ho, int Wo) {
+  Op o;
+  o.kind = OP_CONV; o.name = name; o.in = in; o.out = out;
+  o.kh = o.kw = k; o.cpad = cpad; o.relu = relu; o.Ho = Ho; o.Wo = Wo;
+  return o;
+}
+Op head_op(const std::string& name, int in, int layer, int kind, const ron_ctx* c) {      // 3x3 logits into the caller's buffer
+  Op o = conv_op(name, in, -2, 3, 1, 0, c->feat_h[layer], c->feat_w[layer]);
+  o.head_kind = kind; o.head_layer = layer;
+  return o;
+}
+
+// Packs `r` for the kernels, uploads it and appends `o` as the convolution that runs it, credited with the MACs of the weights
+// that were placed into `r`.
+int add_conv(ron_ctx* c, Op o, const Rows& r) {
+  PackedConv p;
+  const std::vector<uint8_t> bytes = pack_conv_weights(r.w, r.npad, c->cfg.dtype, &p.oscale);
+  p.w_bytes = (int64_t)bytes.size();
+  p.Npad = r.npad; p.Cout = r.cout; p.split_n = r.split_n; p.split_first = r.split_first;
+  RON_HIP_CHECK(ron::dev_upload(&p.w, bytes.data(), bytes.size()));
+  if (dtype_is_half(c->cfg.dtype) && r.kh == 3 && r.kw == 3 && r.cin == 64 && r.npad == r.cout && r.cout % 64 == 0) {
+    const std::vector<uint8_t> img = pack_conv_c64_weights(r.w, r.npad, c->cfg.dtype);
+    RON_HIP_CHECK(ron::dev_upload(&p.w_c64, img.data(), img.size()));
+  }
+  RON_HIP_CHECK(ron::dev_upload(&p.bias, r.b.data(), r.b.size() * sizeof(float)));
+  c->own.packed.push_back(std::move(p));
+  o.packed = (int)c->own.packed.size() - 1;
+  o.flops = conv_flops(r.placed, o.Ho * o.Wo);
+  c->ops.push_back(o);
+  return RON_OK;
+}
+
+int upload_u16(DevBuf* b, const std::vector<uint16_t>& v) { RON_HIP_CHECK(ron::dev_upload(b, v.data(), v.size() * 2)); return RON_OK; }
+int upload_bias64(DevBuf* b, const Var& v) { RON_HIP_CHECK(ron::dev_upload(b, v.data.data(), 64 * sizeof(float))); return RON_OK; }
+
+int build_body(ron_ctx* c, const VggBody& body) {
+  const ron_config& cfg = c->cfg;
+  Weights& W = c->own;
+  int rc, h = cfg.img_h, w = cfg.img_w, prev = c->T("im2col");
+  if (!stem_kernel(cfg)) {
+    Op o; o.kind = OP_IM2COL; o.name = "im2col"; o.out = prev;
+    c->ops.push_back(o);
+  }
+  for (const BodyConv& bc : vgg_body_convs()) {
+    const bool first = bc.cin == 3;
+    if (first && stem_kernel(cfg)) {
+      const Var& w1 = c->var(bc.scope + "/weights");
+      std::vector<uint16_t> frags;
+      if (cfg.dtype == RON_DTYPE_F16X3) W.stem_oscale = stem_pack_weights_split(w1.data.data(), &frags);
+      else stem_pack_weights(w1.data.data(), cfg.dtype, &frags);
+      if ((rc = upload_u16(&W.stem_w, frags)) || (rc = upload_bias64(&W.stem_b, c->var(bc.scope + "/biases")))) return rc;
+      Op o; o.kind = OP_STEM; o.name = bc.name; o.out = c->T(bc.name);
+      o.flops = conv_flops(w1.numel(), h * w);
+      c->ops.push_back(o);
+    } else if (first) {
+      if ((rc = add_conv(c, conv_op(bc.name, prev, c->T(bc.name), 1, 0, 1, h, w), pack_stem(c, bc.scope)))) return rc;
+    } else {
+      if ((rc = add_conv(c, conv_op(bc.name, prev, c->T(bc.name), 3, 1, 1, h, w), pack_plain(c, bc.scope, false)))) return rc;
+    }
+    prev = c->T(bc.name);
+    if (!bc.last) continue;
+    const std::string pname = "pool" + std::to_string(bc.block + 1);
+    const int pooled = c->T(pname);
+    if (bc.block == 4 && body.pool5 == OP_POOL3) {
+      Op p; p.kind = OP_POOL3; p.name = pname; p.in = prev; p.out = pooled;
+      c->ops.push_back(p);
+      continue;
+    }
+    if (bc.block < 3 && pool_fused(cfg, h, w)) {
+      Op& conv = c->ops.back();
+      conv.pool = 1;
+      conv.out = pooled;
+      conv.name += "+" + pname;
+      if (bc.block == 0 && stem2_fused(cfg)) {
+        // (the stand-alone stem kernel keeps its 32x32 fragments in stem_w; the fused kernel reads conv1_1 as 16x16x32 fragments)
+        std::vector<uint16_t> img, w1;
+        stem2_pack_weights(c->var("conv1/conv1_2/weights").data.data(), cfg.dtype, &img);
+        stem2_pack_w1(c->var("conv1/conv1_1/weights").data.data(), cfg.dtype, &w1);
+        if ((rc = upload_u16(&W.stem2_w, img)) || (rc = upload_bias64(&W.stem2_b, c->var("conv1/conv1_2/biases"))) ||
+            (rc = upload_u16(&W.stem2_w1, w1))) return rc;
+        Op f; f.kind = OP_STEM2; f.name = "conv1_1+conv1_2+pool1"; f.out = pooled;
+        const size_t n_ops = c->ops.size();
+        f.flops = c->ops[n_ops - 2].flops + c->ops[n_ops - 1].flops;
+        c->ops.erase(c->ops.end() - 2, c->ops.end());
+        c->ops.push_back(f);
+      }
+    } else {
+      if ((cfg.flags & RON_CFG_FUSE_POOLS) && bc.block >= 3) c->ops.back().fuse_next_pool = 1;
+      Op p; p.kind = OP_POOL; p.name = pname; p.in = prev; p.out = pooled;
+      c->ops.push_back(p);
+    }
+    prev = pooled;
+    h = pool2_out(h); w = pool2_out(w);
+  }
+  return RON_OK;
+}
+
+// fc6 / fc7, then the reverse connections + heads, coarse -> fine
+int build_ron_tail(ron_ctx* c) {
+  auto T = [&](const std::string& n) { return c->T(n); };
+  const bool full = c->cfg.variant == RON_VARIANT_FULL;
+  const int h = c->tensors[T("pool5")].H, w = c->tensors[T("pool5")].W;
+  int rc;
+  Op fc6 = conv_op("fc6", T("pool5"), T("fc6"), full ? 7 : 3, 3, 1, h, w);
+  if (!full) fc6.dil = 3;
+  if ((rc = add_conv(c, fc6, pack_plain(c, "fc6", false)))) return rc;
+  if ((rc = add_conv(c, conv_op("fc7", T("fc6"), T("fc7"), 1, 0, 1, h, w), pack_plain(c, "fc7", false)))) return rc;
+  const char* left_src[4] = {"fc7", "fc6", "conv5_3", "conv4_3"};
+  for (int i = 0; i < 4; ++i) {
+    const std::string Ln = kFeatLayers[i];
+    const std::string L = "reverse_module/" + Ln + "_reverse";
+    const int sh = c->feat_h[i], sw = c->feat_w[i], ref = T(Ln + "_ref"), hcat = T(Ln + "_hcat");
+    // relu(relu(BN(conv_left(backbone map))) + relu(deconv_right(coarser reference map) + b))  (nets/ron_vgg_320.py:420-425).
+    // The LEFT conv writes its half into the reference map's tensor first - it reads a backbone map only, so it is OFF the
+    // coarse -> fine chain and free to be launched early / beside anything - and the transposed conv, the cheap one that IS on the
+    // chain, adds its half in place (pixel-shuffle epilogue with the residual at the same address).  block7 has a left conv only
+    // (2x2 stride 2 over fc7).
+    Op left = conv_op(Ln + "_conv_left", T(left_src[i]), ref, i == 0 ? 2 : 3, i == 0 ? 0 : 1, 1, sh, sw);
+    if (i == 0) left.stride = 2;
+    if ((rc = add_conv(c, left, pack_plain(c, L + "_conv_left", true)))) return rc;
+    if (i > 0) {
+      Op d = conv_op(Ln + "_deconv_right", T(std::string(kFeatLayers[i - 1]) + "_ref"), ref, 1, 0, 1, sh / 2, sw / 2);
+      d.up = 2; d.up_cout = 512;
+      d.res = ref;                            // in place: ref = relu(left + up)
+      if ((rc = add_conv(c, d, pack_deconv(c, L + "_deconv_right")))) return rc;
+    }
+    // hcat channels: [0,512) objectness hidden | [512,1024) box hidden | [1024,1536) inception-1 3x3 | [1536,2048) inception-1 1x1
+    Op trio = conv_op(Ln + "_trio3", ref, hcat, 3, 1, 1, sh, sw);
+    trio.center_from = 1536;
+    if ((rc = add_conv(c, trio, pack_trio3(c, L)))) return rc;
+    Op obj = head_op(Ln + "_objectness_score", hcat, i, 1, c);
+    obj.in_coff = 0; obj.in_C = 512;
+    if ((rc = add_conv(c, obj, pack_plain(c, L + "_objectness_score", false)))) return rc;
+    Op inc2 = conv_op(Ln + "_inception2", hcat, T(Ln + "_inc2"), 3, 1, 1, sh, sw);
+    inc2.in_coff = 1024; inc2.in_C = 1024; inc2.center_from = 512;
+    if ((rc = add_conv(c, inc2, pack_inception(c, L + "_inception2")))) return rc;
+    if ((rc = add_conv(c, head_op(Ln + "_cls_pred", T(Ln + "_inc2"), i, 0, c), pack_plain(c, L + "_inception2/Conv2d_pred_3x3", false)))) return rc;
+    Op loc = head_op(Ln + "_loc_pred", hcat, i, 2, c);
+    loc.in_coff = 512; loc.in_C = 512;
+    if ((rc = add_conv(c, loc, pack_plain(c, L + "/Conv2d_1_3x3", false)))) return rc;
+  }
+  return RON_OK;
+}
+
+// conv6 (3x3 rate 6), conv7 (1x1), the extra blocks (1x1, then SsdExtra: pad 1 + 3x3 stride 2 / pad 1 + 4x4 / 3x3 VALID), then the
+// multibox heads (nets/ssd_vgg_300.py:403-431)
+int build_ssd_tail(ron_ctx* c, const SsdSpec& S) {
+  auto T = [&](const std::string& n) { return c->T(n); };
+  int h = c->tensors[T("pool5")].H, w = c->tensors[T("pool5")].W, rc;
+  Op conv6 = conv_op("conv6", T("pool5"), T("conv6"), 3, 6, 1, h, w);
+  conv6.dil = 6;
+  if ((rc = add_conv(c, conv6, pack_plain(c, "conv6", false)))) return rc;
+  if ((rc = add_conv(c, conv_op("conv7", T("conv6"), T("conv7"), 1, 0, 1, h, w), pack_plain(c, "conv7", false)))) return rc;
+  int src = T("conv7");
+  for (int b = 0; b < S.n_extra; ++b) {
+    const SsdExtra& e = S.extra[b];
+    const std::string B = ssd_block(b), kxk = ssd_extra_conv(e);
+    if ((rc = add_conv(c, conv_op(B + "_conv1x1", src, T(B + "_mid"), 1, 0, 1, h, w), pack_plain(c, B + "/conv1x1", false)))) return rc;
+    h = conv_out(h, e.k, e.stride, e.cpad); w = conv_out(w, e.k, e.stride, e.cpad);
+    Op o = conv_op(B + "_" + kxk, T(B + "_mid"), T(B), e.k, e.cpad, 1, h, w);
+    o.stride = e.stride;
+    if ((rc = add_conv(c, o, pack_plain(c, B + "/" + kxk, false)))) return rc;
+    src = T(B);
+  }
+  const Var& g = c->var("block4_box/L2Normalization/gamma");
+  RON_HIP_CHECK(ron::dev_upload(&c->own.l2_gamma, g.data.data(), g.data.size() * sizeof(float)));
+  Op norm; norm.kind = OP_L2NORM; norm.name = "block4_l2norm"; norm.in = T("conv4_3"); norm.out = T("block4_norm");
+  c->ops.push_back(norm);
+  for (int i = 0; i < S.n_feat; ++i) {
+    const std::string L = std::string(S.feat[i]) + "_box";
+    const int feat = T(i == 0 ? "block4_norm" : (i == 1 ? "conv7" : S.feat[i]));
+    if (i < kSsdPairedHeads) {
+      // the two large maps: loc and cls as one launch with two outputs (pack_box_pair)
+      Op o = head_op(L + "_conv_cls_loc", feat, i, 0, c);
+      o.head_kind2 = 2;
+      if ((rc = add_conv(c, o, pack_box_pair(c, L)))) return rc;
+      continue;
+    }
+    if ((rc = add_conv(c, head_op(L + "_conv_loc", feat, i, 2, c), pack_plain(c, L + "/conv_loc", false)))) return rc;
+    if ((rc = add_conv(c, head_op(L + "_conv_cls", feat, i, 0, c), pack_plain(c, L + "/conv_cls", false)))) return rc;
   }
   return RON_OK;
 }
@@ -515,9 +751,10 @@ int make_anchors_ssd(ron_ctx* c) {
 // other (nets/ron_vgg_320.py:495-506); the true dependencies are listed at the RON tables below.  Every braced set only reads what
 // earlier entries wrote, and its members write disjoint tensors / channel slices.  History of the measurements behind the plans:
 // HISTORY.md (rounds 2-3: T64 / T128 groups by dependency level) and DESIGN.md 3.2 (round 4: mixed-width groups with carriers).
-void plan_groups(ron_ctx* c) {
-  if (c->cfg.flags & (RON_CFG_MULTI_STREAM | RON_CFG_NO_GROUPS)) return;
-  struct Slot { int cfg; std::vector<std::string> names; };     // cfg < 0: launches of their own
+struct Slot { int cfg; std::vector<std::string> names; };     // cfg < 0: launches of their own
+
+// The plan of this context: the SSD table built from the variant's description, or one of the three RON tables.
+std::vector<Slot> head_plan(const ron_ctx* c) {
   const int T64 = kCfgIgemm128x64;     // tiny convolutions (Npad = 64)
   // SSD-512 (nets/ssd_vgg_512.py:395-458): blocks 8-12 are a chain of 1x1 -> 3x3 stride-2 convolutions on 16x16 ... 1x1 maps,
   // each a 13-20 us launch at batch 16; the two box convolutions of a block only need that block's output, so they share a
@@ -525,21 +762,21 @@ void plan_groups(ron_ctx* c) {
   // as carriers of the chain's small launches in mixed-width groups they measured -0.8 % images/s - block4_box_conv_loc then leaves
   // the halo-patch kernel: 114 us for {block8_conv1x1, block4_box_conv_loc} where the two take 40 + 45 us on their own).
   // SSD-300 has the same chain on 19x19 ... 1x1 maps, one block shorter (16 small launches -> 9).
-  std::vector<Slot> ssd_order;
   if (const SsdSpec* S = ssd_spec(c->cfg.variant)) {
-    ssd_order = {{-1, {"conv6"}}, {-1, {"conv7"}}, {-1, {"block8_conv1x1"}}};
+    std::vector<Slot> ssd_order = {{-1, {"conv6"}}, {-1, {"conv7"}}, {-1, {"block8_conv1x1"}}};
     for (int b = 0; b < S->n_extra; ++b) {
-      const std::string B = "block" + std::to_string(8 + b);
+      const std::string B = ssd_block(b);
       ssd_order.push_back({-1, {B + "_" + ssd_extra_conv(S->extra[b])}});
       Slot g{T64, {B + "_box_conv_loc", B + "_box_conv_cls"}};
-      if (b + 1 < S->n_extra) g.names.push_back("block" + std::to_string(9 + b) + "_conv1x1");
+      if (b + 1 < S->n_extra) g.names.push_back(ssd_block(b + 1) + "_conv1x1");
       ssd_order.push_back(g);
     }
     ssd_order.push_back({-1, {"block4_l2norm"}});
     for (int i = 0; i < kSsdPairedHeads; ++i) ssd_order.push_back({-1, {std::string(S->feat[i]) + "_box_conv_cls_loc"}});
+    return ssd_order;
   }
   // RON heads.  Dependencies after the round-4 re-formulation of the reverse connection (the LEFT conv of a scale reads a backbone
-  // map only; the transposed conv adds its half in place, ron_finalize_weights):
+  // map only; the transposed conv adds its half in place, build_ron_tail):
   //   conv_left(i)                       <- backbone (fc7 / fc6 / conv5_3 / conv4_3)        i = block7, 6, 5, 4
   //   deconv_right(i) -> ref(i)          <- ref(i-1), conv_left(i)
   //   trio3(i) -> hcat(i)                <- ref(i)
@@ -608,7 +845,11 @@ void plan_groups(ron_ctx* c) {
   };
   const bool levels = !(c->cfg.flags & RON_CFG_BATCH_GROUPS) &&
                       ((c->cfg.flags & RON_CFG_LEVEL_GROUPS) || c->cfg.max_batch <= kLevelPlanMaxBatch);
-  const std::vector<Slot>& order = c->is_ssd() ? ssd_order : (levels ? ron_levels : (c->cfg.max_batch >= kCarrierPlanMinBatch ? ron_order : ron_mid));
+  return levels ? ron_levels : (c->cfg.max_batch >= kCarrierPlanMinBatch ? ron_order : ron_mid);
+}
+
+// Reorders the tail of the op list as `order` says and marks the grouped launches.
+void plan_groups(ron_ctx* c, const std::vector<Slot>& order) {
   std::map<std::string, int> at;
   for (size_t i = 0; i < c->ops.size(); ++i) at[c->ops[i].name] = (int)i;
   size_t first_head = c->ops.size(), n_named = 0;
@@ -641,15 +882,6 @@ void plan_groups(ron_ctx* c) {
   c->ops.swap(planned);
 }
 
-Op conv_op(const std::string& name, int in, int out, int packed, int k, int cpad, int relu, int Ho, int Wo) {
-  Op o;
-  o.kind = OP_CONV; o.name = name; o.in = in; o.out = out; o.packed = packed;
-  o.kh = o.kw = k; o.cpad = cpad; o.relu = relu; o.Ho = Ho; o.Wo = Wo;
-  return o;
-}
-
-double conv_flops(const Var& w, int out_pixels) { return 2.0 * (double)w.numel() * out_pixels; }
-
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -664,113 +896,21 @@ extern "C" int ron_create(ron_ctx** out, const ron_config* cfg) {
   RON_REQUIRE(cfg->num_classes >= 2 && cfg->num_classes <= RON_MAX_CLASSES, "num_classes %d out of range [2, %d]", cfg->num_classes, RON_MAX_CLASSES);
   RON_REQUIRE(cfg->max_batch >= 1, "max_batch must be >= 1");
   RON_HIP_CHECK(ron::dev_set_device(cfg->device));
-  std::unique_ptr<ron_ctx> c(new ron_ctx());
+  std::unique_ptr<ron_ctx> c(new ron_ctx());     // (a failure below frees what was allocated so far: every buffer has an owner)
   c->cfg = *cfg;
   c->c6 = cfg->variant == RON_VARIANT_FULL ? 4096 : 1024;
-  const int H = cfg->img_h, W = cfg->img_w;
-  if (c->is_ssd()) {
-    declare_variables_ssd(c.get());
-    declare_tensors_ssd(c.get());
-  } else {
   declare_variables(c.get());
-
-  // ---- tensors ----
-  const int chunk = conv_k_chunk(cfg->dtype);
-  c->add_tensor("im2col", H, W, chunk, 0);
-  const int widths[5] = {64, 128, 256, 512, 512};
-  const int reps[5] = {2, 2, 3, 3, 3};
-  int h = H, w = W;
-  for (int b = 0; b < 5; ++b) {
-    for (int r = 0; r < reps[b]; ++r) {
-      const bool last = r == reps[b] - 1;
-      // the block output feeds the pool (no halo needed); block4/block5 also feed a 3x3 left conv
-      const int pad = (!last || b >= 3) ? 1 : 0;
-      c->add_tensor("conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1), h, w, widths[b], pad);
-    }
-    h /= 2; w /= 2;
-    c->add_tensor("pool" + std::to_string(b + 1), h, w, widths[b], b == 4 ? 3 : 1);
-  }
-  c->add_tensor("fc6", h, w, c->c6, 1);
-  c->add_tensor("fc7", h, w, c->c6, 0);
-  for (int i = 0; i < 4; ++i) {
-    const int s_h = (H / 64) << i, s_w = (W / 64) << i;
-    c->feat[i] = s_h;
-    c->feat_h[i] = s_h; c->feat_w[i] = s_w; c->feat_A[i] = c->num_anchors;
-    const std::string L = kFeatLayers[i];
-    c->add_tensor(L + "_ref", s_h, s_w, 512, 1);
-    c->add_tensor(L + "_hcat", s_h, s_w, 2048, 1);
-    c->add_tensor(L + "_inc2", s_h, s_w, 1024, 1);
-  }
-  }
-  for (auto& t : c->tensors) {
-    if (t.name == "im2col" && cfg->dtype != RON_DTYPE_F32) continue;      // bf16 / f16 / f16x3 use the stem kernel
-    if ((cfg->flags & RON_CFG_FUSE_POOLS) && (t.name == "conv1_2" || t.name == "conv2_2" || t.name == "conv3_3") &&
-        !((cfg->flags & RON_CFG_NO_ODD_POOL_FUSE) && ((t.H | t.W) & 1))) continue;
-    if ((cfg->flags & RON_CFG_FUSE_POOLS) && !(cfg->flags & RON_CFG_NO_STEM2) && dtype_is_half(cfg->dtype) && H % 8 == 0 &&
-        W % 32 == 0 && t.name == "conv1_1") continue;         // conv1_1 + conv1_2 + pool1 run fused (stem2_kernel)
-    t.bytes = TensorView::halo_pixels(cfg->max_batch, t.H, t.W, t.pad) * t.cstride * c->esz();     // shared halos, conv_mfma.h
-    if (t.bytes >= ((int64_t)1 << 32)) {
-      ron::set_error("tensor %s needs %lld bytes for max_batch %d: above the 4 GiB buffer-addressing limit; lower max_batch",
-                     t.name.c_str(), (long long)t.bytes, cfg->max_batch);
-      for (auto& u : c->tensors) if (u.d) (void)ron::dev_free(u.d);
-      return RON_ERR_INVALID;
-    }
-    RON_HIP_CHECK(ron::dev_malloc(&t.d, (size_t)t.bytes));
-    RON_HIP_CHECK(ron::dev_memset(t.d, 0, (size_t)t.bytes));     // halos stay zero forever: kernels write interiors only
-  }
-  // ---- anchors (RONNet.default_params, nets/ron_vgg_320.py:97-124) ----
-  if (c->is_ssd()) {
-    int rc = make_anchors_ssd(c.get());
-    if (rc) return rc;
-    *out = c.release();
-    return RON_OK;
-  }
-  const double sizes[4][2] = {{224., 256.}, {160., 192.}, {96., 128.}, {32., 64.}};
-  const double ratios[5] = {1., 2., 3., 1. / 2, 1. / 3};
-  const double steps[4] = {64, 32, 16, 8};
-  for (int i = 0; i < 4; ++i) {
-    const int fh = (H / 64) << i, fw = (W / 64) << i;
-    std::vector<float> y(fh * fw), x(fh * fw), hh(10), ww(10);
-    int rc = ron_anchor_one_layer(H, W, fh, fw, sizes[i], 2, ratios, 5, steps[i], 0.5, y.data(), x.data(), hh.data(), ww.data());
-    if (rc) return rc;
-    const std::vector<float>* src[4] = {&y, &x, &hh, &ww};
-    for (int k = 0; k < 4; ++k) {
-      RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_anchor[i][k], src[k]->size() * sizeof(float)));
-      RON_HIP_CHECK(ron::dev_memcpy(c->d_anchor[i][k], src[k]->data(), src[k]->size() * sizeof(float), hipMemcpyHostToDevice));
-    }
-  }
-  *out = c.release();
-  return RON_OK;
+  declare_tensors(c.get());
+  int rc = allocate_tensors(c.get());
+  if (rc == RON_OK) rc = make_anchors(c.get());
+  if (rc == RON_OK) *out = c.release();
+  return rc;
 }
 
 extern "C" int ron_destroy(ron_ctx* c) {
   if (!c) return RON_OK;
   if (c->clones > 0) { ron::set_error("ron_destroy: %d execution slot(s) still borrow this context's weights", c->clones); return RON_ERR_STATE; }
-  const bool borrowed = c->weights_owner != nullptr;
-  if (borrowed) {                        // the weights belong to the owner
-    --c->weights_owner->clones;
-    c->packed.clear();
-    c->d_l2_gamma = nullptr; c->d_stem_w = nullptr; c->d_stem_b = nullptr; c->d_stem2_w = nullptr; c->d_stem2_b = nullptr; c->d_stem2_w1 = nullptr;
-  }
-  for (auto& t : c->tensors) if (t.d) (void)ron::dev_free(t.d);
-  for (auto& p : c->packed) { if (p.d_w) (void)ron::dev_free(p.d_w); if (p.d_w_c64) (void)ron::dev_free(p.d_w_c64); if (p.d_bias) (void)ron::dev_free(p.d_bias); }
-  for (int i = 0; i < RON_MAX_LAYERS; ++i) for (int k = 0; k < 4; ++k) if (c->d_anchor[i][k]) (void)ron::dev_free(c->d_anchor[i][k]);
-  for (int k = 0; k < 3; ++k) for (int i = 0; i < RON_MAX_LAYERS; ++i) if (c->d_head[k][i]) (void)ron::dev_free(c->d_head[k][i]);
-  if (c->d_l2_gamma) (void)ron::dev_free(c->d_l2_gamma);
-  for (auto& call : c->pending) for (hipEvent_t e : call) (void)hipEventDestroy(e);
-  for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-  if (c->d_post_ws) (void)ron::dev_free(c->d_post_ws);
-  for (int l = 0; l < 4; ++l) {
-    if (c->d_splitk[l]) (void)ron::dev_free(c->d_splitk[l]);
-    if (c->side[l]) (void)hipStreamDestroy(c->side[l]);
-    if (c->lane_ready[l]) (void)hipEventDestroy(c->lane_ready[l]);
-    if (c->lane_done[l]) (void)hipEventDestroy(c->lane_done[l]);
-  }
-  if (c->d_stem_w) (void)ron::dev_free(c->d_stem_w);
-  if (c->d_stem_b) (void)ron::dev_free(c->d_stem_b);
-  if (c->d_stem2_w) (void)ron::dev_free(c->d_stem2_w);
-  if (c->d_stem2_b) (void)ron::dev_free(c->d_stem2_b);
-  if (c->d_stem2_w1) (void)ron::dev_free(c->d_stem2_w1);
+  if (c->weights_owner != nullptr) --c->weights_owner->clones;
   delete c;
   return RON_OK;
 }
@@ -807,221 +947,14 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
   for (auto& v : c->vars)
     if (!v.loaded) { ron::set_error("variable '%s' was not loaded", v.name.c_str()); return RON_ERR_STATE; }
   RON_HIP_CHECK(ron::dev_set_device(c->cfg.device));
-  const int H = c->cfg.img_h, W = c->cfg.img_w;
-  auto T = [&](const std::string& n) { return c->tensor_index.at(n); };
-  double flops = 0, mark = 0;
-  int rc;
-#define ATTR() do { c->ops.back().flops += flops - mark; mark = flops; } while (0)
-#define PACK(expr) do { rc = (expr); if (rc < 0) return rc; } while (0)
-  // ---- VGG-16 body ----
-  const bool use_stem = dtype_is_half(c->cfg.dtype) || c->cfg.dtype == RON_DTYPE_F16X3;      // fp32: conv1_1 as im2col + GEMM
-  if (!use_stem) {
-    Op o; o.kind = OP_IM2COL; o.name = "im2col"; o.out = T("im2col");
-    c->ops.push_back(o);
-  }
-  const int reps[5] = {2, 2, 3, 3, 3};
-  int h = H, w = W, prev = T("im2col");
-  for (int b = 0; b < 5; ++b) {
-    for (int r = 0; r < reps[b]; ++r) {
-      const std::string nm = "conv" + std::to_string(b + 1) + "_" + std::to_string(r + 1);
-      const std::string scope = "conv" + std::to_string(b + 1) + "/" + nm;
-      const bool stem = b == 0 && r == 0;
-      if (stem && use_stem) {
-        std::vector<uint16_t> frags;
-        if (c->cfg.dtype == RON_DTYPE_F16X3) c->stem_oscale = stem_pack_weights_split(c->var(scope + "/weights").data.data(), &frags);
-        else stem_pack_weights(c->var(scope + "/weights").data.data(), c->cfg.dtype, &frags);
-        RON_HIP_CHECK(ron::dev_malloc(&c->d_stem_w, frags.size() * 2));
-        RON_HIP_CHECK(ron::dev_memcpy(c->d_stem_w, frags.data(), frags.size() * 2, hipMemcpyHostToDevice));
-        RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_stem_b, 64 * sizeof(float)));
-        RON_HIP_CHECK(ron::dev_memcpy(c->d_stem_b, c->var(scope + "/biases").data.data(), 64 * sizeof(float), hipMemcpyHostToDevice));
-        Op o; o.kind = OP_STEM; o.name = nm; o.out = T(nm);
-        c->ops.push_back(o);
-      } else {
-        PACK(stem ? pack_stem(c, scope) : pack_plain(c, scope, false));
-        c->ops.push_back(conv_op(nm, prev, T(nm), rc, stem ? 1 : 3, stem ? 0 : 1, 1, h, w));
-      }
-      flops += conv_flops(c->var(scope + "/weights"), h * w); ATTR();
-      prev = T(nm);
-    }
-    const std::string pname = "pool" + std::to_string(b + 1);
-    if (c->is_ssd() && b == 4) {              // SSD: pool5 is 3x3 stride 1 (nets/ssd_vgg_512.py:391)
-      Op p; p.kind = OP_POOL3; p.name = pname; p.in = prev; p.out = T(p.name);
-      c->ops.push_back(p);
-      prev = T(pname);
-      continue;
-    }
-    if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && b < 3 && c->ops.back().kind == OP_CONV &&
-        !((c->cfg.flags & RON_CFG_NO_ODD_POOL_FUSE) && ((h | w) & 1))) {
-      c->ops.back().pool = 1;                 // block1..3 feed nothing but their pool: never written at full size
-      c->ops.back().out = T(pname);
-      c->ops.back().name += "+" + pname;
-      const size_t n_ops = c->ops.size();
-      if (b == 0 && dtype_is_half(c->cfg.dtype) && n_ops >= 2 && c->ops[n_ops - 2].kind == OP_STEM && H % 8 == 0 && W % 32 == 0 &&
-          !(c->cfg.flags & RON_CFG_NO_STEM2)) {
-        // conv1_1 + conv1_2 + pool1 as one kernel (stem.hip): neither full-resolution 64-channel map touches HBM
-        std::vector<uint16_t> img;
-        stem2_pack_weights(c->var("conv1/conv1_2/weights").data.data(), c->cfg.dtype, &img);
-        RON_HIP_CHECK(ron::dev_malloc(&c->d_stem2_w, img.size() * 2));
-        RON_HIP_CHECK(ron::dev_memcpy(c->d_stem2_w, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-        RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_stem2_b, 64 * sizeof(float)));
-        RON_HIP_CHECK(ron::dev_memcpy(c->d_stem2_b, c->var("conv1/conv1_2/biases").data.data(), 64 * sizeof(float), hipMemcpyHostToDevice));
-        // conv1_1 as 16x16x32 fragments for the fused kernel (the stand-alone stem kernel keeps its 32x32 fragments in d_stem_w)
-        stem2_pack_w1(c->var("conv1/conv1_1/weights").data.data(), c->cfg.dtype, &img);
-        RON_HIP_CHECK(ron::dev_malloc(&c->d_stem2_w1, img.size() * 2));
-        RON_HIP_CHECK(ron::dev_memcpy(c->d_stem2_w1, img.data(), img.size() * 2, hipMemcpyHostToDevice));
-        Op f; f.kind = OP_STEM2; f.name = "conv1_1+conv1_2+pool1"; f.out = T(pname);
-        f.flops = c->ops[n_ops - 2].flops + c->ops[n_ops - 1].flops;
-        c->ops.pop_back(); c->ops.pop_back();
-        c->ops.push_back(f);
-      }
-    } else {
-      if ((c->cfg.flags & RON_CFG_FUSE_POOLS) && b >= 3 && c->ops.back().kind == OP_CONV) c->ops.back().fuse_next_pool = 1;
-      Op p; p.kind = OP_POOL; p.name = pname; p.in = prev; p.out = T(p.name);
-      c->ops.push_back(p);
-    }
-    prev = T(pname);
-    h = pool2_out(h); w = pool2_out(w);
-  }
-  if (c->is_ssd()) {
-    const SsdSpec& S = *ssd_spec(c->cfg.variant);
-    // ---- conv6 (3x3 rate 6), conv7 (1x1), extra blocks (1x1, then SsdExtra: pad 1 + 3x3 stride 2 / pad 1 + 4x4 / 3x3 VALID) ----
-    PACK(pack_plain(c, "conv6", false));
-    { Op o = conv_op("conv6", prev, T("conv6"), rc, 3, 6, 1, h, w); o.dil = 6; c->ops.push_back(o); }
-    flops += conv_flops(c->var("conv6/weights"), h * w); ATTR();
-    PACK(pack_plain(c, "conv7", false));
-    c->ops.push_back(conv_op("conv7", T("conv6"), T("conv7"), rc, 1, 0, 1, h, w));
-    flops += conv_flops(c->var("conv7/weights"), h * w); ATTR();
-    int src = T("conv7");
-    for (int b = 0; b < S.n_extra; ++b) {
-      const SsdExtra& e = S.extra[b];
-      const std::string B = "block" + std::to_string(8 + b);
-      PACK(pack_plain(c, B + "/conv1x1", false));
-      c->ops.push_back(conv_op(B + "_conv1x1", src, T(B + "_mid"), rc, 1, 0, 1, h, w));
-      flops += conv_flops(c->var(B + "/conv1x1/weights"), h * w); ATTR();
-      const std::string cs = B + "/" + ssd_extra_conv(e);
-      PACK(pack_plain(c, cs, false));
-      const int ho = conv_out(h, e.k, e.stride, e.cpad), wo = conv_out(w, e.k, e.stride, e.cpad);
-      Op o = conv_op(B + "_" + ssd_extra_conv(e), T(B + "_mid"), T(B), rc, e.k, e.cpad, 1, ho, wo);
-      o.stride = e.stride;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(cs + "/weights"), ho * wo); ATTR();
-      src = T(B); h = ho; w = wo;
-    }
-    // ---- multibox heads (nets/ssd_vgg_300.py:403-431) ----
-    {
-      const Var& g = c->var("block4_box/L2Normalization/gamma");
-      RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_l2_gamma, g.data.size() * sizeof(float)));
-      RON_HIP_CHECK(ron::dev_memcpy(c->d_l2_gamma, g.data.data(), g.data.size() * sizeof(float), hipMemcpyHostToDevice));
-      Op o; o.kind = OP_L2NORM; o.name = "block4_l2norm"; o.in = T("conv4_3"); o.out = T("block4_norm");
-      c->ops.push_back(o);
-    }
-    for (int i = 0; i < S.n_feat; ++i) {
-      const std::string L = std::string(S.feat[i]) + "_box";
-      const std::string feat_src = i == 0 ? "block4_norm" : (i == 1 ? "conv7" : S.feat[i]);
-      const int fh = c->feat_h[i], fw = c->feat_w[i];
-      if (i < kSsdPairedHeads) {
-        // the two large maps: loc and cls as one launch with two outputs (pack_box_pair)
-        PACK(pack_box_pair(c, L));
-        Op o = conv_op(L + "_conv_cls_loc", T(feat_src), -2, rc, 3, 1, 0, fh, fw);
-        o.head_kind = 0; o.head_kind2 = 2; o.head_layer = i;
-        c->ops.push_back(o);
-        flops += conv_flops(c->var(L + "/conv_loc/weights"), fh * fw) + conv_flops(c->var(L + "/conv_cls/weights"), fh * fw); ATTR();
-        continue;
-      }
-      PACK(pack_plain(c, L + "/conv_loc", false));
-      { Op o = conv_op(L + "_conv_loc", T(feat_src), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 2; o.head_layer = i; c->ops.push_back(o); }
-      flops += conv_flops(c->var(L + "/conv_loc/weights"), fh * fw); ATTR();
-      PACK(pack_plain(c, L + "/conv_cls", false));
-      { Op o = conv_op(L + "_conv_cls", T(feat_src), -2, rc, 3, 1, 0, fh, fw); o.head_kind = 0; o.head_layer = i; c->ops.push_back(o); }
-      flops += conv_flops(c->var(L + "/conv_cls/weights"), fh * fw); ATTR();
-    }
-  } else {
-  // ---- fc6 / fc7 ----
-  PACK(pack_plain(c, "fc6", false));
-  {
-    Op o = c->cfg.variant == RON_VARIANT_FULL ? conv_op("fc6", prev, T("fc6"), rc, 7, 3, 1, h, w)
-                                               : conv_op("fc6", prev, T("fc6"), rc, 3, 3, 1, h, w);
-    if (c->cfg.variant != RON_VARIANT_FULL) o.dil = 3;
-    c->ops.push_back(o);
-    flops += conv_flops(c->var("fc6/weights"), h * w); ATTR();
-  }
-  PACK(pack_plain(c, "fc7", false));
-  c->ops.push_back(conv_op("fc7", T("fc6"), T("fc7"), rc, 1, 0, 1, h, w));
-  flops += conv_flops(c->var("fc7/weights"), h * w); ATTR();
-  // ---- reverse connections + heads, coarse -> fine ----
-  const char* left_src[4] = {"fc7", "fc6", "conv5_3", "conv4_3"};
-  for (int i = 0; i < 4; ++i) {
-    const std::string Ln = kFeatLayers[i];
-    const std::string L = "reverse_module/" + Ln + "_reverse";
-    const int sh = c->feat[i], sw = (W / 64) << i;
-    if (i == 0) {
-      PACK(pack_plain(c, L + "_conv_left", true));
-      Op o = conv_op(Ln + "_conv_left", T(left_src[i]), T(Ln + "_ref"), rc, 2, 0, 1, sh, sw);
-      o.stride = 2;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "_conv_left/weights"), sh * sw); ATTR();
-    } else {
-      // relu(relu(BN(conv_left(backbone map))) + relu(deconv_right(coarser reference map) + b))  (nets/ron_vgg_320.py:420-425).
-      // The LEFT conv writes its half into the reference map's tensor first - it reads a backbone map only, so it is OFF the
-      // coarse -> fine chain and free to be launched early / beside anything - and the transposed conv, the cheap one that IS on the
-      // chain, adds its half in place (pixel-shuffle epilogue with the residual at the same address).
-      PACK(pack_plain(c, L + "_conv_left", true));
-      c->ops.push_back(conv_op(Ln + "_conv_left", T(left_src[i]), T(Ln + "_ref"), rc, 3, 1, 1, sh, sw));
-      flops += conv_flops(c->var(L + "_conv_left/weights"), sh * sw); ATTR();
-      PACK(pack_deconv(c, L + "_deconv_right"));
-      Op d = conv_op(Ln + "_deconv_right", T(std::string(kFeatLayers[i - 1]) + "_ref"), T(Ln + "_ref"), rc, 1, 0, 1, sh / 2, sw / 2);
-      d.up = 2; d.up_cout = 512;
-      d.res = T(Ln + "_ref");                 // in place: ref = relu(left + up)
-      c->ops.push_back(d);
-      flops += conv_flops(c->var(L + "_deconv_right/weights"), (sh / 2) * (sw / 2)); ATTR();
-    }
-    // hcat channels: [0,512) objectness hidden | [512,1024) box hidden | [1024,1536) inception-1 3x3 | [1536,2048) inception-1 1x1
-    PACK(pack_trio3(c, L));
-    {
-      Op o = conv_op(Ln + "_trio3", T(Ln + "_ref"), T(Ln + "_hcat"), rc, 3, 1, 1, sh, sw);
-      o.center_from = 1536;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "_objectness/weights"), sh * sw) + conv_flops(c->var(L + "/Conv2d_0_3x3/weights"), sh * sw) +
-               conv_flops(c->var(L + "_inception1/Branch_0/Conv2d_3x3/weights"), sh * sw) +
-               conv_flops(c->var(L + "_inception1/Branch_1/Conv2d_1x1/weights"), sh * sw); ATTR();
-    }
-    PACK(pack_plain(c, L + "_objectness_score", false));
-    {
-      Op o = conv_op(Ln + "_objectness_score", T(Ln + "_hcat"), -2, rc, 3, 1, 0, sh, sw);
-      o.in_coff = 0; o.in_C = 512; o.head_kind = 1; o.head_layer = i;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "_objectness_score/weights"), sh * sw); ATTR();
-    }
-    PACK(pack_inception(c, L + "_inception2"));
-    {
-      Op o = conv_op(Ln + "_inception2", T(Ln + "_hcat"), T(Ln + "_inc2"), rc, 3, 1, 1, sh, sw);
-      o.in_coff = 1024; o.in_C = 1024; o.center_from = 512;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "_inception2/Branch_0/Conv2d_3x3/weights"), sh * sw) +
-               conv_flops(c->var(L + "_inception2/Branch_1/Conv2d_1x1/weights"), sh * sw); ATTR();
-    }
-    PACK(pack_plain(c, L + "_inception2/Conv2d_pred_3x3", false));
-    {
-      Op o = conv_op(Ln + "_cls_pred", T(Ln + "_inc2"), -2, rc, 3, 1, 0, sh, sw);
-      o.head_kind = 0; o.head_layer = i;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "_inception2/Conv2d_pred_3x3/weights"), sh * sw); ATTR();
-    }
-    PACK(pack_plain(c, L + "/Conv2d_1_3x3", false));
-    {
-      Op o = conv_op(Ln + "_loc_pred", T(Ln + "_hcat"), -2, rc, 3, 1, 0, sh, sw);
-      o.in_coff = 512; o.in_C = 512; o.head_kind = 2; o.head_layer = i;
-      c->ops.push_back(o);
-      flops += conv_flops(c->var(L + "/Conv2d_1_3x3/weights"), sh * sw); ATTR();
-    }
-  }
-  }   // RON tail
-#undef PACK
-#undef ATTR
-  c->flops_per_image = flops;
-  plan_groups(c);
+  const SsdSpec* ssd = ssd_spec(c->cfg.variant);
+  int rc = build_body(c, vgg_body(c));
+  if (rc == RON_OK) rc = ssd ? build_ssd_tail(c, *ssd) : build_ron_tail(c);
+  if (rc) return rc;
+  for (const Op& o : c->ops) c->flops_per_image += o.flops;
+  if (!(c->cfg.flags & (RON_CFG_MULTI_STREAM | RON_CFG_NO_GROUPS))) plan_groups(c, head_plan(c));
   // stream lanes: heads of block7 / block6 / block5 are independent of the main chain once their reference map exists
-  if ((c->cfg.flags & RON_CFG_MULTI_STREAM) && !c->is_ssd()) {
+  if ((c->cfg.flags & RON_CFG_MULTI_STREAM) && !ssd) {
     for (Op& o : c->ops)
       for (int i = 0; i < 3; ++i) {
         const std::string pre = std::string(kFeatLayers[i]) + "_";
@@ -1032,7 +965,7 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
   }
   for (Op& o : c->ops) {
     if (o.kind != OP_CONV) continue;
-    const PackedConv& pk = c->packed[o.packed];
+    const PackedConv& pk = c->own.packed[o.packed];
     const Tensor& ti = c->tensors[o.in];
     const int cin = o.in_C > 0 ? o.in_C : ti.C;
     const double out_esz = o.out == -2 ? 4.0 : (double)c->esz();
@@ -1048,64 +981,69 @@ extern "C" int ron_finalize_weights(ron_ctx* c) {
   return RON_OK;
 }
 
+// The dense fp32 tensor of one head output (kind 0 cls, 1 obj, 2 loc) of `o`'s layer in the caller's buffers (heads == nullptr:
+// geometry only, base null).
+static int head_view(const ron_ctx* c, const Op& o, int kind, int n, const ron_heads* heads, TensorView* out_v) {
+  float* dst = nullptr;
+  if (heads != nullptr) {
+    const float* const* arr = kind == 0 ? heads->cls : (kind == 1 ? heads->obj : heads->loc);
+    dst = const_cast<float*>(arr[o.head_layer]);
+    RON_REQUIRE(dst != nullptr, "ron_forward: head buffer (kind %d, layer %d) is NULL", kind, o.head_layer);
+  }
+  TensorView v;
+  const int A = c->feat_A[o.head_layer];
+  v.base = dst; v.N = n; v.H = o.Ho; v.W = o.Wo; v.pad = 0; v.coff = 0;
+  v.C = kind == 0 ? A * c->cfg.num_classes : (kind == 1 ? 2 * A : 4 * A);
+  v.cstride = v.C;
+  v.bytes = (int64_t)n * v.H * v.W * v.C * 4;
+  *out_v = v;
+  return RON_OK;
+}
+
 // The launch description of conv op `o` at batch n (heads == nullptr: geometry only, for sizing).
 static int describe_conv(const ron_ctx* c, const Op& o, int n, const ron_heads* heads, ConvLaunch* out_l) {
-  const PackedConv& p = c->packed[o.packed];
+  const PackedConv& p = c->wts->packed[o.packed];
   ConvLaunch L;
+  int rc;
   L.dtype = c->cfg.dtype;
   L.in = c->view(o.in, n, o.in_coff, o.in_C > 0 ? o.in_C : -1);
   if (o.out == -2) {
-    float* dst = nullptr;
-    if (heads != nullptr) {
-      const float* const* arr = o.head_kind == 0 ? heads->cls : (o.head_kind == 1 ? heads->obj : heads->loc);
-      dst = const_cast<float*>(arr[o.head_layer]);
-      RON_REQUIRE(dst != nullptr, "ron_forward: head buffer (kind %d, layer %d) is NULL", o.head_kind, o.head_layer);
-    }
-    TensorView v;
-    const int A = c->feat_A[o.head_layer];
-    v.base = dst; v.N = n; v.H = o.Ho; v.W = o.Wo; v.pad = 0; v.coff = 0;
-    v.C = o.head_kind == 0 ? A * c->cfg.num_classes : (o.head_kind == 1 ? 2 * A : 4 * A);
-    v.cstride = v.C;
-    v.bytes = (int64_t)n * v.H * v.W * v.C * 4;
-    L.out = v;
+    if ((rc = head_view(c, o, o.head_kind, n, heads, &L.out))) return rc;
     L.out_f32 = 1;
     if (o.head_kind2 >= 0) {
       // second head output of the launch (pack_box_pair): dense like the first
-      float* dst2 = nullptr;
-      if (heads != nullptr) {
-        const float* const* arr2 = o.head_kind2 == 0 ? heads->cls : (o.head_kind2 == 1 ? heads->obj : heads->loc);
-        dst2 = const_cast<float*>(arr2[o.head_layer]);
-        RON_REQUIRE(dst2 != nullptr, "ron_forward: head buffer (kind %d, layer %d) is NULL", o.head_kind2, o.head_layer);
-      }
-      TensorView v2 = v;
-      v2.base = dst2 != nullptr ? dst2 : reinterpret_cast<float*>(16);        // (geometry only: any non-null address)
-      v2.C = o.head_kind2 == 0 ? A * c->cfg.num_classes : (o.head_kind2 == 1 ? 2 * A : 4 * A);
-      v2.cstride = v2.C;
-      v2.bytes = (int64_t)n * v2.H * v2.W * v2.C * 4;
-      L.out2 = v2;
+      if ((rc = head_view(c, o, o.head_kind2, n, heads, &L.out2))) return rc;
+      if (L.out2.base == nullptr) L.out2.base = reinterpret_cast<float*>(16);        // (geometry only: any non-null address)
       L.split_n = p.split_n; L.split_first = p.split_first;
     }
   } else {
-    L.out = c->view(o.out, n, o.out_coff, o.out_C > 0 ? o.out_C : -1);
+    L.out = c->view(o.out, n);
   }
-  L.res = o.res >= 0 ? c->tensors[o.res].d : nullptr;
-  L.wgt = p.d_w; L.wgt_bytes = p.w_bytes; L.wgt_c64 = p.d_w_c64; L.bias = p.d_bias; L.oscale = p.oscale; L.Cout = p.Cout; L.Npad = p.Npad;
+  L.res = o.res >= 0 ? c->tensors[o.res].d.p : nullptr;
+  L.wgt = p.w; L.wgt_bytes = p.w_bytes; L.wgt_c64 = p.w_c64; L.bias = p.bias.as<float>(); L.oscale = p.oscale; L.Cout = p.Cout; L.Npad = p.Npad;
   L.kh = o.kh; L.kw = o.kw; L.stride = o.stride; L.dil = o.dil; L.cpad = o.cpad; L.relu = o.relu;
   L.up = o.up; L.up_cout = o.up_cout; L.Ho = o.Ho; L.Wo = o.Wo; L.pool = o.pool;
   L.center_from = o.center_from;
-  L.scratch = c->d_splitk[o.lane]; L.scratch_bytes = c->splitk_bytes[o.lane];
+  L.scratch = c->splitk[o.lane]; L.scratch_bytes = c->splitk_bytes[o.lane];
   L.halo_skip = (c->cfg.flags & RON_CFG_NO_HALO_SKIP) ? 0 : 1;
   *out_l = L;
   return RON_OK;
 }
 
-// Streams, events, split-K scratch and timing slots of one execution slot (after c->ops / c->packed are in place).
+// the context's own head buffers, as ron_detect hands them to the forward pass and the post-processing
+static void own_heads(const ron_ctx* c, ron_heads* hd) {
+  for (int i = 0; i < c->n_feat; ++i) {
+    hd->cls[i] = c->head[0][i].as<float>(); hd->obj[i] = c->head[1][i].as<float>(); hd->loc[i] = c->head[2][i].as<float>();
+  }
+}
+
+// Streams, events, split-K scratch and timing slots of one execution slot (after c->ops / c->wts are in place).
 static int slot_resources(ron_ctx* c) {
   if ((c->cfg.flags & RON_CFG_MULTI_STREAM) && !c->is_ssd()) {
     for (int l = 1; l < 4; ++l) {
-      RON_HIP_CHECK(hipStreamCreateWithFlags(&c->side[l], hipStreamNonBlocking));
-      RON_HIP_CHECK(hipEventCreateWithFlags(&c->lane_ready[l], hipEventDisableTiming));
-      RON_HIP_CHECK(hipEventCreateWithFlags(&c->lane_done[l], hipEventDisableTiming));
+      RON_HIP_CHECK(hipStreamCreateWithFlags(c->side[l].put(), hipStreamNonBlocking));
+      RON_HIP_CHECK(hipEventCreateWithFlags(c->lane_ready[l].put(), hipEventDisableTiming));
+      RON_HIP_CHECK(hipEventCreateWithFlags(c->lane_done[l].put(), hipEventDisableTiming));
     }
   }
   // split-K scratch: the largest slab set any launch (or grouped launch) of a lane can ask for at max_batch
@@ -1141,28 +1079,26 @@ static int slot_resources(ron_ctx* c) {
   }
   if (c->weights_owner != nullptr) for (int l = 0; l < 4; ++l) c->splitk_bytes[l] = c->weights_owner->splitk_bytes[l];
   for (int l = 0; l < 4; ++l)
-    if (c->splitk_bytes[l] > 0) RON_HIP_CHECK(ron::dev_malloc(&c->d_splitk[l], (size_t)c->splitk_bytes[l]));
+    if (c->splitk_bytes[l] > 0) RON_HIP_CHECK(ron::dev_malloc(c->splitk[l].put(), (size_t)c->splitk_bytes[l]));
   // ron_detect's head buffers and post-processing workspace, for max_batch: allocated (and the workspace zeroed) here, so that the
   // first ron_detect is as free of host synchronisation as every later one (include/ron_hip.h, Ownership)
-  {
-    const int mb = c->cfg.max_batch;
-    for (int i = 0; i < c->n_feat; ++i) {
-      const int A = c->feat_A[i];
-      const size_t cells = (size_t)mb * c->feat_h[i] * c->feat_w[i];
-      RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_head[0][i], cells * A * c->cfg.num_classes * sizeof(float)));
-      if (c->has_obj) RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_head[1][i], cells * A * 2 * sizeof(float)));
-      RON_HIP_CHECK(ron::dev_malloc((void**)&c->d_head[2][i], cells * A * 4 * sizeof(float)));
-    }
-    ron_heads hd;
-    memset(&hd, 0, sizeof(hd));
-    int rc = ron_heads_describe(c, &hd);
-    if (rc) return rc;
-    for (int i = 0; i < c->n_feat; ++i) { hd.cls[i] = c->d_head[0][i]; hd.obj[i] = c->d_head[1][i]; hd.loc[i] = c->d_head[2][i]; }
-    c->post_ws_bytes = ron_post_np_workspace_bytes(&hd, mb);
-    if (c->post_ws_bytes <= 0) return RON_ERR_INVALID;      // (ron_last_error says why)
-    RON_HIP_CHECK(ron::dev_malloc(&c->d_post_ws, (size_t)c->post_ws_bytes));
-    RON_HIP_CHECK(ron::dev_memset(c->d_post_ws, 0, (size_t)c->post_ws_bytes));      // once: the kernels keep the counters clean
+  const int mb = c->cfg.max_batch;
+  for (int i = 0; i < c->n_feat; ++i) {
+    const int A = c->feat_A[i];
+    const size_t cells = (size_t)mb * c->feat_h[i] * c->feat_w[i];
+    RON_HIP_CHECK(ron::dev_malloc(c->head[0][i].put(), cells * A * c->cfg.num_classes * sizeof(float)));
+    if (c->has_obj) RON_HIP_CHECK(ron::dev_malloc(c->head[1][i].put(), cells * A * 2 * sizeof(float)));
+    RON_HIP_CHECK(ron::dev_malloc(c->head[2][i].put(), cells * A * 4 * sizeof(float)));
   }
+  ron_heads hd;
+  memset(&hd, 0, sizeof(hd));
+  int rc = ron_heads_describe(c, &hd);
+  if (rc) return rc;
+  own_heads(c, &hd);
+  c->post_ws_bytes = ron_post_np_workspace_bytes(&hd, mb);
+  if (c->post_ws_bytes <= 0) return RON_ERR_INVALID;      // (ron_last_error says why)
+  RON_HIP_CHECK(ron::dev_malloc(c->post_ws.put(), (size_t)c->post_ws_bytes));
+  RON_HIP_CHECK(ron::dev_memset(c->post_ws, 0, (size_t)c->post_ws_bytes));      // once: the kernels keep the counters clean
   c->timing.assign(c->ops.size() + 1, OpTiming());
   // names ron_profile_get hands out: a grouped launch is reported on its first member as "group[first+N]", the other members as
   // "(name)"; built once so that the pointers stay valid until ron_destroy
@@ -1188,11 +1124,8 @@ extern "C" int ron_clone(ron_ctx* src, ron_ctx** out) {
   ron_ctx* c = nullptr;
   int rc = ron_create(&c, &src->cfg);
   if (rc) return rc;
-  c->packed = owner->packed;
+  c->wts = &owner->own;
   c->ops = owner->ops;
-  c->d_l2_gamma = owner->d_l2_gamma; c->d_stem_w = owner->d_stem_w; c->d_stem_b = owner->d_stem_b;
-  c->d_stem2_w = owner->d_stem2_w; c->d_stem2_b = owner->d_stem2_b; c->d_stem2_w1 = owner->d_stem2_w1;
-  c->stem_oscale = owner->stem_oscale;
   c->flops_per_image = owner->flops_per_image;
   c->grouped_launches = owner->grouped_launches;
   c->weights_owner = owner;
@@ -1214,14 +1147,33 @@ extern "C" int ron_heads_describe(const ron_ctx* c, ron_heads* hd) {
     hd->feat_h[i] = c->feat_h[i];
     hd->feat_w[i] = c->feat_w[i];
     hd->num_anchors[i] = c->feat_A[i];
-    hd->anchor_y[i] = c->d_anchor[i][0]; hd->anchor_x[i] = c->d_anchor[i][1];
-    hd->anchor_h[i] = c->d_anchor[i][2]; hd->anchor_w[i] = c->d_anchor[i][3];
+    hd->anchor_y[i] = c->anchor[i][0].as<float>(); hd->anchor_x[i] = c->anchor[i][1].as<float>();
+    hd->anchor_h[i] = c->anchor[i][2].as<float>(); hd->anchor_w[i] = c->anchor[i][3].as<float>();
     if (!c->has_obj) hd->obj[i] = nullptr;
   }
   return RON_OK;
 }
 
-extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* out, void* stream) {
+// One event on `st` for the call being recorded (the last of c->pending): an op's start on the op's stream, or a kStamp* mark.  An
+// op ends where the next op of its lane starts (or at the lane's end stamp).
+static int stamp(ron_ctx* c, hipStream_t st, int what) {
+  Event e;
+  if (!c->event_pool.empty()) { e = std::move(c->event_pool.back()); c->event_pool.pop_back(); }
+  else RON_HIP_CHECK(hipEventCreate(e.put()));
+  RON_HIP_CHECK(hipEventRecord(e, st));
+  c->pending.back().push_back(std::move(e));
+  c->pending_ops.back().push_back(what);
+  return RON_OK;
+}
+// the stream lane a stamp was recorded on
+static int stamp_lane(const ron_ctx* c, int what) {
+  if (what >= 0) return c->ops[what].lane;
+  return what >= kStampPostEnd ? 0 : (kStampLaneEnd - what) / 10;
+}
+
+// ron_forward; *recorded: the call was picked for per-launch timing (ron_profile_enable) and has opened c->pending.back()
+static int forward(ron_ctx* c, const float* d_images, int n, ron_heads* out, void* stream, bool* recorded) {
+  *recorded = false;
   RON_REQUIRE(c && d_images && out, "NULL argument");
   if (!c->finalized) { ron::set_error("ron_forward before ron_finalize_weights"); return RON_ERR_STATE; }
   RON_REQUIRE(n >= 1 && n <= c->cfg.max_batch, "batch %d outside [1, max_batch=%d]", n, c->cfg.max_batch);
@@ -1230,24 +1182,14 @@ extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* 
   RON_HIP_CHECK(on_device.err);
   int rc = ron_heads_describe(c, out);
   if (rc) return rc;
-  std::vector<hipEvent_t>* ev = nullptr;
   if (c->profiling > 0 && c->pending.size() < 256) {
     --c->profiling;
     c->pending.emplace_back();
     c->pending_ops.emplace_back();
-    ev = &c->pending.back();
+    *recorded = true;
   }
-  // one event per op start on the op's stream; an op ends where the next op of its lane starts (or at the lane's end stamp)
-  auto stamp = [&](hipStream_t st, int what) -> int {
-    if (!ev) return RON_OK;
-    hipEvent_t e;
-    if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-    else RON_HIP_CHECK(hipEventCreate(&e));
-    RON_HIP_CHECK(hipEventRecord(e, st));
-    ev->push_back(e);
-    c->pending_ops.back().push_back(what);
-    return RON_OK;
-  };
+  const bool rec = *recorded;
+  const Weights& W = *c->wts;
   const hipStream_t main_stream = (hipStream_t)stream;
   bool lane_started[4] = {false, false, false, false};
   for (size_t oi = 0; oi < c->ops.size(); ++oi) {
@@ -1261,23 +1203,23 @@ extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* 
         lane_started[o.lane] = true;
       }
     }
-    if ((rc = stamp(s, (int)oi))) return rc;
+    if (rec && (rc = stamp(c, s, (int)oi))) return rc;
     if (o.kind == OP_IM2COL) {
       const Tensor& t = c->tensors[o.out];
       if ((rc = launch_im2col_c3(d_images, n, t.H, t.W, c->cfg.dtype, t.d, t.C, s))) return rc;
     } else if (o.kind == OP_STEM) {
       const Tensor& t = c->tensors[o.out];
-      if ((rc = launch_stem_conv(d_images, n, t.H, t.W, c->cfg.dtype, c->d_stem_w, c->d_stem_b, c->view(o.out, n), s, c->stem_oscale))) return rc;
+      if ((rc = launch_stem_conv(d_images, n, t.H, t.W, c->cfg.dtype, W.stem_w, W.stem_b.as<float>(), c->view(o.out, n), s, W.stem_oscale))) return rc;
     } else if (o.kind == OP_STEM2) {
       const Tensor& t = c->tensors[o.out];
-      if ((rc = launch_stem2(d_images, n, 2 * t.H, 2 * t.W, c->cfg.dtype, c->d_stem2_w1, c->d_stem_b, c->d_stem2_w, c->d_stem2_b,
+      if ((rc = launch_stem2(d_images, n, 2 * t.H, 2 * t.W, c->cfg.dtype, W.stem2_w1, W.stem_b.as<float>(), W.stem2_w, W.stem2_b.as<float>(),
                              c->view(o.out, n), s))) return rc;
     } else if (o.kind == OP_POOL) {
       if ((rc = launch_maxpool2x2(c->view(o.in, n), c->view(o.out, n), c->cfg.dtype, s))) return rc;
     } else if (o.kind == OP_POOL3) {
       if ((rc = launch_maxpool3x3s1(c->view(o.in, n), c->view(o.out, n), c->cfg.dtype, s))) return rc;
     } else if (o.kind == OP_L2NORM) {
-      if ((rc = launch_l2norm(c->view(o.in, n), c->view(o.out, n), c->d_l2_gamma, c->cfg.dtype, s))) return rc;
+      if ((rc = launch_l2norm(c->view(o.in, n), c->view(o.out, n), W.l2_gamma.as<float>(), c->cfg.dtype, s))) return rc;
     } else if (o.group >= 0) {
       // this op and the following ones of the same group: one launch (the stamp above times the whole group)
       ConvLaunch L[kMaxConvGroup];
@@ -1289,7 +1231,7 @@ extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* 
       std::vector<std::array<int, kMaxConvGroup>>& plans = c->group_sk[(int)oi];      // filled by slot_resources
       if (plans.empty()) plans.assign(c->cfg.max_batch + 1, std::array<int, kMaxConvGroup>{});
       if (plans[n][0] == 0) conv_group_plan(L, (int)(j - oi), o.group_cfg, plans[n].data());
-      if ((rc = launch_conv_group(L, (int)(j - oi), o.group_cfg, c->d_splitk[o.lane], c->splitk_bytes[o.lane], s, plans[n].data()))) {
+      if ((rc = launch_conv_group(L, (int)(j - oi), o.group_cfg, c->splitk[o.lane], c->splitk_bytes[o.lane], s, plans[n].data()))) {
         std::string msg = ron_last_error();
         ron::set_error("group of %s: %s", o.name.c_str(), msg.c_str());
         return rc;
@@ -1321,9 +1263,9 @@ extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* 
       }
     }
   }
-  if (ev) {
-    if ((rc = stamp(main_stream, -1))) return rc;
-    for (int l = 1; l < 4; ++l) if (lane_started[l] && (rc = stamp(c->side[l], -1 - 10 * l))) return rc;
+  if (rec) {
+    if ((rc = stamp(c, main_stream, kStampLaneEnd))) return rc;
+    for (int l = 1; l < 4; ++l) if (lane_started[l] && (rc = stamp(c, c->side[l], kStampLaneEnd - 10 * l))) return rc;
   }
   for (int l = 1; l < 4; ++l)
     if (lane_started[l]) {                  // join: the caller's stream continues after every side branch
@@ -1331,6 +1273,11 @@ extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* 
       RON_HIP_CHECK(hipStreamWaitEvent(main_stream, c->lane_done[l], 0));
     }
   return RON_OK;
+}
+
+extern "C" int ron_forward(ron_ctx* c, const float* d_images, int n, ron_heads* out, void* stream) {
+  bool recorded;
+  return forward(c, d_images, n, out, stream, &recorded);
 }
 
 // ---- per-launch timing -----------------------------------------------------------------------
@@ -1345,26 +1292,23 @@ static int profile_collect(ron_ctx* c) {
     auto& call = c->pending[k];
     const auto& what = c->pending_ops[k];
     if (call.empty()) continue;
-    for (hipEvent_t e : call) RON_HIP_CHECK(hipEventSynchronize(e));
+    for (const Event& e : call) RON_HIP_CHECK(hipEventSynchronize(e));
     // the end of op i = the next stamp recorded on the same lane
     for (size_t i = 0; i < call.size(); ++i) {
-      int slot, lane;
-      if (what[i] >= 0) { slot = what[i]; lane = c->ops[slot].lane; }
-      else if (what[i] == -2) { slot = (int)c->ops.size(); lane = 0; }
+      int slot;
+      if (what[i] >= 0) slot = what[i];
+      else if (what[i] == kStampPostStart) slot = (int)c->ops.size();
       else continue;
+      const int lane = stamp_lane(c, what[i]);
       size_t j = i + 1;
-      for (; j < call.size(); ++j) {
-        const int w = what[j];
-        const int lj = w >= 0 ? c->ops[w].lane : (w == -1 || w == -2 || w == -3 ? 0 : (-1 - w) / 10);
-        if (lj == lane) break;
-      }
+      while (j < call.size() && stamp_lane(c, what[j]) != lane) ++j;
       if (j == call.size()) continue;
       float ms = 0.f;
       RON_HIP_CHECK(hipEventElapsedTime(&ms, call[i], call[j]));
       c->timing[slot].ms += ms;
       c->timing[slot].launches += 1;
     }
-    for (hipEvent_t e : call) c->event_pool.push_back(e);
+    for (Event& e : call) c->event_pool.push_back(std::move(e));
   }
   c->pending.clear();
   c->pending_ops.clear();
@@ -1432,7 +1376,7 @@ extern "C" int ron_end_point_copy(ron_ctx* c, const char* name, int n, float* d_
   int64_t shp[4];
   const int idx = ron_end_point_shape(c, name, n, shp);
   if (idx < 0) return idx;
-  if (c->tensors[idx - 1].d == nullptr) { ron::set_error("end point '%s' is not materialised in this configuration", name); return RON_ERR_UNKNOWN_NAME; }
+  if (c->tensors[idx - 1].d.p == nullptr) { ron::set_error("end point '%s' is not materialised in this configuration", name); return RON_ERR_UNKNOWN_NAME; }
   return launch_unpack(c->view(idx - 1, n), c->cfg.dtype, 0, d_out, (hipStream_t)stream);
 }
 
@@ -1445,31 +1389,20 @@ static int detect_with(ron_ctx* c, const float* d_images, int n, void* stream, P
   if (!c->finalized) { ron::set_error("ron_detect before ron_finalize_weights"); return RON_ERR_STATE; }
   ron_heads hd;
   memset(&hd, 0, sizeof(hd));
-  // (head buffers and workspace: slot_resources, at ron_finalize_weights / ron_clone)
-  for (int i = 0; i < c->n_feat; ++i) { hd.cls[i] = c->d_head[0][i]; hd.obj[i] = c->d_head[1][i]; hd.loc[i] = c->d_head[2][i]; }
+  own_heads(c, &hd);      // (head buffers and workspace: slot_resources, at ron_finalize_weights / ron_clone)
   if (c->post_ws_dirty) {
     // an earlier call failed between its select pass and the pass that zeroes the counters again: start from a clean workspace
-    RON_HIP_CHECK(ron::dev_memset_async(c->d_post_ws, 0, (size_t)c->post_ws_bytes, (hipStream_t)stream));
+    RON_HIP_CHECK(ron::dev_memset_async(c->post_ws, 0, (size_t)c->post_ws_bytes, (hipStream_t)stream));
     c->post_ws_dirty = false;
     c->tfe_counters_stale = false;
   }
-  int rc = ron_forward(c, d_images, n, &hd, stream);
+  bool prof;
+  int rc = forward(c, d_images, n, &hd, stream, &prof);
   if (rc) return rc;
-  const bool prof = !c->pending.empty() && !c->pending_ops.back().empty() && c->pending_ops.back().back() <= -1 &&
-                    c->pending_ops.back().back() != -3 && c->pending_ops.back().back() != -2;   // this call was recorded
-  auto post_stamp = [&](int what) -> int {
-    hipEvent_t e;
-    if (!c->event_pool.empty()) { e = c->event_pool.back(); c->event_pool.pop_back(); }
-    else RON_HIP_CHECK(hipEventCreate(&e));
-    RON_HIP_CHECK(hipEventRecord(e, (hipStream_t)stream));
-    c->pending.back().push_back(e);
-    c->pending_ops.back().push_back(what);
-    return RON_OK;
-  };
-  if (prof && (rc = post_stamp(-2))) return rc;
+  if (prof && (rc = stamp(c, (hipStream_t)stream, kStampPostStart))) return rc;
   rc = post(hd);
   if (rc != RON_OK) c->post_ws_dirty = true;
-  if (rc == RON_OK && prof) rc = post_stamp(-3);
+  if (rc == RON_OK && prof) rc = stamp(c, (hipStream_t)stream, kStampPostEnd);
   return rc;
 }
 
@@ -1480,7 +1413,7 @@ extern "C" int ron_detect(ron_ctx* c, const float* d_images, int n, const ron_po
     ron_post_cfg pc = *cfg;
     pc.input_flags = ron::kPostWsClean;      // logits + raw offsets straight from the conv stack; self-cleaning workspace (common.h)
     c->tfe_counters_stale = true;
-    return ron_post_np(&hd, n, &pc, c->d_post_ws, c->post_ws_bytes, out, nullptr, nullptr, stream);
+    return ron_post_np(&hd, n, &pc, c->post_ws, c->post_ws_bytes, out, nullptr, nullptr, stream);
   });
 }
 
@@ -1492,7 +1425,7 @@ extern "C" int ron_detect_tfe(ron_ctx* c, const float* d_images, int n, const ro
   if (rc != RON_OK) return rc;
   if (!c->finalized) { ron::set_error("ron_detect_tfe before ron_finalize_weights"); return RON_ERR_STATE; }
   return detect_with(c, d_images, n, stream, [&](ron_heads& hd) {
-    const int r = ron::post_tfe_ctx(&hd, n, c->cfg.max_batch, cfg, c->d_post_ws, c->post_ws_bytes, c->tfe_counters_stale, scores,
+    const int r = ron::post_tfe_ctx(&hd, n, c->cfg.max_batch, cfg, c->post_ws, c->post_ws_bytes, c->tfe_counters_stale, scores,
                                     bboxes, (hipStream_t)stream);
     if (r == RON_OK) c->tfe_counters_stale = false;
     return r;

@@ -11,15 +11,13 @@
 
 namespace {
 
-struct DevBuf {
-  void* p = nullptr;
-  ~DevBuf() { if (p) (void)hipFree(p); }
-  int alloc(int64_t bytes, bool zero) {
-    RON_HIP_CHECK(hipMalloc(&p, (size_t)bytes));
-    if (zero) RON_HIP_CHECK(hipMemset(p, 0, (size_t)bytes));
-    return RON_OK;
-  }
-};
+using ron::DevBuf;
+
+int alloc(DevBuf* b, int64_t bytes, bool zero) {
+  RON_HIP_CHECK(ron::dev_malloc(b->put(), (size_t)bytes));
+  if (zero) RON_HIP_CHECK(ron::dev_memset(b->p, 0, (size_t)bytes));
+  return RON_OK;
+}
 
 ron::TensorView make_view(void* base, int n, int h, int w, int c, int pad, int esz) {
   ron::TensorView v;
@@ -88,16 +86,13 @@ int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool w
   c.relu = d->relu;
   std::vector<uint8_t> wbytes = pack_conv_weights(rows, c.Npad, d->dtype, &c.oscale);
   int rc;
-  if ((rc = S->d_w.alloc((int64_t)wbytes.size(), false))) return rc;
-  if ((rc = S->d_b.alloc((int64_t)bias_pad.size() * 4, false))) return rc;
-  RON_HIP_CHECK(hipMemcpy(S->d_w.p, wbytes.data(), wbytes.size(), hipMemcpyHostToDevice));
-  RON_HIP_CHECK(hipMemcpy(S->d_b.p, bias_pad.data(), bias_pad.size() * 4, hipMemcpyHostToDevice));
+  RON_HIP_CHECK(dev_upload(&S->d_w, wbytes.data(), wbytes.size()));
+  RON_HIP_CHECK(dev_upload(&S->d_b, bias_pad.data(), bias_pad.size() * 4));
   c.wgt = S->d_w.p; c.wgt_bytes = (int64_t)wbytes.size(); c.bias = (const float*)S->d_b.p;
   if (!d->transpose && !S->is_c3 && dtype_is_half(d->dtype) && d->kh == 3 && d->kw == 3 && d->cin == 64 && c.Npad == d->cout && d->cout % 64 == 0) {
     // what ron_finalize_weights adds for such a layer: the weights once more as LDS images for the resident-weight kernel
     const std::vector<uint8_t> img = pack_conv_c64_weights(rows, c.Npad, d->dtype);
-    if ((rc = S->d_w_c64.alloc((int64_t)img.size(), false))) return rc;
-    RON_HIP_CHECK(hipMemcpy(S->d_w_c64.p, img.data(), img.size(), hipMemcpyHostToDevice));
+    RON_HIP_CHECK(dev_upload(&S->d_w_c64, img.data(), img.size()));
     c.wgt_c64 = S->d_w_c64.p;
   }
   if (S->is_c3) c.in = make_view(nullptr, d->n, d->h, d->w, chunk, 0, esz);
@@ -108,24 +103,24 @@ int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool w
     c.in.C = d->cin;
     c.in.coff = d->in_coff;
   }
-  if ((rc = S->d_in.alloc(c.in.bytes, true))) return rc;
+  if ((rc = alloc(&S->d_in, c.in.bytes, true))) return rc;
   c.in.base = S->d_in.p;
   c.pool = d->pool;
   if (d->pool) { S->ho = (S->ho + 1) / 2; S->wo = (S->wo + 1) / 2; }     // SAME pool: ceil
   // halo 1: exercises padded stores.  Split precision: pixels are whole 32-element (128-byte) chunks
   c.out = make_view(nullptr, d->n, S->ho, S->wo, d->dtype == RON_DTYPE_F16X3 ? round_up(d->cout, 32) : d->cout, 1, esz);
   c.out.C = d->cout;
-  if ((rc = S->d_out.alloc(c.out.bytes, true))) return rc;
+  if ((rc = alloc(&S->d_out, c.out.bytes, true))) return rc;
   c.out.base = S->d_out.p;
   if (with_residual) {
-    if ((rc = S->d_res.alloc(c.out.bytes, true))) return rc;
+    if ((rc = alloc(&S->d_res, c.out.bytes, true))) return rc;
     c.res = S->d_res.p;
   }
   c.splitk = d->splitk;
   c.center_from = d->transpose ? 0 : d->center_from;
   const int64_t sb = conv_scratch_bytes(c);
   if (sb > 0) {
-    if ((rc = S->d_scratch.alloc(sb, false))) return rc;
+    if ((rc = alloc(&S->d_scratch, sb, false))) return rc;
     c.scratch = S->d_scratch.p;
     c.scratch_bytes = sb;
   }
@@ -160,10 +155,8 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
     std::vector<float> b64(64, 0.f);
     if (bias) memcpy(b64.data(), bias, 64 * sizeof(float));
     DevBuf d_f, d_bb;
-    if ((rc = d_f.alloc((int64_t)frags.size() * 2, false))) return rc;
-    if ((rc = d_bb.alloc(64 * 4, false))) return rc;
-    RON_HIP_CHECK(hipMemcpy(d_f.p, frags.data(), frags.size() * 2, hipMemcpyHostToDevice));
-    RON_HIP_CHECK(hipMemcpy(d_bb.p, b64.data(), 64 * 4, hipMemcpyHostToDevice));
+    RON_HIP_CHECK(dev_upload(&d_f, frags.data(), frags.size() * 2));
+    RON_HIP_CHECK(dev_upload(&d_bb, b64.data(), 64 * 4));
     if ((rc = launch_stem_conv(x, d->n, d->h, d->w, d->dtype, d_f.p, (const float*)d_bb.p, S.c.out, s, oscale))) return rc;
     if ((rc = launch_unpack(S.c.out, d->dtype, 0, y, s))) return rc;
     RON_HIP_CHECK(hipStreamSynchronize(s));
@@ -200,7 +193,7 @@ extern "C" int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, con
   DevBuf d_full;
   c.out2 = make_view(nullptr, d->n, d->h, d->w, c.out.cstride, 1, (int)dtype_size(d->dtype));
   c.out2.C = d->cout;
-  if ((rc = d_full.alloc(c.out2.bytes, true))) return rc;
+  if ((rc = alloc(&d_full, c.out2.bytes, true))) return rc;
   c.out2.base = d_full.p;
   if ((rc = launch_pack_input(x, c.in, d->dtype, s))) return rc;
   if ((rc = launch_conv(c, s))) return rc;
@@ -268,7 +261,7 @@ extern "C" int ron_conv2d_heads_nhwc(const ron_conv_desc* d, int split_first, co
   DevBuf scratch2;
   const int64_t sb = conv_scratch_bytes(c);
   if (sb > c.scratch_bytes) {
-    if ((rc = scratch2.alloc(sb, false))) return rc;
+    if ((rc = alloc(&scratch2, sb, false))) return rc;
     c.scratch = scratch2.p;
     c.scratch_bytes = sb;
   }
@@ -297,9 +290,9 @@ extern "C" int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, f
   int rc;
   if ((rc = setup_conv(d, w.data(), b.data(), false, &S))) return rc;
   if (!zeros && (rc = launch_fill_random(S.c.in, d->dtype, 777u, nullptr))) return rc;
-  hipEvent_t e0, e1;
-  RON_HIP_CHECK(hipEventCreate(&e0));
-  RON_HIP_CHECK(hipEventCreate(&e1));
+  Event e0, e1;
+  RON_HIP_CHECK(hipEventCreate(e0.put()));
+  RON_HIP_CHECK(hipEventCreate(e1.put()));
   for (int i = 0; i < warmup; ++i) if ((rc = launch_conv(S.c, nullptr))) return rc;
   RON_HIP_CHECK(hipEventRecord(e0, nullptr));
   for (int i = 0; i < iters; ++i) if ((rc = launch_conv(S.c, nullptr))) return rc;
@@ -308,8 +301,6 @@ extern "C" int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, f
   float ms = 0.f;
   RON_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
   *ms_per_launch = ms / iters;
-  (void)hipEventDestroy(e0);
-  (void)hipEventDestroy(e1);
   return RON_OK;
 }
 
@@ -322,8 +313,8 @@ extern "C" int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, i
   TensorView vout = make_view(nullptr, n, (h + 1) / 2, (w + 1) / 2, c, 3, esz);     // SAME: ceil
   DevBuf d_in, d_out;
   int rc;
-  if ((rc = d_in.alloc(vin.bytes, true))) return rc;
-  if ((rc = d_out.alloc(vout.bytes, true))) return rc;
+  if ((rc = alloc(&d_in, vin.bytes, true))) return rc;
+  if ((rc = alloc(&d_out, vout.bytes, true))) return rc;
   vin.base = d_in.p; vout.base = d_out.p;
   if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
   if ((rc = launch_maxpool2x2(vin, vout, dtype, s))) return rc;

@@ -1,11 +1,11 @@
 """CPU: the host planners of libron_hip under AddressSanitizer + UBSan (`make -C ron_tensorflow_amd/csrc asan`).
 
-graph.cpp is 1.3 k lines of index tables (tensors, ops, grouped launch plans), conv_mfma.hip's host half picks tiles, split-K
+graph.cpp is 1.4 k lines of index tables (tensors, ops, grouped launch plans), conv_mfma.hip's host half picks tiles, split-K
 factors and tile orders from a schedule model: an index that runs off a table there corrupts memory quietly.  The library has
 a dry-run mode for exactly this (RON_PLAN_ONLY=1, csrc/common.h: every host-side decision is made, no HIP call); the `asan` target
 compiles every source host-only with -fsanitize=address,undefined and runs tools/plan_sweep.cpp, which builds contexts over
 variants x head plans x batch sizes, plans every batch 1..max_batch in each, and walks ron_detect / ron_clone up to the launches.
-Here the quick ladder (three batch sizes per plan, ~1 minute with the build); `make asan` without arguments runs all 115 contexts."""
+Here the quick ladder (three batch sizes per plan, ~1 minute with the build); `make asan` without arguments runs all 149 contexts."""
 import os
 import subprocess
 
