@@ -462,6 +462,9 @@ int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, int dtype, f
 /* Tooling: time the conv kernel alone on random data (ms per launch, HIP events, default stream, synchronises). */
 int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, float* ms_per_launch);
 int ron_conv_num_tile_cfgs(void);
+/* Tooling: workgroups of the fused stem kernel (conv1_1 + conv1_2 + pool1, bf16 / f16) that fit one CU of the current device, as the
+ * runtime's occupancy query answers for the launch's block and LDS size.  ron_forward requires 2 and fails otherwise. */
+int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
 
 #ifdef __cplusplus
 }

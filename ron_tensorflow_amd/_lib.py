@@ -142,6 +142,7 @@ SIGNATURES = {
     'ron_maxpool2x2_nhwc': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     'ron_conv2d_bench': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     'ron_conv_num_tile_cfgs': (C.c_int, []),
+    'ron_stem2_workgroups_per_cu': (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
 }
 
 _lib = None

@@ -78,22 +78,26 @@ hipError_t dev_upload(DevBuf* b, const void* host, size_t bytes);      // a new 
   } while (0)
 
 // hipFuncSetAttribute applies to the current device only: one of these per kernel instantiation remembers on which
-// devices (id < 64) the dynamic-LDS limit has been raised.  Safe from several host threads: nobody returns before the
+// devices (id < 64) the dynamic-LDS limit has been raised (or another per-device step, `once`, has been taken).  Safe from several host threads: nobody returns before the
 // attribute is set on his device.
 struct PerDeviceOnce {
   std::atomic<uint64_t> done{0};
   std::mutex mu;
-  hipError_t max_dynamic_lds(const void* kernel, int bytes) {
+  // f() once per device, again at the next call for as long as it fails; nothing is called in a dry run
+  template <class F> hipError_t once(F f) {
     if (plan_only()) return hipSuccess;
     int dev = 0;
-    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev <= 63;     // unknown device: just set it again
+    const bool known = hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev <= 63;     // unknown device: just do it again
     const uint64_t bit = known ? 1ull << dev : 0;
     if (known && (done.load(std::memory_order_acquire) & bit)) return hipSuccess;
     std::lock_guard<std::mutex> lock(mu);
     if (known && (done.load(std::memory_order_relaxed) & bit)) return hipSuccess;
-    const hipError_t e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    const hipError_t e = f();
     if (e == hipSuccess && known) done.fetch_or(bit, std::memory_order_release);
     return e;
+  }
+  hipError_t max_dynamic_lds(const void* kernel, int bytes) {
+    return once([&]() { return hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); });
   }
 };
 

@@ -3,7 +3,8 @@
 // Cin = 64 means K = 576: nine K steps.  The row-gather kernel (conv_mfma.hip) re-stages 16 KB of weights per step and tile for
 // that little work and spends a third of a tile's time filling and draining its pipeline (conv2_1 at batch 32: 175 us,
 // 0.69 PFLOP/s, the L2 -> LDS path of a CU at the rate the wide layers reach with twice the arithmetic per byte).  Here the
-// loop of stem2_kernel's conv1_2 phase (stem.hip) is its own kernel:
+// tap loop the fused stem's conv1_2 phase had while it kept its weights in LDS (stem.hip: stem2_kernel has since moved them into
+// registers and runs two workgroups of four waves per CU) is its own kernel:
 //   * a persistent workgroup owns one 64-channel slice of the outputs ("half": Cout / 64 of them) and keeps that slice's nine
 //     taps (72 KB, the exact LDS image packed by pack_conv_c64_weights) in LDS for its whole life;
 //   * per 8 x 32 pixel tile it stages the 10 x 34 x 64-channel input patch once (LDS-DMA, 43 KB, double buffered: the next

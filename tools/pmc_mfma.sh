@@ -23,7 +23,8 @@ dur = collections.defaultdict(float)      # ns of the dispatches, from the count
 have_ts = False
 for f in glob.glob('%s/pmc_mfma/*/*counter_collection.csv' % out):
     for r in csv.DictReader(open(f)):
-        k = r['Kernel_Name'].split('<')[0].split('(')[0].replace('void ', '')
+        # (kernels of an anonymous namespace - the stem - would otherwise all end at that parenthesis, as one entry 'ron::')
+        k = r['Kernel_Name'].replace('(anonymous namespace)::', '').split('<')[0].split('(')[0].replace('void ', '')
         per[k][r['Counter_Name']] += float(r['Counter_Value'])
         if r['Counter_Name'] == 'GRBM_GUI_ACTIVE':
             n[k] += 1
