@@ -303,6 +303,58 @@ int ron_bboxes_matching(const float* scores, const float* bboxes, int n, int num
                         float matching_threshold, int32_t* n_gbboxes, uint8_t* tp, uint8_t* fp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Label side: per-anchor targets and the held-out loss.  Forward computations only (no gradients).
+ * ---------------------------------------------------------------------------------------- */
+/* Per-anchor targets of one batch (device pointers, one per feature layer, coarse -> fine): what RONNet.bboxes_encode returns as
+ * four Python lists (nets/ron_vgg_320.py:173-186) and RONNet.losses consumes. */
+typedef struct {
+  int64_t* gclasses[RON_MAX_LAYERS];        /* [N,H,W,A]    label of a positive, 0 negative, -1 ignored */
+  float* glocalisations[RON_MAX_LAYERS];    /* [N,H,W,A,4]  (cx, cy, w, h) regression targets           */
+  float* gscores[RON_MAX_LAYERS];           /* [N,H,W,A]    overlap with the matched box                */
+  float* gbboxes[RON_MAX_LAYERS];           /* [N,H,W,A,4]  the anchors' corners (ymin,xmin,ymax,xmax)  */
+} ron_targets;
+
+/* RONNet.bboxes_encode (nets/ron_vgg_320.py:173-186) -> ssd_common.tf_ssd_bboxes_encode / tf_ssd_bboxes_encode_layer /
+ * do_dual_max_match / iou_matrix (nets/ssd_common.py:337-414, :77-147, :49-75, :27-47), for a batch: the reference encodes one image
+ * per call on the CPU in front of tf.train.batch (ron_net.py:277-304).
+ *   anchors : shapes + anchor_y/x/h/w of every layer (what ron_heads_describe fills; cls / obj / loc are not read)
+ *   glabels [N, G] int32 (0 = padding; the present rows are a prefix), gbboxes [N, G, 4], 1 <= G <= RON_MAX_GT (device)
+ *   allowed_borders : [num_layers] host ints (RONParams.allowed_borders), prior_scaling : [4] host floats
+ * An anchor whose best overlap is >= positive_threshold keeps its box (the reference's masks leave an overlap equal to the threshold
+ * matched), one in [ignore_threshold, positive_threshold) is ignored (-1), the rest are negative; the best anchor of every box is
+ * matched to it whatever its overlap (the lowest box wins an anchor several boxes claim).  An image without a present row (TF cannot
+ * run it) gives all-negative targets.  The anchors' corners, the classes, scores and the centre targets are those of the reference's
+ * float32 arithmetic bit for bit; the w / h targets go through logf.
+ * workspace: ron_bboxes_encode_workspace_bytes(n, g) bytes of device scratch (one 64-bit key per box). */
+int64_t ron_bboxes_encode_workspace_bytes(int n, int g);
+int ron_bboxes_encode(const ron_heads* anchors, int n, const int32_t* glabels, const float* gbboxes, int g,
+                      int img_h, int img_w, const int32_t* allowed_borders,
+                      float positive_threshold, float ignore_threshold, const float prior_scaling[4],
+                      void* workspace, int64_t workspace_bytes, ron_targets* out, void* stream);
+
+/* RONNet.losses (nets/ron_vgg_320.py:258-279) -> ron_losses (:635-778) with custom_layers.modified_smooth_l1 (sigma 3,
+ * nets/custom_layers.py:31-49), over the whole batch (the reference flattens layers, then images, into one list of rows).
+ *   heads        : raw logits cls [N,H,W,A,C], obj [N,H,W,A,2], loc [N,H,W,A,4] (anchor_* are not read)
+ *   objness_pred : per layer [N,H,W,A,1], P(object) (RONNet.net()[2])
+ *   targets      : gclasses / glocalisations of ron_bboxes_encode (gscores / gbboxes are not read, as in the reference)
+ *   rand_objness, rand_cls : one float in [0, 1) per row, in the flattened order (layer, image, row, column, anchor): the draws the
+ *                  reference makes inside the graph (tf.random_uniform, :703, :735) are inputs here
+ *   losses [4]   : cross_entropy_pos, cross_entropy_objectness, localization, their sum (device)
+ *   counts [6]   : n_pos, n_neg, n_cls_pos, n_cls_neg, rows in the objectness set, rows in the class set (device, int32)
+ * Deterministic: integer counts, float sums through per-workgroup partials added in a fixed order.
+ * workspace: ron_losses_workspace_bytes(heads, n) bytes of device scratch. */
+typedef struct {
+  float objness_threshold;  /* 0.03 */
+  float negative_ratio;     /* 3    */
+  float alpha;              /* 1/3: weight of the objectness term */
+  float beta;               /* 1/3: weight of the localisation term; the class term gets 1 - alpha - beta */
+} ron_loss_cfg;
+int64_t ron_losses_workspace_bytes(const ron_heads* heads, int n);
+int ron_losses(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
+               const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg,
+               void* workspace, int64_t workspace_bytes, float* losses, int32_t* counts, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Conv stack.  Replaces RONNet.net / ron_net / ron_net_reducedfc
  * (nets/ron_vgg_320.py:136-154, :434-508, :510-580) with slim semantics of ron_arg_scope
  * (:595-629).  Weights enter by TF variable name (SURVEY.md 8b "weight contract").

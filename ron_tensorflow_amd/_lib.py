@@ -16,6 +16,7 @@ EXPECTED_ABI = 2
 
 RON_MAX_LAYERS = 8
 RON_MAX_TOPK = 512
+RON_MAX_GT = 256
 
 RON_IN_CLS_IS_PROB = 1
 RON_IN_OBJ_IS_PROB = 2
@@ -67,6 +68,15 @@ class TfeCfg(C.Structure):
                 ('input_flags', C.c_uint32)]
 
 
+class Targets(C.Structure):
+    _fields_ = [('gclasses', C.c_void_p * RON_MAX_LAYERS), ('glocalisations', C.c_void_p * RON_MAX_LAYERS),
+                ('gscores', C.c_void_p * RON_MAX_LAYERS), ('gbboxes', C.c_void_p * RON_MAX_LAYERS)]
+
+
+class LossCfg(C.Structure):
+    _fields_ = [('objness_threshold', C.c_float), ('negative_ratio', C.c_float), ('alpha', C.c_float), ('beta', C.c_float)]
+
+
 class Detections(C.Structure):
     _fields_ = [('capacity', C.c_int32), ('classes', C.c_void_p), ('scores', C.c_void_p), ('bboxes', C.c_void_p),
                 ('anchor_index', C.c_void_p), ('count', C.c_void_p)]
@@ -114,6 +124,12 @@ SIGNATURES = {
     'ron_pack_records': (C.c_int, [C.POINTER(Detections), C.c_int, _P, _P]),
     'ron_gather_records': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     'ron_bboxes_matching': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P]),
+    'ron_bboxes_encode_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'ron_bboxes_encode': (C.c_int, [C.POINTER(Heads), C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int32),
+                                    C.c_float, C.c_float, C.POINTER(C.c_float), _P, C.c_int64, C.POINTER(Targets), _P]),
+    'ron_losses_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
+    'ron_losses': (C.c_int, [C.POINTER(Heads), C.POINTER(_P), C.POINTER(Targets), C.c_int, _P, _P, C.POINTER(LossCfg), _P,
+                             C.c_int64, _P, _P, _P]),
     'ron_post_tfe': (C.c_int, [C.POINTER(Heads), C.c_int, C.POINTER(TfeCfg), _P, C.c_int64, _P, _P, _P]),
     'ron_create': (C.c_int, [C.POINTER(_P), C.POINTER(Config)]),
     'ron_destroy': (C.c_int, [_P]),

@@ -291,6 +291,66 @@ class RONNet(object):
                                    clipping_bbox=clipping_bbox, top_k=top_k, keep_top_k=keep_top_k,
                                    nms_mode=nms_mode, min_size=0.03)
 
+    # ------------------------------------------------------------------ label side (forward only: no gradients)
+    def _ground_truth(self, labels, bboxes):
+        """(glabels int32 [N, G], gbboxes float32 [N, G, 4]) on the device, and whether the caller gave one image."""
+        if not torch.is_tensor(labels):
+            labels = torch.from_numpy(np.ascontiguousarray(labels).astype(np.int32))
+        if not torch.is_tensor(bboxes):
+            bboxes = torch.from_numpy(np.ascontiguousarray(bboxes, dtype=np.float32))
+        if not labels.is_cuda and labels.dtype != torch.int32:
+            labels = labels.to(torch.int32)                      # on the host, before the upload
+        labels = labels.to(self.device, torch.int32)
+        bboxes = bboxes.to(self.device, torch.float32)
+        single = labels.dim() == 1
+        if single:
+            labels, bboxes = labels[None], bboxes[None]
+        if labels.dim() != 2 or tuple(bboxes.shape) != tuple(labels.shape) + (4,):
+            raise ValueError('labels [G] / [N, G] and bboxes [G, 4] / [N, G, 4] expected')
+        return labels.contiguous(), bboxes.contiguous(), single
+
+    def bboxes_encode(self, labels, bboxes, anchors, positive_threshold=0.5, ignore_threshold=0.3, scope=None):
+        """Ground truth -> per-anchor targets (nets/ron_vgg_320.py:173-186 -> ssd_common.tf_ssd_bboxes_encode) on the GPU.
+        One image, labels [G] and bboxes [G, 4], as in the reference (outputs without a batch axis), or a padded batch [N, G] /
+        [N, G, 4] with label 0 as padding behind the present rows.  Returns the reference's four per-layer lists
+        (target_labels int64, target_localizations, target_scores, anchor corners)."""
+        glabels, gbboxes, single = self._ground_truth(labels, bboxes)
+        adev = ops.anchors_to_device(anchors, self.device)
+        shapes = [(int(np.shape(y)[0]), int(np.shape(y)[1]), int(np.size(h))) for (y, x, h, w) in anchors]
+        out = ops.bboxes_encode(glabels, gbboxes, adev, shapes, self.params.img_shape, self.params.allowed_borders,
+                                positive_threshold, ignore_threshold, tuple(self.params.prior_scaling))
+        return tuple([t[0] for t in lst] for lst in out) if single else out
+
+    def losses(self, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, gscores, match_threshold=0.5,
+               neg_threshold=0.3, objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3, label_smoothing=0.,
+               scope='ron_losses', rand_objness=None, rand_cls=None, generator=None):
+        """The RON losses (nets/ron_vgg_320.py:258-279 -> ron_losses, :635-778) of a batch, forward only.  `match_threshold`,
+        `neg_threshold` and `label_smoothing` are accepted and unused, as in the reference.  The reference draws its two random
+        negative selections inside the graph; here they are inputs (`rand_objness`, `rand_cls`: one float32 in [0, 1) per anchor of
+        the batch, flattened layer by layer) and are drawn with torch.rand from `generator` when None.  Returns 0-d GPU tensors
+        {'cross_entropy_pos', 'cross_entropy_objectness', 'localization', 'total'} and 'counts' (int32 [6], ops.LOSS_COUNTS)."""
+        rows = sum(int(g.numel()) for g in gclasses)
+        if rand_objness is None:
+            rand_objness = torch.rand((rows,), dtype=torch.float32, device=self.device, generator=generator)
+        if rand_cls is None:
+            rand_cls = torch.rand((rows,), dtype=torch.float32, device=self.device, generator=generator)
+        out, counts = ops.losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                                 objness_threshold=objness_threshold, negative_ratio=negative_ratio, alpha=alpha, beta=beta)
+        return {'cross_entropy_pos': out[0], 'cross_entropy_objectness': out[1], 'localization': out[2], 'total': out[3],
+                'counts': counts}
+
+    def validation_losses(self, images, glabels, gbboxes, positive_threshold=0.5, ignore_threshold=0.3, **loss_kwargs):
+        """Held-out loss of a labelled batch: net() -> bboxes_encode (on the network's own anchors) -> losses, all on the device;
+        no host copy in between.  glabels [N, G] (0 = padding), gbboxes [N, G, 4]; loss_kwargs go to `losses`."""
+        _, logits, objness_pred, objness_logits, localisations, _ = self.net(images, is_training=False, end_points=())
+        glabels, gbboxes, _ = self._ground_truth(glabels, gbboxes)
+        hd = _lib.Heads()
+        check(lib().ron_heads_describe(self._context(), C.byref(hd)))
+        gclasses, glocalisations, gscores, _ = ops.bboxes_encode(
+            glabels, gbboxes, None, None, self.params.img_shape, self.params.allowed_borders, positive_threshold, ignore_threshold,
+            tuple(self.params.prior_scaling), heads=hd)
+        return self.losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, gscores, **loss_kwargs)
+
     # ------------------------------------------------------------------ fused graded path
     def detect(self, inputs, objectness_thres=0.03, select_threshold=0.01, nms_threshold=0.45, top_k=400,
                bbox_img=(0., 0., 1., 1.), out=None):

@@ -228,6 +228,99 @@ def softmax_last(x, pick=-1):
 
 
 # --------------------------------------------------------------------------- #
+# label side: per-anchor targets and the held-out loss
+# --------------------------------------------------------------------------- #
+def _anchor_heads(anchors_dev, shapes):
+    """A Heads that carries shapes [(H, W, A)] and anchor pointers only (what ron_bboxes_encode reads)."""
+    h = Heads()
+    h.num_layers = len(shapes)
+    for i, (fh, fw, a) in enumerate(shapes):
+        h.feat_h[i], h.feat_w[i], h.num_anchors[i] = fh, fw, a
+        ay, ax, ah, aw = anchors_dev[i]
+        h.anchor_y[i], h.anchor_x[i], h.anchor_h[i], h.anchor_w[i] = ay.data_ptr(), ax.data_ptr(), ah.data_ptr(), aw.data_ptr()
+    return h
+
+
+def bboxes_encode(glabels, gbboxes, anchors_dev, shapes, img_shape, allowed_borders, positive_threshold=0.5,
+                  ignore_threshold=0.3, prior_scaling=(0.1, 0.1, 0.2, 0.2), heads=None):
+    """tf_ssd_bboxes_encode for a padded batch (ron_bboxes_encode): glabels int32 [N, G] (0 = padding), gbboxes [N, G, 4] on the GPU;
+    anchors_dev as anchors_to_device gives them, shapes [(H, W, A)] per layer (or `heads`: a Heads that already holds both).
+    Returns four per-layer lists: gclasses int64 [N,H,W,A], glocalisations [N,H,W,A,4], gscores [N,H,W,A], gbboxes [N,H,W,A,4]."""
+    assert glabels.is_cuda and glabels.dtype == torch.int32 and glabels.dim() == 2, 'glabels must be an int32 GPU tensor [N, G]'
+    assert gbboxes.is_cuda and gbboxes.dtype == torch.float32 and tuple(gbboxes.shape) == tuple(glabels.shape) + (4,), \
+        'gbboxes must be a float32 GPU tensor [N, G, 4]'
+    glabels, gbboxes = glabels.contiguous(), gbboxes.contiguous()
+    n, g = glabels.shape
+    dev = glabels.device
+    if heads is None:
+        heads = _anchor_heads(anchors_dev, shapes)
+    shapes = [(int(heads.feat_h[i]), int(heads.feat_w[i]), int(heads.num_anchors[i])) for i in range(heads.num_layers)]
+    assert len(allowed_borders) >= len(shapes), 'one allowed border per feature layer'
+    out = _lib.Targets()
+    gcl, glo, gsc, gbb = [], [], [], []
+    for i, (fh, fw, a) in enumerate(shapes):
+        gcl.append(torch.empty((n, fh, fw, a), dtype=torch.int64, device=dev))
+        glo.append(torch.empty((n, fh, fw, a, 4), dtype=torch.float32, device=dev))
+        gsc.append(torch.empty((n, fh, fw, a), dtype=torch.float32, device=dev))
+        gbb.append(torch.empty((n, fh, fw, a, 4), dtype=torch.float32, device=dev))
+        out.gclasses[i], out.glocalisations[i] = gcl[i].data_ptr(), glo[i].data_ptr()
+        out.gscores[i], out.gbboxes[i] = gsc[i].data_ptr(), gbb[i].data_ptr()
+    nbytes = lib().ron_bboxes_encode_workspace_bytes(n, g)
+    if nbytes < 0:
+        check(-1)
+    ws = _workspace(dev, nbytes)
+    borders = (C.c_int32 * len(shapes))(*[int(b) for b in allowed_borders[:len(shapes)]])
+    ps = (C.c_float * 4)(*prior_scaling)
+    check(lib().ron_bboxes_encode(C.byref(heads), n, ptr(glabels), ptr(gbboxes), g, int(img_shape[0]), int(img_shape[1]), borders,
+                                  float(positive_threshold), float(ignore_threshold), ps, ptr(ws), nbytes, C.byref(out),
+                                  current_stream()))
+    return gcl, glo, gsc, gbb
+
+
+LOSS_COUNTS = ('n_pos', 'n_neg', 'n_cls_pos', 'n_cls_neg', 'n_objness_set', 'n_cls_set')
+
+
+def losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+           objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3):
+    """ron_losses over the whole batch (nets/ron_vgg_320.py:635-778): per-layer lists of GPU tensors [N,H,W,A,*]; rand_objness /
+    rand_cls: one float32 in [0, 1) per row, flattened (layer, image, row, column, anchor).  Returns (losses float32 [4]:
+    cross_entropy_pos, cross_entropy_objectness, localization, total; counts int32 [6]: LOSS_COUNTS), both on the GPU."""
+    n = logits[0].shape[0]
+    dev = logits[0].device
+    heads, keep = _fill_heads(logits, objness_logits, localisations, None, int(logits[0].shape[-1]))
+    tg = _lib.Targets()
+    objp = (C.c_void_p * _lib.RON_MAX_LAYERS)()
+    rows = 0
+    for i in range(len(logits)):
+        shp = tuple(logits[i].shape[:4])
+        for name, t, want, dt in (('objness_logits', objness_logits[i], shp + (2,), torch.float32),
+                                  ('localisations', localisations[i], shp + (4,), torch.float32),
+                                  ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
+                                  ('gclasses', gclasses[i], shp, torch.int64)):
+            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == want, '%s[%d] must be a %s GPU tensor %s' % (name, i, dt, want)
+        op = objness_pred[i]
+        assert op.is_cuda and op.dtype == torch.float32 and op.numel() == gclasses[i].numel(), 'objness_pred[%d]: one float32 per anchor' % i
+        tensors = [op.contiguous(), gclasses[i].contiguous(), glocalisations[i].contiguous()]
+        keep.append(tensors)
+        objp[i], tg.gclasses[i], tg.glocalisations[i] = tensors[0].data_ptr(), tensors[1].data_ptr(), tensors[2].data_ptr()
+        rows += gclasses[i].numel()
+    for name, t in (('rand_objness', rand_objness), ('rand_cls', rand_cls)):
+        assert t.is_cuda and t.dtype == torch.float32 and t.numel() == rows, '%s must hold one float32 per anchor of the batch (%d)' % (name, rows)
+    rand_objness, rand_cls = rand_objness.contiguous(), rand_cls.contiguous()
+    cfg = _lib.LossCfg(float(objness_threshold), float(negative_ratio), float(alpha), float(beta))
+    nbytes = lib().ron_losses_workspace_bytes(C.byref(heads), n)
+    if nbytes < 0:
+        check(-1)
+    ws = _workspace(dev, nbytes)
+    out = torch.empty((4,), dtype=torch.float32, device=dev)
+    counts = torch.empty((6,), dtype=torch.int32, device=dev)
+    check(lib().ron_losses(C.byref(heads), objp, C.byref(tg), n, ptr(rand_objness), ptr(rand_cls), C.byref(cfg), ptr(ws), nbytes,
+                           ptr(out), ptr(counts), current_stream()))
+    del keep
+    return out, counts
+
+
+# --------------------------------------------------------------------------- #
 # single operators (parity tests of the conv kernels)
 # --------------------------------------------------------------------------- #
 def conv2d_nhwc(x, w, bias=None, residual=None, stride=1, dilation=1, relu=True, transpose=False, dtype='bf16',
