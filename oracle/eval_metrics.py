@@ -7,8 +7,12 @@ Restates the TF graph code the reference's eval driver runs after the detections
   P / R      ``tfe.precision_recall``             tf_extended/metrics.py:100-130
   AP         ``average_precision_voc07 / voc12``  tf_extended/metrics.py:212-258
 
-TensorFlow code: **parity unpinned** for matching / streaming; the two AP integrals ARE pinned against the reference's own
-numpy ``voc_ap`` (datasets/voc_eval.py:130-162, same definitions) through tests/golden/g6_voc_ap.npz.
+TensorFlow code, and still no TensorFlow run behind matching / streaming.  What stands behind the matching instead: a second
+reference written from the TensorFlow text alone (tests/match_cases.py ``match_ref``: jaccard matrix first, scalar walk after), equal
+to this one on cases built at every decision (threshold to the ulp, tied maxima, nothing to match, the matched flags, degenerate
+boxes, extents) and on seeded random inputs, and a table of mutants each of which those cases tell apart; the
+family-D list is carried by hand through streaming, P / R and both AP values.  The two AP integrals ARE pinned against the
+reference's own numpy ``voc_ap`` (datasets/voc_eval.py:130-162, same definitions) through tests/golden/g6_voc_ap.npz.
 """
 import numpy as np
 
