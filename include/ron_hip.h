@@ -355,6 +355,42 @@ int ron_losses(const ron_heads* heads, const float* const* objness_pred, const r
                void* workspace, int64_t workspace_bytes, float* losses, int32_t* counts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Training preprocessing: ron_preprocess_for_train (preprocessing/ssd_vgg_preprocessing.py:297-356), the chain
+ * preprocess_image(is_training=True) runs in front of RONNet.bboxes_encode (ron_net.py:249-306).  Its colour distortion is
+ * computed and discarded (:343-348); what reaches the network is
+ *   uint8 * (1/255) -> ssd_random_expand with probability 1/2 (tf_image.py:440-467) -> ssd_random_sample_patch (:310-438)
+ *   -> random_flip_left_right (:284-308) -> TF1 bilinear resize -> * 255 -> minus the means.
+ * TensorFlow's random streams cannot be reproduced: the draws are an input, RON_TRAIN_DRAWS uniform floats in [0, 1) per image
+ * at fixed slots (a slot belongs to one decision whether or not that decision is reached):
+ *   d[0]  expand unless d[0] < 0.5          d[1], d[2]  expand offsets x, y
+ *   d[3]  min_iou = {0.4 .. 0.9}[min(int(d[3] * 6), 5)]       d[4]  flip iff d[4] < 0.5
+ *   attempt (o, c) of the overlap loop (o < 10) and the centre loop (c < 10) owns the 12 slots from 5 + (o * 10 + c) * 12:
+ *   try t = 0..4 of sample_width_height reads (u_w, u_h) at +2t, +2t+1, the roi position reads (u_x, u_y) at +10, +11.
+ * A float draw is (u * (0.999f - 0.1f) + 0.1f) * size, an int draw in [0, m) is min((int)(u * (float)m), m - 1).
+ * ---------------------------------------------------------------------------------------- */
+#define RON_TRAIN_DRAWS 1205       /* 5 + 10 * 10 * 12 */
+#define RON_TRAIN_GEOM 12          /* int32 columns of one geometry row */
+/* Every random decision of a batch and its effect on the ground truth, without a host synchronisation (all pointers device):
+ *   hw [N, 2], glabels [N, G] int32 (0 = padding; the present rows are a prefix), gbboxes [N, G, 4], 1 <= G <= RON_MAX_GT,
+ *   draws [N, RON_TRAIN_DRAWS]
+ *   geom [N, RON_TRAIN_GEOM] : {expanded, canvas_h, canvas_w, img_y, img_x, crop_y, crop_x, crop_h, crop_w, flip,
+ *                               min_iou index, overlap iterations}: the image sits at (img_y, img_x) of a canvas_h x canvas_w
+ *                               canvas (the image itself when not expanded); the crop window of the canvas is flipped or not
+ *   glabels_out [N, G], gbboxes_out [N, G, 4] : the kept rows, transformed, at the front in their order, zeros behind
+ *   counts [N] : kept rows
+ * Padding rows take no part in any test.  All arithmetic is the reference's float32, one rounding per operation. */
+int ron_train_geometry(const int32_t* hw, const int32_t* glabels, const float* gbboxes, int n, int g, const float* draws,
+                       int32_t* geom, int32_t* glabels_out, float* gbboxes_out, int32_t* counts, void* stream);
+/* The pixels for a geometry table: packed / offsets / hw / means as for the evaluation entry above, out [n, out_h, out_w, 3].
+ * A canvas sample is (float)u8 * (1.0f / 255.0f) where the image lies and the fill elsewhere; the fill of channel c is
+ * (float)((double)sum_c / (255.0 * h * w)) from exact integer channel sums, i.e. the correctly rounded mean colour
+ * (tf.reduce_mean leaves the summation order open).  Bilinear over the flipped crop window, then * 255.0f, then - means[c].
+ * workspace: that many bytes of device scratch (the channel sums), zeroed by the call itself. */
+int64_t ron_preprocess_train_workspace_bytes(int n);
+int ron_preprocess_train(const uint8_t* packed, const int64_t* offsets, const int32_t* hw, const int32_t* geom, int n,
+                         int out_h, int out_w, const float* means, void* workspace, float* out, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Conv stack.  Replaces RONNet.net / ron_net / ron_net_reducedfc
  * (nets/ron_vgg_320.py:136-154, :434-508, :510-580) with slim semantics of ron_arg_scope
  * (:595-629).  Weights enter by TF variable name (SURVEY.md 8b "weight contract").

@@ -17,6 +17,8 @@ EXPECTED_ABI = 2
 RON_MAX_LAYERS = 8
 RON_MAX_TOPK = 512
 RON_MAX_GT = 256
+RON_TRAIN_DRAWS = 5 + 10 * 10 * 12
+RON_TRAIN_GEOM = 12
 
 RON_IN_CLS_IS_PROB = 1
 RON_IN_OBJ_IS_PROB = 2
@@ -121,6 +123,9 @@ SIGNATURES = {
     'ron_post_tfe_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
     'ron_preprocess_eval': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
     'ron_preprocess_eval_geom': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P]),
+    'ron_train_geometry': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, _P, _P, _P]),
+    'ron_preprocess_train_workspace_bytes': (C.c_int64, [C.c_int]),
+    'ron_preprocess_train': (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), _P, _P, _P]),
     'ron_pack_records': (C.c_int, [C.POINTER(Detections), C.c_int, _P, _P]),
     'ron_gather_records': (C.c_int, [_P, C.c_int, C.c_int, _P, _P, _P]),
     'ron_bboxes_matching': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int, C.c_float, _P, _P, _P, _P]),
