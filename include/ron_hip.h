@@ -303,7 +303,8 @@ int ron_bboxes_matching(const float* scores, const float* bboxes, int n, int num
                         float matching_threshold, int32_t* n_gbboxes, uint8_t* tp, uint8_t* fp, void* stream);
 
 /* ------------------------------------------------------------------------------------------
- * Label side: per-anchor targets and the held-out loss.  Forward computations only (no gradients).
+ * Label side: per-anchor targets, the loss, and the loss's gradient with respect to the head tensors (ron_losses_grad).  The
+ * gradient stops at the head tensors: there is no backward pass through the conv stack.
  * ---------------------------------------------------------------------------------------- */
 /* Per-anchor targets of one batch (device pointers, one per feature layer, coarse -> fine): what RONNet.bboxes_encode returns as
  * four Python lists (nets/ron_vgg_320.py:173-186) and RONNet.losses consumes. */
@@ -353,6 +354,32 @@ int64_t ron_losses_workspace_bytes(const ron_heads* heads, int n);
 int ron_losses(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
                const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg,
                void* workspace, int64_t workspace_bytes, float* losses, int32_t* counts, void* stream);
+
+/* ron_losses and, in the same call, d losses[0] / d cls, d losses[1] / d obj, d losses[2] / d loc.  Each term reads one head tensor,
+ * so the three tensors are also the gradient of losses[3]; a caller scales each by its upstream scalar.  objness_pred enters through
+ * comparisons only and has no gradient.  `losses` and `counts` are bit for bit what ron_losses writes (the same kernels run).
+ *   class term   : a row of the class set with clipped label l gets (softmax(x)[k] - [k == l]) * s_cls, softmax(x)[k] =
+ *                  expf(x[k] - max) / sum (the sum in index order), s_cls = (1 - alpha - beta) / n_cls_set when n_pos > 0, else 0;
+ *                  a label equal to num_classes gives a NaN row, as it gives a NaN loss
+ *   objectness   : the same over the objectness set with two logits and label (gclasses > 0), s_obj = alpha / n_objness_set
+ *                  when n_pos > 0, else 0
+ *   localisation : a row with gclasses > 0 and objness_pred > objness_threshold, d = pred - target per coordinate, gets
+ *                  (9 * d) * s_loc when |d| < 1.0f / 9.0f, else copysignf(1, d) * s_loc; s_loc = beta / n_cls_pos when n_cls_pos > 0,
+ *                  else 0
+ * Every element of the three tensors is written (rows outside a set: +0), nothing has to be cleared; no floating-point atomics, two
+ * calls give the same bytes; counts and scales stay on the device.  obj / d_obj rows are moved as 8-byte, loc / glocalisations /
+ * d_loc rows as 16-byte accesses: the layer pointers must be aligned accordingly.
+ * workspace: ron_losses_grad_workspace_bytes(heads, n) bytes of device scratch. */
+typedef struct {                       /* device pointers, one per layer, same layouts as ron_heads' cls / obj / loc */
+  float* d_cls[RON_MAX_LAYERS];        /* [N,H,W,A,C]  d losses[0] / d cls */
+  float* d_obj[RON_MAX_LAYERS];        /* [N,H,W,A,2]  d losses[1] / d obj */
+  float* d_loc[RON_MAX_LAYERS];        /* [N,H,W,A,4]  d losses[2] / d loc */
+} ron_head_grads;
+int64_t ron_losses_grad_workspace_bytes(const ron_heads* heads, int n);
+int ron_losses_grad(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
+                    const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg,
+                    void* workspace, int64_t workspace_bytes,
+                    float* losses, int32_t* counts, const ron_head_grads* grads, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Training preprocessing: ron_preprocess_for_train (preprocessing/ssd_vgg_preprocessing.py:297-356), the chain

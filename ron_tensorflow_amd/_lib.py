@@ -75,6 +75,11 @@ class Targets(C.Structure):
                 ('gscores', C.c_void_p * RON_MAX_LAYERS), ('gbboxes', C.c_void_p * RON_MAX_LAYERS)]
 
 
+class HeadGrads(C.Structure):
+    _fields_ = [('d_cls', C.c_void_p * RON_MAX_LAYERS), ('d_obj', C.c_void_p * RON_MAX_LAYERS),
+                ('d_loc', C.c_void_p * RON_MAX_LAYERS)]
+
+
 class LossCfg(C.Structure):
     _fields_ = [('objness_threshold', C.c_float), ('negative_ratio', C.c_float), ('alpha', C.c_float), ('beta', C.c_float)]
 
@@ -135,6 +140,9 @@ SIGNATURES = {
     'ron_losses_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
     'ron_losses': (C.c_int, [C.POINTER(Heads), C.POINTER(_P), C.POINTER(Targets), C.c_int, _P, _P, C.POINTER(LossCfg), _P,
                              C.c_int64, _P, _P, _P]),
+    'ron_losses_grad_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
+    'ron_losses_grad': (C.c_int, [C.POINTER(Heads), C.POINTER(_P), C.POINTER(Targets), C.c_int, _P, _P, C.POINTER(LossCfg), _P,
+                                  C.c_int64, _P, _P, C.POINTER(HeadGrads), _P]),
     'ron_post_tfe': (C.c_int, [C.POINTER(Heads), C.c_int, C.POINTER(TfeCfg), _P, C.c_int64, _P, _P, _P]),
     'ron_create': (C.c_int, [C.POINTER(_P), C.POINTER(Config)]),
     'ron_destroy': (C.c_int, [_P]),

@@ -9,6 +9,8 @@
 // Losses restate ron_losses (nets/ron_vgg_320.py:635-778): a counting pass (the selection probabilities need the four counts), a
 // pass that forms the per-row terms in float32 and adds them per workgroup, and a one-workgroup pass that adds the partial sums in a
 // fixed order.  The counts are integer atomics (exact); no floating-point atomics anywhere, so a call is reproducible bit for bit.
+// The gradient of the three terms with respect to the head tensors (ron_losses_grad) is one more pass behind those three: the set
+// sizes are known by then, so every element is written once, already scaled.
 //
 // Compiled with -ffp-contract=off: every comparison here decides an index or a set, it has to round once per operation like the
 // float32 numpy / TF arithmetic it restates.
@@ -335,6 +337,122 @@ __global__ __launch_bounds__(kThreads) void loss_final_kernel(const double* __re
   }
 }
 
+// ----------------------------------------------------------------------------------------------------------------- loss gradients
+struct GradDev {
+  float* d_cls[RON_MAX_LAYERS];
+  float* d_obj[RON_MAX_LAYERS];
+  float* d_loc[RON_MAX_LAYERS];
+};
+
+constexpr int kGradTileFloats = 8192;     // LDS tile of class logits: rows x (C | 1) floats, 32 KiB
+
+// d modified_smooth_l1 / d pred, one coordinate: 9 d in the square branch, sign(d) in the linear one; the branch test is the forward's
+__device__ inline float smooth_l1_grad(float pred, float target, float s) {
+  const float d = pred - target;
+  return fabsf(d) < 1.0f / 9.0f ? (9.0f * d) * s : copysignf(1.f, d) * s;
+}
+
+// One workgroup owns the same 256 rows as in loss_rows_kernel.  A thread forms its row's sets and writes the row's objectness and
+// localisation gradients (8 and 16 bytes per lane: contiguous across lanes).  The class rows go through LDS: the workgroup's rows of
+// the class set are loaded with consecutive lanes on consecutive floats, a thread takes its own row's maximum and sum (in index
+// order, like cross_entropy) from LDS at an odd row stride, and the gradient leaves with consecutive lanes on consecutive floats
+// again.  Rows x (C | 1) floats that do not fit the tile are taken in several chunks of rows.
+__global__ __launch_bounds__(kThreads) void loss_grad_kernel(LossDev p, GradDev q, const float* __restrict__ rand_obj,
+                                                             const float* __restrict__ rand_cls, const int32_t* __restrict__ counts,
+                                                             float w_cls, float w_obj, float w_loc) {
+  __shared__ float tile[kGradTileFloats];
+  __shared__ const float* row_src[kThreads];       // the row's logits (null: the row does not exist)
+  __shared__ float* row_dst[kThreads];
+  __shared__ int row_lab[kThreads];                // clipped label of a row of the class set, -1 outside it
+  __shared__ float row_mx[kThreads], row_sum[kThreads];
+  const int t = threadIdx.x;
+  const int C = p.num_classes;
+  const int n_pos = counts[0], n_cls_pos = counts[2];
+  const float p_obj = select_probability(p.negative_ratio, n_pos, counts[1]);
+  const float p_cls = select_probability(p.negative_ratio, n_cls_pos, counts[3]);
+  const float s_cls = n_pos > 0 ? w_cls / (float)counts[5] : 0.f;
+  const float s_obj = n_pos > 0 ? w_obj / (float)counts[4] : 0.f;
+  const float s_loc = n_cls_pos > 0 ? w_loc / (float)n_cls_pos : 0.f;
+  const long long r = (long long)blockIdx.x * kThreads + t;
+  const long long total = p.row_off[p.num_layers];
+  const float* src = nullptr;
+  float* dst = nullptr;
+  int lab = -1;
+  if (r < total) {
+    int l; long long j;
+    locate_row(p, r, &l, &j);
+    const long long g = p.gclasses[l][j];
+    const bool pos = g > 0, neg = g == 0;
+    const bool om = p.objp[l][j] > p.objness_threshold;
+    const bool in_obj = (neg && rand_obj[r] < p_obj) || pos;
+    const bool in_cls = (neg && om && rand_cls[r] < p_cls) || (pos && om);
+    src = p.cls[l] + j * C;
+    dst = q.d_cls[l] + j * C;
+    if (in_cls) lab = (int)(g < 0 ? 0 : (g > C ? C : g));
+    float2 go = make_float2(0.f, 0.f);
+    if (in_obj) {
+      const float2 x = *(reinterpret_cast<const float2*>(p.obj[l]) + j);
+      const float mx = fmaxf(x.x, x.y);
+      const float e0 = expf(x.x - mx), e1 = expf(x.y - mx);
+      const float sum = e0 + e1;
+      go.x = (e0 / sum - (pos ? 0.f : 1.f)) * s_obj;
+      go.y = (e1 / sum - (pos ? 1.f : 0.f)) * s_obj;
+    }
+    *(reinterpret_cast<float2*>(q.d_obj[l]) + j) = go;
+    float4 gl = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (pos && om) {
+      const float4 a = *(reinterpret_cast<const float4*>(p.loc[l]) + j);
+      const float4 b = *(reinterpret_cast<const float4*>(p.gloc[l]) + j);
+      gl = make_float4(smooth_l1_grad(a.x, b.x, s_loc), smooth_l1_grad(a.y, b.y, s_loc), smooth_l1_grad(a.z, b.z, s_loc),
+                       smooth_l1_grad(a.w, b.w, s_loc));
+    }
+    *(reinterpret_cast<float4*>(q.d_loc[l]) + j) = gl;
+  }
+  row_src[t] = src;
+  row_dst[t] = dst;
+  row_lab[t] = lab;
+  const int stride = C | 1;                                               // odd: a thread per row walks the banks without conflict
+  const int chunk = kGradTileFloats / stride < kThreads ? kGradTileFloats / stride : kThreads;      // >= 63 rows (C <= 128)
+  const int dq = kThreads / C, dr = kThreads - dq * C;
+  for (int r0 = 0; r0 < kThreads; r0 += chunk) {
+    const int nrows = kThreads - r0 < chunk ? kThreads - r0 : chunk;
+    const int nelem = nrows * C;
+    __syncthreads();                                                      // row_*[] written; the previous chunk's tile consumed
+    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
+      if (row_lab[r0 + row] >= 0) tile[row * stride + k] = row_src[r0 + row][k];
+      row += dq; k += dr;
+      if (k >= C) { k -= C; ++row; }
+    }
+    __syncthreads();
+    if (t >= r0 && t < r0 + nrows && lab >= 0) {
+      const float* x = tile + (t - r0) * stride;
+      float mx = x[0];
+      for (int i = 1; i < C; ++i) mx = fmaxf(mx, x[i]);
+      float sum = 0.f;
+      for (int i = 0; i < C; ++i) sum += expf(x[i] - mx);
+      row_mx[t] = mx;
+      row_sum[t] = sum;
+    }
+    __syncthreads();
+    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
+      float* out = row_dst[r0 + row];
+      if (out != nullptr) {
+        const int rl = row_lab[r0 + row];
+        float v = 0.f;
+        if (rl >= C) {
+          v = __uint_as_float(0x7fc00000u);                               // label out of range: the forward's row is NaN
+        } else if (rl >= 0) {
+          const float pk = expf(tile[row * stride + k] - row_mx[r0 + row]) / row_sum[r0 + row];
+          v = (pk - (k == rl ? 1.f : 0.f)) * s_cls;
+        }
+        out[k] = v;
+      }
+      row += dq; k += dr;
+      if (k >= C) { k -= C; ++row; }
+    }
+  }
+}
+
 int check_layers(const ron_heads* h, const char* what) {
   RON_REQUIRE(h != nullptr, "%s: null argument", what);
   RON_REQUIRE(h->num_layers >= 1 && h->num_layers <= RON_MAX_LAYERS, "%s: %d layers not in [1, %d]", what, h->num_layers,
@@ -419,46 +537,103 @@ extern "C" int64_t ron_losses_workspace_bytes(const ron_heads* heads, int n) {
   return ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
 }
 
-extern "C" int ron_losses(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
-                          const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg, void* workspace,
-                          int64_t workspace_bytes, float* losses, int32_t* counts, void* stream) {
-  if (int rc = ron::check_layers(heads, "ron_losses")) return rc;
-  RON_REQUIRE(n > 0, "ron_losses: bad batch %d", n);
+// what ron_losses and ron_losses_grad share: the arguments checked, the kernels' parameter block filled
+static int loss_setup(const char* what, const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
+                      const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg, void* workspace,
+                      int64_t workspace_bytes, float* losses, int32_t* counts, ron::LossDev* out, int64_t* out_wgs) {
+  if (int rc = ron::check_layers(heads, what)) return rc;
+  RON_REQUIRE(n > 0, "%s: bad batch %d", what, n);
   RON_REQUIRE(objness_pred != nullptr && targets != nullptr && rand_objness != nullptr && rand_cls != nullptr && cfg != nullptr &&
-              losses != nullptr && counts != nullptr, "ron_losses: null argument");
-  RON_REQUIRE(heads->num_classes >= 2 && heads->num_classes <= RON_MAX_CLASSES, "ron_losses: %d classes not in [2, %d]",
+              losses != nullptr && counts != nullptr, "%s: null argument", what);
+  RON_REQUIRE(heads->num_classes >= 2 && heads->num_classes <= RON_MAX_CLASSES, "%s: %d classes not in [2, %d]", what,
               heads->num_classes, RON_MAX_CLASSES);
   ron::LossDev p = {};
   p.num_layers = heads->num_layers;
   p.num_classes = heads->num_classes;
   int64_t rows = 0;
   for (int l = 0; l < p.num_layers; ++l) {
-    RON_REQUIRE(heads->cls[l] && heads->obj[l] && heads->loc[l] && objness_pred[l], "ron_losses: null head pointer of layer %d", l);
-    RON_REQUIRE(targets->gclasses[l] && targets->glocalisations[l], "ron_losses: null target pointer of layer %d", l);
+    RON_REQUIRE(heads->cls[l] && heads->obj[l] && heads->loc[l] && objness_pred[l], "%s: null head pointer of layer %d", what, l);
+    RON_REQUIRE(targets->gclasses[l] && targets->glocalisations[l], "%s: null target pointer of layer %d", what, l);
     p.row_off[l] = rows;
     rows += (int64_t)n * heads->feat_h[l] * heads->feat_w[l] * heads->num_anchors[l];
     p.cls[l] = heads->cls[l]; p.obj[l] = heads->obj[l]; p.loc[l] = heads->loc[l]; p.objp[l] = objness_pred[l];
     p.gclasses[l] = targets->gclasses[l]; p.gloc[l] = targets->glocalisations[l];
   }
   p.row_off[p.num_layers] = rows;
-  RON_REQUIRE(rows < (1ll << 24) * 64, "ron_losses: too many rows");
+  RON_REQUIRE(rows < (1ll << 24) * 64, "%s: too many rows", what);
   p.objness_threshold = cfg->objness_threshold;
   p.negative_ratio = cfg->negative_ratio;
   const int64_t wgs = (rows + ron::kThreads - 1) / ron::kThreads;
   const int64_t need = ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "ron_losses: workspace of %lld bytes, %lld needed",
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", what,
               (long long)workspace_bytes, (long long)need);
-  RON_REQUIRE(((uintptr_t)workspace & 7) == 0, "ron_losses: workspace must be 8-byte aligned");
+  RON_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
+  *out = p;
+  *out_wgs = wgs;
+  return RON_OK;
+}
+
+// the class term's weight: 1 - alpha - beta, formed once in double (:750)
+static float class_weight(const ron_loss_cfg* cfg) { return (float)(1.0 - (double)cfg->alpha - (double)cfg->beta); }
+
+// the three forward launches; the counters and the partial sums stay in the workspace
+static int loss_forward(const ron::LossDev& p, int64_t wgs, const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg,
+                        void* workspace, float* losses, int32_t* counts, hipStream_t s) {
   int32_t* d_counts = (int32_t*)workspace;
   double* partials = (double*)((char*)workspace + ron::kPartialsOffset);
-  // the class term's weight: 1 - alpha - beta, formed once in double (:750)
-  const float w_cls = (float)(1.0 - (double)cfg->alpha - (double)cfg->beta);
-  hipStream_t s = (hipStream_t)stream;
   RON_HIP_CHECK(ron::dev_memset_async(workspace, 0, (size_t)ron::kPartialsOffset, s));
   RON_LAUNCH(ron::loss_count_kernel, dim3((unsigned)wgs), dim3(ron::kThreads), 0, s, p, d_counts);
   RON_LAUNCH(ron::loss_rows_kernel, dim3((unsigned)wgs), dim3(ron::kThreads), 0, s, p, rand_objness, rand_cls, d_counts, partials);
   RON_LAUNCH(ron::loss_final_kernel, dim3(1), dim3(ron::kThreads), 0, s, (const double*)partials, (int)wgs, (const int32_t*)d_counts,
-             w_cls, cfg->alpha, cfg->beta, losses, counts);
+             class_weight(cfg), cfg->alpha, cfg->beta, losses, counts);
+  return RON_OK;
+}
+
+extern "C" int ron_losses(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
+                          const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg, void* workspace,
+                          int64_t workspace_bytes, float* losses, int32_t* counts, void* stream) {
+  ron::LossDev p;
+  int64_t wgs;
+  if (int rc = loss_setup("ron_losses", heads, objness_pred, targets, n, rand_objness, rand_cls, cfg, workspace, workspace_bytes,
+                          losses, counts, &p, &wgs))
+    return rc;
+  if (int rc = loss_forward(p, wgs, rand_objness, rand_cls, cfg, workspace, losses, counts, (hipStream_t)stream)) return rc;
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+extern "C" int64_t ron_losses_grad_workspace_bytes(const ron_heads* heads, int n) {
+  if (ron::check_layers(heads, "ron_losses_grad_workspace_bytes") != RON_OK) return -1;
+  if (n <= 0) {
+    ron::set_error("ron_losses_grad_workspace_bytes: bad batch %d", n);
+    return -1;
+  }
+  const int64_t wgs = (loss_rows(heads, n) + ron::kThreads - 1) / ron::kThreads;
+  return ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
+}
+
+extern "C" int ron_losses_grad(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,
+                               const float* rand_objness, const float* rand_cls, const ron_loss_cfg* cfg, void* workspace,
+                               int64_t workspace_bytes, float* losses, int32_t* counts, const ron_head_grads* grads, void* stream) {
+  ron::LossDev p;
+  int64_t wgs;
+  if (int rc = loss_setup("ron_losses_grad", heads, objness_pred, targets, n, rand_objness, rand_cls, cfg, workspace,
+                          workspace_bytes, losses, counts, &p, &wgs))
+    return rc;
+  RON_REQUIRE(grads != nullptr, "ron_losses_grad: null argument");
+  ron::GradDev q = {};
+  for (int l = 0; l < p.num_layers; ++l) {
+    RON_REQUIRE(grads->d_cls[l] && grads->d_obj[l] && grads->d_loc[l], "ron_losses_grad: null gradient pointer of layer %d", l);
+    // the kernel moves an objectness row as one 8-byte and a localisation row as one 16-byte access
+    RON_REQUIRE((((uintptr_t)p.obj[l] | (uintptr_t)grads->d_obj[l]) & 7) == 0 &&
+                (((uintptr_t)p.loc[l] | (uintptr_t)p.gloc[l] | (uintptr_t)grads->d_loc[l]) & 15) == 0,
+                "ron_losses_grad: obj / d_obj of layer %d must be 8-byte, loc / glocalisations / d_loc 16-byte aligned", l);
+    q.d_cls[l] = grads->d_cls[l]; q.d_obj[l] = grads->d_obj[l]; q.d_loc[l] = grads->d_loc[l];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (int rc = loss_forward(p, wgs, rand_objness, rand_cls, cfg, workspace, losses, counts, s)) return rc;
+  RON_LAUNCH(ron::loss_grad_kernel, dim3((unsigned)wgs), dim3(ron::kThreads), 0, s, p, q, rand_objness, rand_cls,
+             (const int32_t*)workspace, class_weight(cfg), cfg->alpha, cfg->beta);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
 }

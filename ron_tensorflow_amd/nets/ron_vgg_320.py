@@ -44,6 +44,31 @@ class _DataFormatScope(object):
         return False
 
 
+class _LossesFunction(torch.autograd.Function):
+    """RONNet.losses for head tensors that require grad.  forward: one ron_losses_grad call, the unit gradients saved; backward:
+    each saved tensor times (upstream of its term + upstream of the total), a torch multiply on the device.  The inputs are
+    (number of layers, (objness_pred, gclasses, glocalisations, rand_objness, rand_cls), loss keyword arguments, then the logits,
+    objness_logits and localisations of every layer); the outputs the four losses as one tensor [4] and the counts."""
+
+    @staticmethod
+    def forward(ctx, num_layers, fixed, kwargs, *heads):
+        logits, objness_logits, localisations = (list(heads[i * num_layers:(i + 1) * num_layers]) for i in range(3))
+        objness_pred, gclasses, glocalisations, rand_objness, rand_cls = fixed
+        out, counts, d_cls, d_obj, d_loc = ops.losses_grad(logits, localisations, objness_logits, objness_pred, gclasses,
+                                                           glocalisations, rand_objness, rand_cls, **kwargs)
+        ctx.save_for_backward(*(d_cls + d_obj + d_loc))
+        ctx.num_layers = num_layers
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    def backward(ctx, g, _g_counts):
+        n = ctx.num_layers
+        scales = (g[0] + g[3], g[1] + g[3], g[2] + g[3])              # 0-d tensors on the device
+        grads = [d * scales[i // n] if ctx.needs_input_grad[3 + i] else None for i, d in enumerate(ctx.saved_tensors)]
+        return (None, None, None) + tuple(grads)
+
+
 class RONNet(object):
     """RON VGG-based 320 network: conv4 -> 40x40, conv5 -> 20x20, fc6 -> 10x10, fc7 -> 5x5."""
     default_params = RONParams(
@@ -291,7 +316,7 @@ class RONNet(object):
                                    clipping_bbox=clipping_bbox, top_k=top_k, keep_top_k=keep_top_k,
                                    nms_mode=nms_mode, min_size=0.03)
 
-    # ------------------------------------------------------------------ label side (forward only: no gradients)
+    # ------------------------------------------------------------------ label side (gradients stop at the head tensors)
     def _ground_truth(self, labels, bboxes):
         """(glabels int32 [N, G], gbboxes float32 [N, G, 4]) on the device, and whether the caller gave one image."""
         if not torch.is_tensor(labels):
@@ -321,23 +346,51 @@ class RONNet(object):
                                 positive_threshold, ignore_threshold, tuple(self.params.prior_scaling))
         return tuple([t[0] for t in lst] for lst in out) if single else out
 
-    def losses(self, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, gscores, match_threshold=0.5,
-               neg_threshold=0.3, objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3, label_smoothing=0.,
-               scope='ron_losses', rand_objness=None, rand_cls=None, generator=None):
-        """The RON losses (nets/ron_vgg_320.py:258-279 -> ron_losses, :635-778) of a batch, forward only.  `match_threshold`,
-        `neg_threshold` and `label_smoothing` are accepted and unused, as in the reference.  The reference draws its two random
-        negative selections inside the graph; here they are inputs (`rand_objness`, `rand_cls`: one float32 in [0, 1) per anchor of
-        the batch, flattened layer by layer) and are drawn with torch.rand from `generator` when None.  Returns 0-d GPU tensors
-        {'cross_entropy_pos', 'cross_entropy_objectness', 'localization', 'total'} and 'counts' (int32 [6], ops.LOSS_COUNTS)."""
+    def _loss_draws(self, gclasses, rand_objness, rand_cls, generator):
         rows = sum(int(g.numel()) for g in gclasses)
         if rand_objness is None:
             rand_objness = torch.rand((rows,), dtype=torch.float32, device=self.device, generator=generator)
         if rand_cls is None:
             rand_cls = torch.rand((rows,), dtype=torch.float32, device=self.device, generator=generator)
-        out, counts = ops.losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
-                                 objness_threshold=objness_threshold, negative_ratio=negative_ratio, alpha=alpha, beta=beta)
+        return rand_objness, rand_cls
+
+    def losses(self, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, gscores, match_threshold=0.5,
+               neg_threshold=0.3, objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3, label_smoothing=0.,
+               scope='ron_losses', rand_objness=None, rand_cls=None, generator=None):
+        """The RON losses (nets/ron_vgg_320.py:258-279 -> ron_losses, :635-778) of a batch.  `match_threshold`,
+        `neg_threshold` and `label_smoothing` are accepted and unused, as in the reference.  The reference draws its two random
+        negative selections inside the graph; here they are inputs (`rand_objness`, `rand_cls`: one float32 in [0, 1) per anchor of
+        the batch, flattened layer by layer) and are drawn with torch.rand from `generator` when None.  Returns 0-d GPU tensors
+        {'cross_entropy_pos', 'cross_entropy_objectness', 'localization', 'total'} and 'counts' (int32 [6], ops.LOSS_COUNTS).
+        When autograd is enabled and a tensor of `logits`, `objness_logits` or `localisations` requires grad, the four scalars are
+        differentiable with respect to those tensors (ron_losses_grad, one call; the same values bit for bit); `objness_pred` enters
+        through comparisons only and gets no gradient."""
+        rand_objness, rand_cls = self._loss_draws(gclasses, rand_objness, rand_cls, generator)
+        kwargs = dict(objness_threshold=objness_threshold, negative_ratio=negative_ratio, alpha=alpha, beta=beta)
+        heads = list(logits) + list(objness_logits) + list(localisations)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in heads):
+            out, counts = _LossesFunction.apply(len(logits), (objness_pred, gclasses, glocalisations, rand_objness, rand_cls), kwargs,
+                                                *heads)
+        else:
+            out, counts = ops.losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness,
+                                     rand_cls, **kwargs)
         return {'cross_entropy_pos': out[0], 'cross_entropy_objectness': out[1], 'localization': out[2], 'total': out[3],
                 'counts': counts}
+
+    def losses_and_gradients(self, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, gscores,
+                             match_threshold=0.5, neg_threshold=0.3, objness_threshold=0.03, negative_ratio=3., alpha=1. / 3,
+                             beta=1. / 3, label_smoothing=0., scope='ron_losses', rand_objness=None, rand_cls=None, generator=None):
+        """`losses` and, from the same call (ron_losses_grad), 'gradients': {'logits', 'objness_logits', 'localisations'}: per-layer
+        lists of float32 GPU tensors shaped like the inputs, d cross_entropy_pos / d logits, d cross_entropy_objectness /
+        d objness_logits and d localization / d localisations.  Each term reads one head tensor, so these are also the gradients of
+        'total'.  The loss values are those of `losses` bit for bit."""
+        rand_objness, rand_cls = self._loss_draws(gclasses, rand_objness, rand_cls, generator)
+        with torch.no_grad():
+            out, counts, d_cls, d_obj, d_loc = ops.losses_grad(
+                logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                objness_threshold=objness_threshold, negative_ratio=negative_ratio, alpha=alpha, beta=beta)
+        return {'cross_entropy_pos': out[0], 'cross_entropy_objectness': out[1], 'localization': out[2], 'total': out[3],
+                'counts': counts, 'gradients': {'logits': d_cls, 'objness_logits': d_obj, 'localisations': d_loc}}
 
     def validation_losses(self, images, glabels, gbboxes, positive_threshold=0.5, ignore_threshold=0.3, **loss_kwargs):
         """Held-out loss of a labelled batch: net() -> bboxes_encode (on the network's own anchors) -> losses, all on the device;

@@ -280,11 +280,9 @@ def bboxes_encode(glabels, gbboxes, anchors_dev, shapes, img_shape, allowed_bord
 LOSS_COUNTS = ('n_pos', 'n_neg', 'n_cls_pos', 'n_cls_neg', 'n_objness_set', 'n_cls_set')
 
 
-def losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
-           objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3):
-    """ron_losses over the whole batch (nets/ron_vgg_320.py:635-778): per-layer lists of GPU tensors [N,H,W,A,*]; rand_objness /
-    rand_cls: one float32 in [0, 1) per row, flattened (layer, image, row, column, anchor).  Returns (losses float32 [4]:
-    cross_entropy_pos, cross_entropy_objectness, localization, total; counts int32 [6]: LOSS_COUNTS), both on the GPU."""
+def _losses_call(grad, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                 objness_threshold, negative_ratio, alpha, beta, out_grads=None):
+    """ron_losses (grad False) or ron_losses_grad (grad True) on checked arguments."""
     n = logits[0].shape[0]
     dev = logits[0].device
     heads, keep = _fill_heads(logits, objness_logits, localisations, None, int(logits[0].shape[-1]))
@@ -308,16 +306,52 @@ def losses(logits, localisations, objness_logits, objness_pred, gclasses, glocal
         assert t.is_cuda and t.dtype == torch.float32 and t.numel() == rows, '%s must hold one float32 per anchor of the batch (%d)' % (name, rows)
     rand_objness, rand_cls = rand_objness.contiguous(), rand_cls.contiguous()
     cfg = _lib.LossCfg(float(objness_threshold), float(negative_ratio), float(alpha), float(beta))
-    nbytes = lib().ron_losses_workspace_bytes(C.byref(heads), n)
+    nbytes = (lib().ron_losses_grad_workspace_bytes if grad else lib().ron_losses_workspace_bytes)(C.byref(heads), n)
     if nbytes < 0:
         check(-1)
     ws = _workspace(dev, nbytes)
     out = torch.empty((4,), dtype=torch.float32, device=dev)
     counts = torch.empty((6,), dtype=torch.int32, device=dev)
-    check(lib().ron_losses(C.byref(heads), objp, C.byref(tg), n, ptr(rand_objness), ptr(rand_cls), C.byref(cfg), ptr(ws), nbytes,
-                           ptr(out), ptr(counts), current_stream()))
+    if not grad:
+        check(lib().ron_losses(C.byref(heads), objp, C.byref(tg), n, ptr(rand_objness), ptr(rand_cls), C.byref(cfg), ptr(ws), nbytes,
+                               ptr(out), ptr(counts), current_stream()))
+        del keep
+        return out, counts
+    hg = _lib.HeadGrads()
+    if out_grads is None:
+        out_grads = tuple([torch.empty(t.shape, dtype=torch.float32, device=dev) for t in lst]
+                          for lst in (logits, objness_logits, localisations))
+    d_cls, d_obj, d_loc = out_grads
+    for i in range(len(logits)):
+        for name, t, like in (('d_logits', d_cls[i], logits[i]), ('d_objness_logits', d_obj[i], objness_logits[i]),
+                              ('d_localisations', d_loc[i], localisations[i])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == like.shape and t.is_contiguous(), \
+                '%s[%d] must be a contiguous float32 GPU tensor %s' % (name, i, tuple(like.shape))
+        hg.d_cls[i], hg.d_obj[i], hg.d_loc[i] = d_cls[i].data_ptr(), d_obj[i].data_ptr(), d_loc[i].data_ptr()
+    check(lib().ron_losses_grad(C.byref(heads), objp, C.byref(tg), n, ptr(rand_objness), ptr(rand_cls), C.byref(cfg), ptr(ws), nbytes,
+                                ptr(out), ptr(counts), C.byref(hg), current_stream()))
     del keep
-    return out, counts
+    return out, counts, d_cls, d_obj, d_loc
+
+
+def losses(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+           objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3):
+    """ron_losses over the whole batch (nets/ron_vgg_320.py:635-778): per-layer lists of GPU tensors [N,H,W,A,*]; rand_objness /
+    rand_cls: one float32 in [0, 1) per row, flattened (layer, image, row, column, anchor).  Returns (losses float32 [4]:
+    cross_entropy_pos, cross_entropy_objectness, localization, total; counts int32 [6]: LOSS_COUNTS), both on the GPU."""
+    return _losses_call(False, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                        objness_threshold, negative_ratio, alpha, beta)
+
+
+def losses_grad(logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                objness_threshold=0.03, negative_ratio=3., alpha=1. / 3, beta=1. / 3, out=None):
+    """ron_losses_grad: the arguments of `losses`; returns (losses [4], counts [6], d_logits, d_objness_logits, d_localisations).
+    The first two are bit for bit those of `losses`; the last three are per-layer lists of new float32 GPU tensors shaped like
+    `logits`, `objness_logits` and `localisations`: the gradient of the class term, the objectness term and the localisation term
+    with respect to its own head tensor (and, each term reading one tensor, of the total).  Every element is written by the call;
+    `out`, when given, is (d_logits, d_objness_logits, d_localisations) to write into instead of new tensors."""
+    return _losses_call(True, logits, localisations, objness_logits, objness_pred, gclasses, glocalisations, rand_objness, rand_cls,
+                        objness_threshold, negative_ratio, alpha, beta, out_grads=out)
 
 
 # --------------------------------------------------------------------------- #

@@ -84,6 +84,51 @@ static int run(int variant, int dtype, uint32_t flags, int max_batch, bool detec
   return 0;
 }
 
+// The argument handling of ron_losses / ron_losses_grad in the dry run (no launch): the per-layer tables filled for 1 .. RON_MAX_LAYERS
+// layers from pointers nobody dereferences, and every refusal the header promises as a status code.
+static int loss_arguments() {
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 20);          // fake device addresses, 16-byte aligned
+  int64_t* const g = reinterpret_cast<int64_t*>(uintptr_t(2) << 20);
+  const ron_loss_cfg cfg = {0.03f, 3.f, 1.f / 3, 1.f / 3};
+  for (int layers = 1; layers <= RON_MAX_LAYERS; ++layers) {
+    ron_heads h;
+    ron_targets t;
+    ron_head_grads d;
+    const float* objp[RON_MAX_LAYERS];
+    memset(&h, 0, sizeof h);
+    memset(&t, 0, sizeof t);
+    memset(&d, 0, sizeof d);
+    h.num_layers = layers;
+    h.num_classes = layers == 1 ? 2 : (layers == RON_MAX_LAYERS ? RON_MAX_CLASSES : 21);
+    for (int l = 0; l < layers; ++l) {
+      h.feat_h[l] = l + 1; h.feat_w[l] = 2 * l + 1; h.num_anchors[l] = l % RON_MAX_ANCHORS_PER_CELL + 1;
+      h.cls[l] = f; h.obj[l] = f; h.loc[l] = f; objp[l] = f;
+      t.gclasses[l] = g; t.glocalisations[l] = f;
+      d.d_cls[l] = f; d.d_obj[l] = f; d.d_loc[l] = f;
+    }
+    for (int n : {1, 2, 32}) {
+      const int64_t ws = ron_losses_grad_workspace_bytes(&h, n);
+      if (ws <= 0 || ws != ron_losses_workspace_bytes(&h, n)) return 1;
+      int32_t* counts = reinterpret_cast<int32_t*>(g);
+      CHECK(ron_losses(&h, objp, &t, n, f, f, &cfg, f, ws, f, counts, nullptr));
+      CHECK(ron_losses_grad(&h, objp, &t, n, f, f, &cfg, f, ws, f, counts, &d, nullptr));
+      // refusals: a short workspace, a missing gradient table, a missing and a misaligned gradient pointer, a bad batch
+      if (ron_losses_grad(&h, objp, &t, n, f, f, &cfg, f, ws - 1, f, counts, &d, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_losses_grad(&h, objp, &t, n, f, f, &cfg, f, ws, f, counts, nullptr, nullptr) != RON_ERR_INVALID) return 1;
+      ron_head_grads bad = d;
+      bad.d_obj[layers - 1] = nullptr;
+      if (ron_losses_grad(&h, objp, &t, n, f, f, &cfg, f, ws, f, counts, &bad, nullptr) != RON_ERR_INVALID) return 1;
+      bad = d;
+      bad.d_loc[layers - 1] = f + 1;
+      if (ron_losses_grad(&h, objp, &t, n, f, f, &cfg, f, ws, f, counts, &bad, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_losses_grad(&h, objp, &t, 0, f, f, &cfg, f, ws, f, counts, &d, nullptr) != RON_ERR_INVALID) return 1;
+    }
+    h.num_layers = RON_MAX_LAYERS + 1;
+    if (ron_losses_grad_workspace_bytes(&h, 1) != -1) return 1;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (getenv("RON_PLAN_ONLY") == nullptr) {
     fprintf(stderr, "plan_sweep: run with RON_PLAN_ONLY=1 (a dry run: this binary holds no device code)\n");
@@ -132,6 +177,10 @@ int main(int argc, char** argv) {
     if (run(RON_VARIANT_REDUCEDFC, RON_DTYPE_F32, 0u, 4, true)) return 1;
     if (run(RON_VARIANT_REDUCEDFC, RON_DTYPE_F16, RON_CFG_FUSE_POOLS | RON_CFG_NO_STEM2, 32, true)) return 1;
     runs += 2;
+  }
+  if (loss_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_losses / ron_losses_grad argument handling: %s\n", ron_last_error());
+    return 1;
   }
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
   return 0;
