@@ -381,6 +381,56 @@ int ron_losses_grad(const ron_heads* heads, const float* const* objness_pred, co
                     void* workspace, int64_t workspace_bytes,
                     float* losses, int32_t* counts, const ron_head_grads* grads, void* stream);
 
+/* SSDNet.losses of the two SSD networks -> ssd_losses (nets/ssd_vgg_300.py:580-659, one hard-negative selection over the whole batch;
+ * nets/ssd_vgg_512.py:516-607, one per feature layer) with custom_layers.abs_smooth (nets/custom_layers.py:51-63).  TensorFlow runs
+ * neither where this library is built; the semantics below are the contract, the choices made where TF raises are marked (*).
+ *   heads   : raw logits cls [N,H,W,A,C] and loc [N,H,W,A,4] (obj and anchor_* are not read)
+ *   targets : gclasses, glocalisations, gscores of ron_bboxes_encode (gbboxes is not read)
+ * Rows are flattened as in ron_losses (layer, image, row, column, anchor).  A segment is the whole batch (S = 1, BATCH) or one layer
+ * (S = num_layers, LAYER); R is its row count, N the batch size.  Per row, with logits x, score s and class g:
+ *   pos = s > match_threshold; cand = !pos && s > -0.5f; p0 = expf(x[0] - max) / sum (the sum in index order); v = cand ? p0 : 1.0f
+ * Per segment, n_pos and n_cand counted as integers:
+ *   BATCH  k = min((int)(negative_ratio * (float)n_pos) + N, n_cand)              (:630-632; the cast truncates)
+ *   LAYER  k = min(max((int)(negative_ratio * (float)n_pos), R / 8, 4 * N), 1 + n_cand)   (:563-567)
+ *   k = min(k, R) (*: top_k raises beyond R); t = the k-th smallest v over all R rows; mined = cand && v < t, strictly, so the k-th
+ *   row and its ties are not mined; k == 0 (*: val[-1] raises) mines nothing
+ * Terms: ce = sparse softmax cross-entropy (a label < 0 counts as 0, a label >= C gives NaN), sl1(d) = 0.5f*((|d|-1)*min(|d|,1)+|d|)
+ *   BATCH  losses[0] = sum_pos ce(x, g) / N, losses[1] = sum_mined ce(x, 0) / N, losses[2] = alpha * (sum_pos sum_4 sl1(loc - gloc) / N)
+ *   LAYER  per layer sum_pos ce / n_pos, sum_mined ce / n_mined, alpha * (sum_pos sum_4 sl1 / (4 n_pos)) (tf.losses.
+ *          compute_weighted_loss: the sum by the number of non-zero weights), each 0 where its divisor is 0 and the last 0 when
+ *          alpha == 0; the layers added in order
+ *   losses[3] = (losses[0] + losses[1]) + losses[2]
+ *   counts [4 * S] : per segment n_pos, n_cand, k, n_mined (device, int32)
+ *   nvalues [rows] or NULL : every row's v
+ * Deterministic: integer atomics only, float sums through per-workgroup double partials added in a fixed order; two calls give the
+ * same bytes.  Non-finite logits give unspecified selections; the call stays memory safe and terminates.  loc / glocalisations rows
+ * move as 16-byte accesses: the layer pointers must be aligned accordingly.
+ * workspace: ron_ssd_losses_workspace_bytes(heads, n) bytes of device scratch, 16-byte aligned. */
+enum { RON_SSD_MINING_BATCH = 0,   /* ssd_vgg_300.ssd_losses: one selection over the whole batch   */
+       RON_SSD_MINING_LAYER = 1 }; /* ssd_vgg_512.ssd_losses: one selection per feature layer      */
+typedef struct {
+  int mining;
+  float match_threshold;    /* 0.5 */
+  float negative_ratio;     /* 3   */
+  float alpha;              /* 1: weight of the localisation term */
+} ron_ssd_loss_cfg;
+int64_t ron_ssd_losses_workspace_bytes(const ron_heads* heads, int n);
+int ron_ssd_losses(const ron_heads* heads, const ron_targets* targets, int n, const ron_ssd_loss_cfg* cfg,
+                   void* workspace, int64_t workspace_bytes, float* losses, int32_t* counts, float* nvalues, void* stream);
+
+/* ron_ssd_losses and, in the same call, d losses[0] + losses[1] / d cls and d losses[2] / d loc (grads->d_obj is not read).  t is a
+ * constant with respect to the logits, as top_k's comparison is in TF.
+ *   a pos row   : d_cls = (softmax(x) - onehot(g)) * s_pos (a label >= C: a NaN row), d_loc = clamp(loc - gloc, -1, 1) * s_loc
+ *   a mined row : d_cls = (softmax(x) - onehot(0)) * s_neg
+ *   s_pos, s_neg, s_loc : BATCH 1 / N, 1 / N, alpha / N; LAYER 1 / n_pos, 1 / n_mined, alpha / (4 n_pos), 0 where the term is 0
+ * Every element of d_cls and d_loc is written (rows in no set: +0).  `losses` and `counts` are bit for bit those of ron_ssd_losses
+ * (the same kernels run).  d_loc rows move as 16-byte accesses.
+ * workspace: ron_ssd_losses_grad_workspace_bytes(heads, n) bytes of device scratch, 16-byte aligned. */
+int64_t ron_ssd_losses_grad_workspace_bytes(const ron_heads* heads, int n);
+int ron_ssd_losses_grad(const ron_heads* heads, const ron_targets* targets, int n, const ron_ssd_loss_cfg* cfg,
+                        void* workspace, int64_t workspace_bytes, float* losses, int32_t* counts, float* nvalues,
+                        const ron_head_grads* grads, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Training preprocessing: ron_preprocess_for_train (preprocessing/ssd_vgg_preprocessing.py:297-356), the chain
  * preprocess_image(is_training=True) runs in front of RONNet.bboxes_encode (ron_net.py:249-306).  Its colour distortion is

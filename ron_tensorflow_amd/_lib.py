@@ -20,6 +20,9 @@ RON_MAX_GT = 256
 RON_TRAIN_DRAWS = 5 + 10 * 10 * 12
 RON_TRAIN_GEOM = 12
 
+RON_SSD_MINING_BATCH = 0
+RON_SSD_MINING_LAYER = 1
+
 RON_IN_CLS_IS_PROB = 1
 RON_IN_OBJ_IS_PROB = 2
 RON_IN_LOC_DECODED = 4
@@ -84,6 +87,10 @@ class LossCfg(C.Structure):
     _fields_ = [('objness_threshold', C.c_float), ('negative_ratio', C.c_float), ('alpha', C.c_float), ('beta', C.c_float)]
 
 
+class SsdLossCfg(C.Structure):
+    _fields_ = [('mining', C.c_int), ('match_threshold', C.c_float), ('negative_ratio', C.c_float), ('alpha', C.c_float)]
+
+
 class Detections(C.Structure):
     _fields_ = [('capacity', C.c_int32), ('classes', C.c_void_p), ('scores', C.c_void_p), ('bboxes', C.c_void_p),
                 ('anchor_index', C.c_void_p), ('count', C.c_void_p)]
@@ -143,6 +150,11 @@ SIGNATURES = {
     'ron_losses_grad_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
     'ron_losses_grad': (C.c_int, [C.POINTER(Heads), C.POINTER(_P), C.POINTER(Targets), C.c_int, _P, _P, C.POINTER(LossCfg), _P,
                                   C.c_int64, _P, _P, C.POINTER(HeadGrads), _P]),
+    'ron_ssd_losses_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
+    'ron_ssd_losses': (C.c_int, [C.POINTER(Heads), C.POINTER(Targets), C.c_int, C.POINTER(SsdLossCfg), _P, C.c_int64, _P, _P, _P, _P]),
+    'ron_ssd_losses_grad_workspace_bytes': (C.c_int64, [C.POINTER(Heads), C.c_int]),
+    'ron_ssd_losses_grad': (C.c_int, [C.POINTER(Heads), C.POINTER(Targets), C.c_int, C.POINTER(SsdLossCfg), _P, C.c_int64, _P, _P, _P,
+                                      C.POINTER(HeadGrads), _P]),
     'ron_post_tfe': (C.c_int, [C.POINTER(Heads), C.c_int, C.POINTER(TfeCfg), _P, C.c_int64, _P, _P, _P]),
     'ron_create': (C.c_int, [C.POINTER(_P), C.POINTER(Config)]),
     'ron_destroy': (C.c_int, [_P]),

@@ -3,8 +3,9 @@
 ``SSDNet`` keeps names / defaults / return arity of the reference class (nets/ssd_vgg_300.py:82-245): ``net`` returns
 ``(predictions, localisations, logits, end_points)``.  It is ``ssd_vgg_512.SSDNet`` with other parameters and the context
 variant RON_VARIANT_SSD300: ``update_feature_shapes``, ``anchors``, ``bboxes_decode``, ``detected_bboxes``, ``detect``,
-``detect_tfe``, ``load_weights``, ``load_checkpoint`` and ``clone`` are inherited.  The maps are 300 -> 150 -> 75 -> 38 -> 19
-(SAME 2x2 pools: ceil) -> 10 -> 5 (pad 1 + 3x3 stride 2) -> 3 -> 1 (3x3 VALID): 8732 anchors."""
+``detect_tfe``, ``bboxes_encode``, ``losses``, ``losses_and_gradients``, ``validation_losses``, ``load_weights``,
+``load_checkpoint`` and ``clone`` are inherited.  The maps are 300 -> 150 -> 75 -> 38 -> 19 (SAME 2x2 pools: ceil) -> 10 -> 5
+(pad 1 + 3x3 stride 2) -> 3 -> 1 (3x3 VALID): 8732 anchors."""
 from . import ron_vgg_320, ssd_vgg_512
 from .ssd_vgg_512 import SSDParams
 
@@ -27,6 +28,7 @@ class SSDNet(ssd_vgg_512.SSDNet):
         normalizations=[20, -1, -1, -1, -1, -1],
         prior_scaling=[0.1, 0.1, 0.2, 0.2])
     _variant = 'ssd300'
+    _mining = 'batch'          # nets/ssd_vgg_300.py:580-659: one hard-negative selection over the whole batch
 
     def __init__(self, params=None, dtype='bf16', max_batch=32, device=None, fuse_pools=False):
         ssd_vgg_512.SSDNet.__init__(self, params, dtype=dtype, max_batch=max_batch, device=device, fuse_pools=fuse_pools)
@@ -51,6 +53,14 @@ def ssd_net(inputs, num_classes=SSDNet.default_params.num_classes, feat_layers=S
 
 
 ssd_net.default_image_size = 300
+
+
+def ssd_losses(logits, localisations, gclasses, glocalisations, gscores, match_threshold=0.5, negative_ratio=3., alpha=1.,
+               label_smoothing=0., device='/cpu:0', scope=None):
+    """Loss functions of the SSD-300 network (nets/ssd_vgg_300.py:580-659): one hard-negative selection over the whole batch.
+    `device` is accepted and unused; the terms are returned, as SSDNet.losses returns them."""
+    return ssd_vgg_512._ssd_losses_fn('batch', logits, localisations, gclasses, glocalisations, gscores, match_threshold,
+                                      negative_ratio, alpha)
 
 
 def ssd_arg_scope(weight_decay=0.0005, data_format='NHWC'):

@@ -21,6 +21,39 @@ SSDParams = namedtuple('SSDParameters', ['img_shape', 'num_classes', 'no_annotat
                                          'anchor_offset', 'normalizations', 'prior_scaling'])
 
 
+_LOSS_KEYS = ('cross_entropy_pos', 'cross_entropy_neg', 'localization', 'total')
+_NO_BORDER = 1 << 24       # allowed border of ron_bboxes_encode under which the inside test never fails for a finite anchor
+
+
+class _SSDLossesFunction(torch.autograd.Function):
+    """SSDNet.losses for head tensors that require grad.  forward: one ron_ssd_losses_grad call, the unit gradients saved; backward:
+    the localisation gradient times (upstream of its term + upstream of the total), and the class gradient, whose rows belong to
+    the positive or to the mined set, times the upstream of that row's term + the upstream of the total: torch multiplies on the
+    device.  The inputs are (number of layers, (gclasses, glocalisations, gscores), loss keyword arguments, then the logits and
+    localisations of every layer); the outputs the four losses as one tensor [4] and the counts."""
+
+    @staticmethod
+    def forward(ctx, num_layers, fixed, kwargs, *heads):
+        logits, localisations = list(heads[:num_layers]), list(heads[num_layers:])
+        gclasses, glocalisations, gscores = fixed
+        out, counts, _, d_cls, d_loc = ops.ssd_losses_grad(logits, localisations, gclasses, glocalisations, gscores, **kwargs)
+        ctx.save_for_backward(*(d_cls + d_loc + list(gscores)))
+        ctx.num_layers, ctx.match_threshold = num_layers, float(kwargs['match_threshold'])
+        ctx.mark_non_differentiable(counts)
+        return out, counts
+
+    @staticmethod
+    def backward(ctx, g, _g_counts):
+        n = ctx.num_layers
+        saved = ctx.saved_tensors
+        d_cls, d_loc, gscores = saved[:n], saved[n:2 * n], saved[2 * n:]
+        s_pos, s_neg, s_loc = g[0] + g[3], g[1] + g[3], g[2] + g[3]              # 0-d tensors on the device
+        grads = [d * torch.where(sc > ctx.match_threshold, s_pos, s_neg).unsqueeze(-1) if ctx.needs_input_grad[3 + i] else None
+                 for i, (d, sc) in enumerate(zip(d_cls, gscores))]
+        grads += [d * s_loc if ctx.needs_input_grad[3 + n + i] else None for i, d in enumerate(d_loc)]
+        return (None, None, None) + tuple(grads)
+
+
 class SSDNet(RONNet):
     """SSD VGG-based 512 network: conv4 64x64, conv7 32x32, conv8 16x16, conv9 8x8, conv10 4x4, conv11 2x2, conv12 1x1."""
     default_params = SSDParams(
@@ -39,6 +72,7 @@ class SSDNet(RONNet):
         prior_scaling=[0.1, 0.1, 0.2, 0.2])
 
     _variant = 'ssd512'        # _lib.VARIANTS key of the context this class builds (ssd_vgg_300.SSDNet: 'ssd300')
+    _mining = 'layer'          # ssd_losses selects its hard negatives per feature layer here, over the batch in ssd_vgg_300
 
     def __init__(self, params=None, dtype='bf16', max_batch=16, device=None, fuse_pools=False):
         self.params = params if isinstance(params, SSDParams) else type(self).default_params
@@ -117,6 +151,64 @@ class SSDNet(RONNet):
                                    select_threshold=select_threshold, nms_threshold=nms_threshold, clipping_bbox=None,
                                    top_k=top_k, keep_top_k=keep_top_k, nms_mode=nms_mode, min_size=None)
 
+    # ------------------------------------------------------------------ label side (gradients stop at the head tensors)
+    def bboxes_encode(self, labels, bboxes, anchors, scope=None):
+        """Ground truth -> per-anchor targets (nets/ssd_vgg_512.py:161-171, nets/ssd_vgg_300.py:191-201) on the GPU.  The reference's
+        own call hands five arguments to the eight-argument ssd_common.tf_ssd_bboxes_encode and cannot run; its evident intent is
+        the contract: a match at an overlap of 0.5 or more, no ignore band, no border restriction.  One image, labels [G] and bboxes
+        [G, 4] (outputs without a batch axis), or a padded batch [N, G] / [N, G, 4] with label 0 as padding behind the present rows,
+        as in RONNet.bboxes_encode; returns its four per-layer lists."""
+        glabels, gbboxes, single = self._ground_truth(labels, bboxes)
+        adev = ops.anchors_to_device(anchors, self.device)
+        shapes = [(int(np.shape(y)[0]), int(np.shape(y)[1]), int(np.size(h))) for (y, x, h, w) in anchors]
+        out = ops.bboxes_encode(glabels, gbboxes, adev, shapes, self.params.img_shape, [_NO_BORDER] * len(shapes), 0.5, 0.5,
+                                tuple(self.params.prior_scaling))
+        return tuple([t[0] for t in lst] for lst in out) if single else out
+
+    def losses(self, logits, localisations, gclasses, glocalisations, gscores, match_threshold=0.5, negative_ratio=3., alpha=1.,
+               label_smoothing=0., scope='ssd_losses'):
+        """The SSD losses (nets/ssd_vgg_512.py:203-218 -> ssd_losses, :516-607: hard negatives per feature layer; ssd_vgg_300.SSDNet
+        -> nets/ssd_vgg_300.py:580-659: over the whole batch) of a batch, one ron_ssd_losses call.  `label_smoothing` is accepted
+        and unused, as in the reference.  Returns 0-d GPU tensors {'cross_entropy_pos', 'cross_entropy_neg', 'localization',
+        'total'} and 'counts' (int32 [S, 4], ops.SSD_LOSS_COUNTS per segment: S = 1 over the batch, the number of layers else).
+        When autograd is enabled and a tensor of `logits` or `localisations` requires grad, the four scalars are differentiable with
+        respect to those tensors (ron_ssd_losses_grad, one call; the same values bit for bit); the mining threshold is a constant."""
+        kwargs = dict(mining=self._mining, match_threshold=match_threshold, negative_ratio=negative_ratio, alpha=alpha)
+        heads = list(logits) + list(localisations)
+        if torch.is_grad_enabled() and any(t.requires_grad for t in heads):
+            out, counts = _SSDLossesFunction.apply(len(logits), (gclasses, glocalisations, gscores), kwargs, *heads)
+        else:
+            out, counts, _ = ops.ssd_losses(logits, localisations, gclasses, glocalisations, gscores, **kwargs)
+        res = {k: out[i] for i, k in enumerate(_LOSS_KEYS)}
+        res['counts'] = counts
+        return res
+
+    def losses_and_gradients(self, logits, localisations, gclasses, glocalisations, gscores, match_threshold=0.5, negative_ratio=3.,
+                             alpha=1., label_smoothing=0., scope='ssd_losses'):
+        """`losses` and, from the same call (ron_ssd_losses_grad), 'gradients': {'logits', 'localisations'}: per-layer lists of
+        float32 GPU tensors shaped like the inputs, d (cross_entropy_pos + cross_entropy_neg) / d logits and d localization /
+        d localisations; each term reads one head tensor, so these are also the gradients of 'total'.  The loss values are those of
+        `losses` bit for bit."""
+        with torch.no_grad():
+            out, counts, _, d_cls, d_loc = ops.ssd_losses_grad(logits, localisations, gclasses, glocalisations, gscores,
+                                                               mining=self._mining, match_threshold=match_threshold,
+                                                               negative_ratio=negative_ratio, alpha=alpha)
+        res = {k: out[i] for i, k in enumerate(_LOSS_KEYS)}
+        res.update(counts=counts, gradients={'logits': d_cls, 'localisations': d_loc})
+        return res
+
+    def validation_losses(self, images, glabels, gbboxes, **loss_kwargs):
+        """Held-out loss of a labelled batch: net() -> bboxes_encode (on the network's own anchors) -> losses, all on the device;
+        no host copy in between.  glabels [N, G] (0 = padding), gbboxes [N, G, 4]; loss_kwargs go to `losses`."""
+        _, localisations, logits, _ = self.net(images, is_training=False, update_feat_shapes=False, end_points=())
+        glabels, gbboxes, _ = self._ground_truth(glabels, gbboxes)
+        hd = _lib.Heads()
+        check(lib().ron_heads_describe(self._context(), C.byref(hd)))
+        gclasses, glocalisations, gscores, _ = ops.bboxes_encode(
+            glabels, gbboxes, None, None, self.params.img_shape, [_NO_BORDER] * int(hd.num_layers), 0.5, 0.5,
+            tuple(self.params.prior_scaling), heads=hd)
+        return self.losses(logits, localisations, gclasses, glocalisations, gscores, **loss_kwargs)
+
     def detect(self, inputs, select_threshold=0.01, nms_threshold=0.45, top_k=400, bbox_img=(0., 0., 1., 1.), out=None):
         """forward + np_methods post-processing (no objectness gate for SSD)."""
         return RONNet.detect(self, inputs, objectness_thres=0.0, select_threshold=select_threshold,
@@ -156,6 +248,20 @@ def ssd_net(inputs, num_classes=SSDNet.default_params.num_classes, feat_layers=S
 
 
 ssd_net.default_image_size = 512
+
+
+def _ssd_losses_fn(mining, logits, localisations, gclasses, glocalisations, gscores, match_threshold, negative_ratio, alpha):
+    net = SSDNet.__new__(SSDNet)                       # losses() reads nothing of the object but the mining mode
+    net._mining = mining
+    return net.losses(logits, localisations, gclasses, glocalisations, gscores, match_threshold=match_threshold,
+                      negative_ratio=negative_ratio, alpha=alpha)
+
+
+def ssd_losses(logits, localisations, gclasses, glocalisations, gscores, match_threshold=0.5, negative_ratio=3., alpha=1.,
+               label_smoothing=0., scope=None):
+    """Loss functions of the SSD-512 network (nets/ssd_vgg_512.py:516-607): hard negatives per feature layer.  The reference adds
+    its terms to TF collections; here they are returned, as SSDNet.losses returns them."""
+    return _ssd_losses_fn('layer', logits, localisations, gclasses, glocalisations, gscores, match_threshold, negative_ratio, alpha)
 
 
 def ssd_arg_scope(weight_decay=0.0005, data_format='NHWC'):

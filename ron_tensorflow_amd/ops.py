@@ -354,6 +354,81 @@ def losses_grad(logits, localisations, objness_logits, objness_pred, gclasses, g
                         objness_threshold, negative_ratio, alpha, beta, out_grads=out)
 
 
+SSD_LOSS_COUNTS = ('n_pos', 'n_cand', 'k', 'n_mined')
+SSD_MINING = {'batch': _lib.RON_SSD_MINING_BATCH, 'layer': _lib.RON_SSD_MINING_LAYER}
+
+
+def _ssd_losses_call(grad, logits, localisations, gclasses, glocalisations, gscores, mining, match_threshold, negative_ratio, alpha,
+                     want_nvalues, out_grads=None):
+    """ron_ssd_losses (grad False) or ron_ssd_losses_grad (grad True) on checked arguments."""
+    if mining not in SSD_MINING:
+        raise ValueError("mining must be 'batch' or 'layer', not %r" % (mining,))
+    n = logits[0].shape[0]
+    dev = logits[0].device
+    heads, keep = _fill_heads(logits, None, localisations, None, int(logits[0].shape[-1]))
+    tg = _lib.Targets()
+    rows = 0
+    for i in range(len(logits)):
+        shp = tuple(logits[i].shape[:4])
+        for name, t, want, dt in (('localisations', localisations[i], shp + (4,), torch.float32),
+                                  ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
+                                  ('gscores', gscores[i], shp, torch.float32),
+                                  ('gclasses', gclasses[i], shp, torch.int64)):
+            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == want, '%s[%d] must be a %s GPU tensor %s' % (name, i, dt, want)
+        tensors = [gclasses[i].contiguous(), glocalisations[i].contiguous(), gscores[i].contiguous()]
+        keep.append(tensors)
+        tg.gclasses[i], tg.glocalisations[i], tg.gscores[i] = (t.data_ptr() for t in tensors)
+        rows += gclasses[i].numel()
+    cfg = _lib.SsdLossCfg(SSD_MINING[mining], float(match_threshold), float(negative_ratio), float(alpha))
+    nbytes = (lib().ron_ssd_losses_grad_workspace_bytes if grad else lib().ron_ssd_losses_workspace_bytes)(C.byref(heads), n)
+    if nbytes < 0:
+        check(-1)
+    ws = _workspace(dev, nbytes)
+    segs = 1 if mining == 'batch' else len(logits)
+    out = torch.empty((4,), dtype=torch.float32, device=dev)
+    counts = torch.empty((segs, 4), dtype=torch.int32, device=dev)
+    nvalues = torch.empty((rows,), dtype=torch.float32, device=dev) if want_nvalues else None
+    if not grad:
+        check(lib().ron_ssd_losses(C.byref(heads), C.byref(tg), n, C.byref(cfg), ptr(ws), nbytes, ptr(out), ptr(counts), ptr(nvalues),
+                                   current_stream()))
+        del keep
+        return out, counts, nvalues
+    hg = _lib.HeadGrads()
+    if out_grads is None:
+        out_grads = tuple([torch.empty(t.shape, dtype=torch.float32, device=dev) for t in lst] for lst in (logits, localisations))
+    d_cls, d_loc = out_grads
+    for i in range(len(logits)):
+        for name, t, like in (('d_logits', d_cls[i], logits[i]), ('d_localisations', d_loc[i], localisations[i])):
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == like.shape and t.is_contiguous(), \
+                '%s[%d] must be a contiguous float32 GPU tensor %s' % (name, i, tuple(like.shape))
+        hg.d_cls[i], hg.d_loc[i] = d_cls[i].data_ptr(), d_loc[i].data_ptr()
+    check(lib().ron_ssd_losses_grad(C.byref(heads), C.byref(tg), n, C.byref(cfg), ptr(ws), nbytes, ptr(out), ptr(counts), ptr(nvalues),
+                                    C.byref(hg), current_stream()))
+    del keep
+    return out, counts, nvalues, d_cls, d_loc
+
+
+def ssd_losses(logits, localisations, gclasses, glocalisations, gscores, mining='batch', match_threshold=0.5, negative_ratio=3.,
+               alpha=1., nvalues=False):
+    """ron_ssd_losses (nets/ssd_vgg_300.py:580-659 with mining 'batch', nets/ssd_vgg_512.py:516-607 with 'layer'): per-layer lists of
+    GPU tensors [N,H,W,A,*].  Returns (losses float32 [4]: cross_entropy_pos, cross_entropy_neg, localization, total; counts int32
+    [S, 4]: SSD_LOSS_COUNTS per segment, S = 1 or the number of layers; nvalues), all on the GPU; `nvalues` is None unless asked
+    for: float32 [rows], every row's mining value (its background probability when it is a candidate, else 1)."""
+    return _ssd_losses_call(False, logits, localisations, gclasses, glocalisations, gscores, mining, match_threshold, negative_ratio,
+                            alpha, nvalues)
+
+
+def ssd_losses_grad(logits, localisations, gclasses, glocalisations, gscores, mining='batch', match_threshold=0.5, negative_ratio=3.,
+                    alpha=1., nvalues=False, out=None):
+    """ron_ssd_losses_grad: the arguments of `ssd_losses`; returns (losses [4], counts [S, 4], nvalues, d_logits, d_localisations).
+    The first three are bit for bit those of `ssd_losses`; the last two are per-layer lists of new float32 GPU tensors shaped like
+    `logits` and `localisations`: the gradient of the two cross-entropy terms and of the localisation term (and, each reading one
+    tensor, of the total).  Every element is written by the call; `out`, when given, is (d_logits, d_localisations) to write
+    into instead of new tensors."""
+    return _ssd_losses_call(True, logits, localisations, gclasses, glocalisations, gscores, mining, match_threshold, negative_ratio,
+                            alpha, nvalues, out_grads=out)
+
+
 # --------------------------------------------------------------------------- #
 # single operators (parity tests of the conv kernels)
 # --------------------------------------------------------------------------- #
