@@ -24,7 +24,14 @@ hipError_t dev_malloc(void** p, size_t bytes) {
   return hipSuccess;
 }
 hipError_t dev_free(void* p) { return plan_only() ? hipSuccess : hipFree(p); }
-hipError_t dev_memset(void* p, int v, size_t bytes) { return plan_only() ? hipSuccess : hipMemset(p, v, bytes); }
+// hipMemset on device memory only ENQUEUES on the null stream (measured: with the null stream busy it returns at once, the memory
+// still unset; tests/test_gpu_stream_order.py).  Callers of this one zero memory at set-up and hand it to streams that do not wait
+// for the null stream (ron_clone: a slot used at once on a non-blocking stream), so it returns when the memory is zero.
+hipError_t dev_memset(void* p, int v, size_t bytes) {
+  if (plan_only()) return hipSuccess;
+  const hipError_t e = hipMemset(p, v, bytes);
+  return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
+}
 hipError_t dev_memset_async(void* p, int v, size_t bytes, hipStream_t s) { return plan_only() ? hipSuccess : hipMemsetAsync(p, v, bytes, s); }
 hipError_t dev_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   return plan_only() ? hipSuccess : hipMemcpy(dst, src, bytes, kind);

@@ -42,7 +42,7 @@ static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * 
 bool plan_only();
 hipError_t dev_malloc(void** p, size_t bytes);
 hipError_t dev_free(void* p);
-hipError_t dev_memset(void* p, int v, size_t bytes);
+hipError_t dev_memset(void* p, int v, size_t bytes);                              // complete when it returns (waits for the null stream)
 hipError_t dev_memset_async(void* p, int v, size_t bytes, hipStream_t s);
 hipError_t dev_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind);
 hipError_t dev_set_device(int device);

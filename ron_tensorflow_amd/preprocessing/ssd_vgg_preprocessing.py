@@ -79,7 +79,9 @@ def _pack(arrs, dev):
 def preprocess_for_eval_batch(images, out_shape=EVAL_SIZE, resize=Resize.WARP_RESIZE, device='cuda:0',
                               means=(_R_MEAN, _G_MEAN, _B_MEAN)):
     """List of HWC uint8 images (numpy or torch, any sizes) -> float32 GPU tensor [N, out_h, out_w, 3]: one packed
-    upload, one launch.  All four modes of the reference (Resize.NONE needs equally sized images)."""
+    upload, one launch.  All four modes of the reference (Resize.NONE needs equally sized images).  The upload comes from pageable host
+    memory and holds the host until what is queued on the current stream has finished; the launch itself (ron_preprocess_eval_geom)
+    does not synchronise."""
     if resize not in (Resize.WARP_RESIZE, Resize.NONE, Resize.CENTRAL_CROP, Resize.PAD_AND_RESIZE):
         raise ValueError('unknown resize mode %r' % (resize,))
     dev = torch.device(device)
@@ -151,7 +153,9 @@ def ron_preprocess_for_train_batch(images, glabels, gbboxes, out_shape=EVAL_SIZE
     (glabels [N, G], 0 = padding; gbboxes [N, G, 4]) -> GPU tensors
         images [N, out_h, out_w, 3] float32, glabels int32 [N, G], gbboxes float32 [N, G, 4], counts int32 [N], geom int32 [N, 12]
     with the kept rows at the front (what RONNet.bboxes_encode / validation_losses take).  One packed upload, three launches
-    (geometry, channel sums of the expanded images, pixels), no synchronisation.  The random decisions are `draws`
+    (geometry, channel sums of the expanded images, pixels), no read-back; the uploads of host arrays (images, and ground truth / draws
+    when given as numpy) come from pageable memory and hold the host until what is queued on the current stream has finished, the
+    launches themselves do not synchronise.  The random decisions are `draws`
     ([N, RON_TRAIN_DRAWS] uniform floats in [0, 1), slot layout in include/ron_hip.h); drawn with torch.rand from `generator`
     (a generator of the target device) when not given."""
     dev = torch.device(device)

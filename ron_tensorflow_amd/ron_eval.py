@@ -34,7 +34,8 @@ def post_eval(cls, obj, loc, anchors_dev, image_shapes, num_classes=21, objectne
     only suppresses boxes of its own label.  'scores' = ``tf_bboxes_nms_by_class`` (ron_eval.py:212-280, the function the commented call
     of :474 names): every score column (objectness x class probability, background included) runs its own greedy NMS with at most
     ``keep_top_k`` picks; a row some column kept comes back with the largest of its kept scores and that column as its class, rows in
-    the flattened ANCHOR order, up to num_classes * keep_top_k of them (the buffers get that capacity)."""
+    the flattened ANCHOR order, up to num_classes * keep_top_k of them (the buffers get that capacity).
+    Enqueues on torch's current stream and does not synchronise with the host."""
     if nms_by_class not in (False, True, 'v1', 'scores'):
         raise ValueError("nms_by_class must be False, True / 'v1' or 'scores'")
     per_column = nms_by_class == 'scores'
@@ -50,7 +51,9 @@ def post_eval(cls, obj, loc, anchors_dev, image_shapes, num_classes=21, objectne
         cfg.prior_scaling[i] = prior_scaling[i]
     cfg.input_flags = ((_lib.RON_IN_CLS_IS_PROB if cls_is_prob else 0) | (_lib.RON_IN_OBJ_IS_PROB if obj_is_prob else 0) |
                        (_lib.RON_IN_LOC_DECODED if loc_decoded else 0))
-    ms = torch.from_numpy(filter_min_size(image_shapes, net_input_shape, min_size_ratio)).to(dev)
+    # the per-image minimum sizes go up from pinned memory on the current stream, without holding the host (a pageable upload would
+    # wait for everything queued on the stream): like ron_post_eval itself, this call only enqueues
+    ms = torch.from_numpy(filter_min_size(image_shapes, net_input_shape, min_size_ratio)).pin_memory().to(dev, non_blocking=True)
     assert ms.shape[0] == n, 'one (height, width) per image'
     nbytes = lib().ron_post_eval_workspace_bytes_mode(C.byref(heads), n, cfg.nms_mode)
     if nbytes < 0:
