@@ -631,6 +631,39 @@ int ron_conv_num_tile_cfgs(void);
  * runtime's occupancy query answers for the launch's block and LDS size.  ron_forward requires 2 and fails otherwise. */
 int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
 
+/* ------------------------------------------------------------------------------------------
+ * Convolution backward: the gradients of ONE stride-1 SAME convolution (every VGG body layer, fc6 / fc7, conv6 / conv7,
+ * the stride-1 convolutions of the SSD extra blocks, every head).  Unlike the test operators above this is a real entry
+ * point: it enqueues on `stream`, allocates nothing, never synchronises, honours the dry-run mode, and assumes nothing
+ * about the workspace's contents (every halo and guard zero it relies on is written by the call).
+ *
+ * Operands are rounded to d->dtype (bf16 or fp16) and accumulated in fp32, like the forward:
+ *   dz    = round(dy * (y > 0)) when d->relu (TF's ReluGrad: no gradient where y == 0), else round(dy)
+ *   dx    = round(conv_SAME(dz, w')), w'[ky,kx,co,ci] = round(w)[kh-1-ky, kw-1-kx, ci, co], same dilation; delivered as
+ *           storage-type values in fp32, as ron_conv2d_nhwc delivers y
+ *   dw[ky,kx,ci,co] = sum over n, y, x of round(x)[n, y + ky*dil - pad, x + kx*dil - pad, ci] * dz[n,y,x,co]: an fp32 sum,
+ *           not rounded further; terms outside the map are zero
+ *   dbias[co] = sum of dz[..., co]: the rounded dz, in fp32
+ * The sums run in a fixed order: the same inputs give the same bytes on every call.
+ *
+ * All pointers are DEVICE fp32, w included (weights live on the device in training): x [n,h,w,cin], w and dw HWIO
+ * [kh,kw,cin,cout], y and dy [n,h,w,cout], dx [n,h,w,cin], dbias [cout].  y is read only when d->relu.  dx, dw, dbias may
+ * each be NULL (not computed); every element of a non-NULL output is written.  x may be NULL when dw is, w when dx is.
+ * x, y and dy must be 16-byte aligned (they are read 16 bytes at a time), the workspace 256-byte aligned.
+ *
+ * Accepted descriptors: stride 1, kh == kw in {1, 3}, dilation >= 1, dtype bf16 / fp16, cin a multiple of 64, any
+ * cout >= 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1.  d->splitk is the pixel-split
+ * factor of the weight gradient: -1 = by shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the
+ * fp32 partial sums of the slices would reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned pointer and a
+ * workspace that is too small included - is RON_ERR_INVALID with a message, before any HIP call.
+ * Out of scope: the 3-channel stem, strided and transposed convolutions, pools, fp32 and f16x3 arithmetic.
+ * ron_conv2d_backward_workspace_bytes is host arithmetic only (it depends on d->splitk too); -1 + ron_last_error() on a
+ * descriptor the call would refuse.
+ * ---------------------------------------------------------------------------------------- */
+int64_t ron_conv2d_backward_workspace_bytes(const ron_conv_desc* d);
+int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
+                             float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

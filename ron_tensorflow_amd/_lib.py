@@ -184,6 +184,8 @@ SIGNATURES = {
     'ron_conv2d_bench': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(C.c_float)]),
     'ron_conv_num_tile_cfgs': (C.c_int, []),
     'ron_stem2_workgroups_per_cu': (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
+    'ron_conv2d_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
+    'ron_conv2d_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

@@ -113,6 +113,27 @@ constexpr int kGroupMixed = 64;
 size_t dtype_size(int dtype);
 inline bool dtype_is_half(int dtype) { return dtype == RON_DTYPE_BF16 || dtype == RON_DTYPE_F16; }   // 2-byte elements
 
+// Weight gradient of a stride-1 SAME convolution (conv_wgrad.hip): dw[ky,kx,ci,co] = sum over pixels of x[pixel + tap] * dz[pixel], fp32,
+// not rounded.  x and dz are whole halo tensors of `dtype` (bf16 / f16) in ONE geometry (same N, H, W, pad = (kh - 1) * dil / 2,
+// channels padded to 64: x.C = cin, dz.C >= Cout with zero pad channels).  The kernel walks the flat halo-pixel index without a bounds
+// test, so the caller guarantees: dz's halo is zero; both tensors are zero from pixels() up to the next multiple of 32; x has `guard`
+// >= pad * Wp + pad pixels of finite data (zeros) in front of base and behind its last padded pixel.  ron_conv2d_backward_nhwc packs
+// its fp32 operands that way; a network-level backward calls this on its own halo tensors without the fp32 boundary conversions.
+struct WgradLaunch {
+  int dtype = RON_DTYPE_BF16;
+  TensorView x, dz;              // base = halo pixel 0
+  int kh = 1, kw = 1, dil = 1;
+  int Cout = 0;                  // columns of dw that are stored (<= dz.C)
+  int64_t guard = 0;             // readable pixels of x on either side (see above)
+  float* dw = nullptr;           // [kh,kw,cin,Cout] HWIO fp32: every element written
+  int splitk = -1;               // pixel slices: -1 = by shape, 1 = off, S = forced (never more than there are 32-pixel steps, or than keeps the slabs below 2 GiB)
+  void* scratch = nullptr;       // fp32 slabs of the slices (conv_wgrad_scratch_bytes), summed in slice order: bitwise reproducible
+  int64_t scratch_bytes = 0;
+};
+int launch_conv_wgrad(const WgradLaunch& c, hipStream_t stream);
+int conv_wgrad_slices(const WgradLaunch& c);                 // the pixel slices launch_conv_wgrad would use (-1: `c` is refused)
+int64_t conv_wgrad_scratch_bytes(const WgradLaunch& c);      // 0 when it does not split, -1 when `c` is refused
+
 // conv1_1 (stem.hip): 3 -> 64 channels straight from the fp32 image (bf16 / f16; f16x3: the split-precision form)
 void stem_pack_weights(const float* hwio, int dtype, std::vector<uint16_t>* frags);
 float stem_pack_weights_split(const float* hwio, std::vector<uint16_t>* frags);     // RON_DTYPE_F16X3: returns the epilogue's 2^-k

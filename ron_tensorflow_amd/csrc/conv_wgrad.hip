@@ -1,0 +1,597 @@
+// Backward of the stride-1 SAME convolution (ron_conv2d_backward_nhwc): data, weight and bias gradients.
+//
+//   dz    = round(dy * (y > 0))                              pack_halo_kernel (ReLU mask fused), a halo tensor of the storage type
+//   dx    = round(conv_SAME(dz, flipped / swapped weights))  launch_conv on dz (the forward's kernels), weights packed ON THE DEVICE
+//   dw[t] = X_t^T . dZ  per tap                              conv_wgrad_tile_kernel: the new GEMM, K = the pixel axis
+//   dbias = column sums of dz                                colsum kernels, two passes, fixed order
+//
+// The weight gradient.  x and dz live in the SAME halo geometry (TensorView: shared halos, pad = (k - 1) * dilation / 2) and dz's
+// halo is zero, so K is simply the flat halo-pixel index q: dz row q meets x row q + (ky * dil - pad) * Wp + (kx * dil - pad), the
+// addressing of the forward's row gather.  A product whose dz pixel is a halo pixel is 0 * (a finite x value), one whose x pixel left
+// the map reads a zero halo pixel: no 2-D index math and no bounds test in the loop.  The price is that EVERY row the loop can touch
+// holds finite data: x carries `guard` = pad * Wp + pad zero pixels in front of pixel 0 and behind the last one, and both tensors
+// are zero up to the next multiple of 32 pixels (the K step).  ron_conv2d_backward_nhwc writes all of that itself.
+//
+// One workgroup = four waves = one 128 (cin) x 128 (cout) tile of one tap over one slice of the pixel range; each wave owns 64 x 64
+// of it as 4 x 4 v_mfma_f32_16x16x32 accumulators (64 fp32 registers per lane).  An axis of exactly 64 channels gets a 64-wide tile
+// (2 blocks per wave along it) instead of multiplying zeros in half of a 128-wide one.  Per K step of 32 pixels both operands are staged
+// as [32 pixels][128 channels] images: plain 16-byte global loads -> registers -> ds_write_b128, double buffered, one barrier per step
+// (no LDS-DMA, no counted vmcnt: nothing for tools/check_dma_counts.py here).  Both MFMA operands want K (pixels) along the lane's
+// registers while the images have channels along the row, so both are read with ds_read_b64_tr_b16: per 16 channels two reads per
+// lane group g, pixel rows 8g .. 8g+3 and 8g+4 .. 8g+7.  The images use the XOR swizzle of 256-byte rows that is documented as
+// conflict free for these reads on a full 128-channel image (not measured here: no LDS bank-conflict counter was collected):  off(row, ch) = 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))),  ch = the 16-byte chunk of the row.
+// The transposed read needs EXEC all ones: the workgroup is 256 lanes, every branch around the reads is workgroup-uniform, and
+// channel tiles that overhang the tensor are staged as zeros (pad, do not mask).
+//
+// Pixel slices: when tiles x taps leave CUs idle the pixel range is split over S workgroups per tile (conv1_2: 64 x 64 channels,
+// 3.3 M pixels -> 9 tiles, S > 100).  Slices write fp32 slabs with plain stores, conv_wgrad_reduce_kernel adds them in slice order:
+// no float atomics, the same bits on every run.  The taps of one (slice, tile) are adjacent workgroup ids: the nine read the same
+// pixel rows, shifted, while those are in L2.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+
+#include "conv_mfma.h"
+
+namespace ron {
+namespace {
+
+constexpr int kWgTile = 128;        // channels per tile side
+constexpr int kWgStep = 32;         // pixels per K step
+constexpr int kWgImage = kWgStep * kWgTile * 2;     // bytes of one staged operand image
+constexpr int kWgLds = 4 * kWgImage;                // two operands, double buffered: 32 KB, inside the default limit
+
+typedef short v4i16 __attribute__((ext_vector_type(4)));
+typedef short v8i16 __attribute__((ext_vector_type(8)));
+typedef __bf16 v8bf16 __attribute__((ext_vector_type(8)));
+typedef _Float16 v8f16 __attribute__((ext_vector_type(8)));
+typedef float v4f32 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
+
+__device__ __forceinline__ unsigned short round_bf16_bits(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);      // keep NaN a NaN
+  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+}
+__device__ __forceinline__ unsigned short round_f16_bits(float f) {
+  const _Float16 h = (_Float16)f;
+  return __builtin_bit_cast(unsigned short, h);
+}
+template <bool BF16> __device__ __forceinline__ unsigned short round_bits(float f) { return BF16 ? round_bf16_bits(f) : round_f16_bits(f); }
+template <bool BF16> __device__ __forceinline__ float bits_to_f(unsigned short b) {
+  if (BF16) return __uint_as_float((unsigned)b << 16);
+  return (float)__builtin_bit_cast(_Float16, b);
+}
+
+// byte offset of 16-byte chunk `ch` (0..15) of pixel row `row` (0..31) in a staged image
+__device__ __forceinline__ int image_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
+
+// ---- pack: dense fp32 [N,H,W,Csrc] -> halo tensor of the storage type, EVERY pixel of the buffer written ---------------------------
+// The buffer holds `rows` pixels of Cdst channels; pixel `guard` is halo pixel 0 of the view.  Interior pixels get the rounded
+// value (zero where mask <= 0, and in channels >= Csrc), everything else - halos, guards, the tail - zero.
+struct PackArgs {
+  const float* src;
+  const float* mask;        // null: no mask
+  unsigned short* out;
+  long long rows, guard;
+  int N, H, W, pad, Csrc, Cdst;
+};
+
+template <bool BF16>
+__global__ void conv_bwd_pack_halo_kernel(PackArgs a) {
+  // (every buffer of the entry point is below 2 GiB, plan_backward: the 16-byte pieces and the pixels fit 32-bit arithmetic)
+  const unsigned vecs = a.Cdst / 8;
+  const unsigned total = (unsigned)a.rows * vecs;
+  const unsigned Wp = a.W + a.pad, Hp = a.H + a.pad;
+  const bool vec_ok = a.Csrc % 4 == 0;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const unsigned b = i / vecs;
+    const int v = (int)(i - b * vecs);
+    float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (b >= (unsigned)a.guard) {
+      const unsigned q = b - (unsigned)a.guard;
+      const unsigned r = q / Wp;
+      const int col = (int)(q - r * Wp);
+      const unsigned img = r / Hp;
+      const int row = (int)(r - img * Hp);
+      if (col >= a.pad && row >= a.pad && img < (unsigned)a.N) {
+        const long long s0 = (((long long)img * a.H + (row - a.pad)) * a.W + (col - a.pad)) * a.Csrc + v * 8;
+        if (vec_ok && v * 8 + 8 <= a.Csrc) {
+          const float4 lo = *reinterpret_cast<const float4*>(a.src + s0), hi = *reinterpret_cast<const float4*>(a.src + s0 + 4);
+          f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+          if (a.mask != nullptr) {
+            const float4 ml = *reinterpret_cast<const float4*>(a.mask + s0), mh = *reinterpret_cast<const float4*>(a.mask + s0 + 4);
+            const float m[8] = {ml.x, ml.y, ml.z, ml.w, mh.x, mh.y, mh.z, mh.w};
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = m[e] > 0.f ? f[e] : 0.f;
+          }
+        } else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            if (v * 8 + e < a.Csrc) {
+              const float val = a.src[s0 + e];
+              f[e] = (a.mask == nullptr || a.mask[s0 + e] > 0.f) ? val : 0.f;
+            }
+          }
+        }
+      }
+    }
+    uint4 o;
+    o.x = round_bits<BF16>(f[0]) | ((unsigned)round_bits<BF16>(f[1]) << 16);
+    o.y = round_bits<BF16>(f[2]) | ((unsigned)round_bits<BF16>(f[3]) << 16);
+    o.z = round_bits<BF16>(f[4]) | ((unsigned)round_bits<BF16>(f[5]) << 16);
+    o.w = round_bits<BF16>(f[6]) | ((unsigned)round_bits<BF16>(f[7]) << 16);
+    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = o;
+  }
+}
+
+// ---- weights for the data gradient: fp32 HWIO on the device -> the blocked rows of pack.h, taps flipped, cin / cout swapped ----------
+// rows[n = ci][k = t * CoP + co] = round(w[kh-1-ky, kw-1-kx, ci, co])  (zero for co >= cout and n >= cin), stored as
+// [Npad / 64][K / 64][64 rows][64 elements]: hwio_to_rows + cast_rows + block_rows of the transposed filter.
+struct WpackArgs {
+  const float* w;
+  unsigned short* out;
+  int taps, cin, cout, cop, npad;
+};
+
+template <bool BF16>
+__global__ void conv_bwd_pack_weights_kernel(WpackArgs a) {
+  const int K = a.taps * a.cop, steps = K / 64;
+  const long long total = (long long)a.npad * (K / 8);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    // i counts 16-byte pieces of the blocked image: [n / 64][kt][n % 64][piece of 8]
+    const int piece = (int)(i & 7);
+    const int nl = (int)((i >> 3) & 63);
+    const long long blk = i >> 9;
+    const int kt = (int)(blk % steps), nb = (int)(blk / steps);
+    const int n = nb * 64 + nl, k = kt * 64 + piece * 8;
+    const int t = k / a.cop, co = k - t * a.cop;
+    const int ts = a.taps - 1 - t;                 // flipped tap (ky, kx both reversed = the flat tap index reversed)
+    unsigned short h[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      float v = 0.f;
+      if (n < a.cin && co + e < a.cout) v = a.w[((long long)ts * a.cin + n) * a.cout + co + e];
+      h[e] = round_bits<BF16>(v);
+    }
+    uint4 o;
+    o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
+    o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
+    *reinterpret_cast<uint4*>(a.out + i * 8) = o;
+  }
+}
+
+// ---- bias gradient: column sums of the packed dz, two passes in a fixed order ----------------------------------------------------------
+// pass 1: block (chunk, 64-channel group): 32 row lanes x 8 vectors of 8 channels; a row lane adds rows r, r + 32, ... of its chunk,
+// then 64 threads add the 32 lane sums in lane order.  pass 2: one wave per channel adds the chunk sums, lanes strided, then a fixed tree.
+template <bool BF16>
+__global__ __launch_bounds__(256) void conv_bwd_colsum_kernel(const unsigned short* dz, long long rows, int cop, long long chunk_rows, float* partial) {
+  __shared__ float sums[32][64];
+  const int tid = threadIdx.x, v = tid & 7, rl = tid >> 3;
+  const int c0 = blockIdx.y * 64;
+  const long long r0 = (long long)blockIdx.x * chunk_rows, r1 = r0 + chunk_rows < rows ? r0 + chunk_rows : rows;
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (long long r = r0 + rl; r < r1; r += 32) {
+    const uint4 d = *reinterpret_cast<const uint4*>(dz + r * cop + c0 + v * 8);
+    const unsigned u[4] = {d.x, d.y, d.z, d.w};
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      acc[2 * e] += bits_to_f<BF16>((unsigned short)(u[e] & 0xFFFFu));
+      acc[2 * e + 1] += bits_to_f<BF16>((unsigned short)(u[e] >> 16));
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 8; ++e) sums[rl][v * 8 + e] = acc[e];
+  __syncthreads();
+  if (tid < 64) {
+    float s = 0.f;
+    for (int l = 0; l < 32; ++l) s += sums[l][tid];
+    partial[(long long)blockIdx.x * cop + c0 + tid] = s;
+  }
+}
+
+// one wave per channel: lane l adds chunks l, l + 64, ... in that order, then the 64 lane sums are added in a fixed tree
+__global__ __launch_bounds__(64) void conv_bwd_colsum_final_kernel(const float* partial, int chunks, int cop, float* dbias) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  float s = 0.f;
+  for (int k = lane; k < chunks; k += 64) s += partial[(long long)k * cop + c];
+#pragma unroll
+  for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+  if (lane == 0) dbias[c] = s;
+}
+
+// ---- the weight-gradient tile ----------------------------------------------------------------------------------------------------------
+struct WgradArgs {
+  const char* x;            // halo pixel 0 of x (guard pixels in front)
+  const char* dz;           // halo pixel 0 of dz
+  float* out;               // dw [taps][cin][cout], or the slabs [slices][taps][cin][cout]
+  long long slab_elems;     // taps * cin * cout
+  int cin, cop, cout;
+  int Wp, pad, dil, kw, taps;
+  int tiles_m, tiles_n;
+  int steps, steps_per;     // K steps in all / per slice (no empty slice)
+};
+
+template <bool BF16>
+__device__ __forceinline__ v4f32 wgrad_mfma(v8i16 a, v8i16 b, v4f32 c) {
+  if (BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf16, a), __builtin_bit_cast(v8bf16, b), c, 0, 0, 0);
+  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8f16, a), __builtin_bit_cast(v8f16, b), c, 0, 0, 0);
+}
+
+// the 8 K values (pixel rows 8g .. 8g+7) x 16 channels operand of one lane group, from the image at `img`: two transposed reads
+__device__ __forceinline__ v8i16 wgrad_operand(const char* img, int off_lo, int off_hi) {
+  const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(img + off_lo));
+  const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(img + off_hi));
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+}
+
+// WBM, WBN: 16-channel MFMA blocks per wave along cin / cout (4 or 2): the workgroup's tile is 32 WBM x 32 WBN channels.  The 64-wide
+// forms are for tensors of 64 channels (conv1_2; heads of <= 64 outputs), where a 128-wide tile would multiply zeros half the time.
+// They keep the 256-byte image rows and their swizzle and fill half of each row: whether the transposed reads stay conflict free on
+// the half-filled image has not been measured.  The epilogue stores 4 bytes per lane, 16 lanes side by side (64-byte segments at
+// stride cout): not measured either; it runs once per workgroup behind the whole K loop.
+template <bool BF16, int WBM, int WBN>
+__global__ __launch_bounds__(256) void conv_wgrad_tile_kernel(WgradArgs a) {
+  constexpr int TM = 32 * WBM, TN = 32 * WBN;
+  constexpr int XCH = TM / 8, ZCH = TN / 8;            // 16-byte chunks per image row
+  constexpr int XN = XCH * kWgStep / 256, ZN = ZCH * kWgStep / 256;      // chunks a lane stages per step (2 or 1)
+  extern __shared__ __attribute__((aligned(16))) char smem[];      // [buffer][x image | dz image]
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wm = wave >> 1, wn = wave & 1;
+  unsigned id = blockIdx.x;
+  const int tap = id % a.taps; id /= a.taps;
+  const int tn = id % a.tiles_n; id /= a.tiles_n;
+  const int tm = id % a.tiles_m;
+  const int slice = id / a.tiles_m;
+  const int m0 = tm * TM, n0 = tn * TN;
+  const int ky = tap / a.kw, kx = tap - ky * a.kw;
+  const long long tap_off = (long long)(ky * a.dil - a.pad) * a.Wp + (kx * a.dil - a.pad);
+
+  // staging: lane -> 16-byte chunk xch of pixel row xrow (and, 128-wide, of row xrow + 16) of the x image; the same for dz
+  const int xrow = tid / XCH, xch = tid % XCH, zrow = tid / ZCH, zch = tid % ZCH;
+  const bool xv = m0 + xch * 8 < a.cin, zv = n0 + zch * 8 < a.cop;        // a tile that overhangs the channels stages zeros
+  const int s_begin = slice * a.steps_per;
+  const int n_steps = (a.steps - s_begin < a.steps_per ? a.steps - s_begin : a.steps_per);
+  const long long q0 = (long long)s_begin * kWgStep;
+  const long long x_row_bytes = (long long)a.cin * 2, z_row_bytes = (long long)a.cop * 2;
+  const char* xp = a.x + (q0 + xrow + tap_off) * x_row_bytes + (long long)(m0 + xch * 8) * 2;
+  const char* zp = a.dz + (q0 + zrow) * z_row_bytes + (long long)(n0 + zch * 8) * 2;
+  const int xst = image_off(xrow, xch), zst = image_off(zrow, zch);        // (row + 16: the same swizzle, 4096 bytes on)
+  const uint4 zero4 = {0u, 0u, 0u, 0u};
+  // (plain variables, not arrays: indexed through the lambdas' references they ended up in scratch memory, the loads waited for at once)
+  uint4 rx0 = zero4, rx1 = zero4, rz0 = zero4, rz1 = zero4;
+  auto fetch = [&]() {
+    rx0 = xv ? *reinterpret_cast<const uint4*>(xp) : zero4;
+    if constexpr (XN == 2) rx1 = xv ? *reinterpret_cast<const uint4*>(xp + 16 * x_row_bytes) : zero4;
+    rz0 = zv ? *reinterpret_cast<const uint4*>(zp) : zero4;
+    if constexpr (ZN == 2) rz1 = zv ? *reinterpret_cast<const uint4*>(zp + 16 * z_row_bytes) : zero4;
+    xp += kWgStep * x_row_bytes;
+    zp += kWgStep * z_row_bytes;
+  };
+  auto stage = [&](int buf) {
+    char* xi = smem + buf * 2 * kWgImage;
+    char* zi = xi + kWgImage;
+    *reinterpret_cast<uint4*>(xi + xst) = rx0;
+    if constexpr (XN == 2) *reinterpret_cast<uint4*>(xi + xst + 4096) = rx1;
+    *reinterpret_cast<uint4*>(zi + zst) = rz0;
+    if constexpr (ZN == 2) *reinterpret_cast<uint4*>(zi + zst + 4096) = rz1;
+  };
+
+  // transposed reads: lane 16g + 4q + p supplies row 8g + 4h + q, channels 16 * blk + 4p .. + 3 (h = 0, 1)
+  const int g = lane >> 4, q = (lane >> 2) & 3, p = lane & 3;
+  int aoff[WBM][2], boff[WBN][2];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int row = 8 * g + 4 * h + q;
+#pragma unroll
+    for (int i = 0; i < WBM; ++i) aoff[i][h] = image_off(row, 2 * (wm * WBM + i) + (p >> 1)) + 8 * (p & 1);
+#pragma unroll
+    for (int j = 0; j < WBN; ++j) boff[j][h] = image_off(row, 2 * (wn * WBN + j) + (p >> 1)) + 8 * (p & 1);
+  }
+
+  v4f32 acc[WBM][WBN];
+#pragma unroll
+  for (int i = 0; i < WBM; ++i)
+#pragma unroll
+    for (int j = 0; j < WBN; ++j) acc[i][j] = v4f32{0.f, 0.f, 0.f, 0.f};
+
+  fetch();
+  stage(0);
+  __syncthreads();
+  for (int k = 0; k < n_steps; ++k) {                 // every branch here is workgroup-uniform: EXEC stays all ones at the reads
+    const bool more = k + 1 < n_steps;
+    if (more) fetch();
+    const char* xi = smem + (k & 1) * 2 * kWgImage;
+    const char* zi = xi + kWgImage;
+    v8i16 A[WBM], B[WBN];
+#pragma unroll
+    for (int i = 0; i < WBM; ++i) A[i] = wgrad_operand(xi, aoff[i][0], aoff[i][1]);
+#pragma unroll
+    for (int j = 0; j < WBN; ++j) B[j] = wgrad_operand(zi, boff[j][0], boff[j][1]);
+#pragma unroll
+    for (int i = 0; i < WBM; ++i)
+#pragma unroll
+      for (int j = 0; j < WBN; ++j) acc[i][j] = wgrad_mfma<BF16>(A[i], B[j], acc[i][j]);
+    if (more) stage((k + 1) & 1);
+    __syncthreads();
+  }
+
+  // accumulator (i, j), register r of lane l: cin = 16 i + 4 (l / 16) + r, cout = 16 j + l % 16 of the wave's blocks
+  float* out = a.out + (long long)slice * a.slab_elems + (long long)tap * a.cin * a.cout;
+#pragma unroll
+  for (int i = 0; i < WBM; ++i)
+#pragma unroll
+    for (int j = 0; j < WBN; ++j) {
+      const int n = n0 + (wn * WBN + j) * 16 + (lane & 15);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + (wm * WBM + i) * 16 + 4 * g + r;
+        if (m < a.cin && n < a.cout) out[(long long)m * a.cout + n] = acc[i][j][r];
+      }
+    }
+}
+
+// dw = slab 0 + slab 1 + ... in slice order
+__global__ void conv_wgrad_reduce_kernel(const float* slabs, int slices, long long elems, float* dw) {
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < elems; i += (long long)gridDim.x * blockDim.x) {
+    float s = slabs[i];
+    for (int k = 1; k < slices; ++k) s += slabs[(long long)k * elems + i];
+    dw[i] = s;
+  }
+}
+
+int grid_for(long long total) { return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16)); }
+
+// ---- planner ---------------------------------------------------------------------------------------------------------------------------
+struct WgradPlan {
+  int tm, tn;               // tile sides (128 or 64 channels)
+  int taps, tiles_m, tiles_n, steps, steps_per, slices;
+  int64_t slab_elems;
+};
+
+int plan_wgrad(const WgradLaunch& c, WgradPlan* p) {
+  RON_REQUIRE(dtype_is_half(c.dtype), "conv wgrad: bf16 / f16 only (dtype %d)", c.dtype);
+  RON_REQUIRE(c.kh >= 1 && c.kh == c.kw && (c.kh & 1) && c.dil >= 1, "conv wgrad: square odd filters (%d x %d, dilation %d)", c.kh, c.kw, c.dil);
+  const int pad = (c.kh - 1) * c.dil / 2;
+  RON_REQUIRE(c.x.N == c.dz.N && c.x.H == c.dz.H && c.x.W == c.dz.W && c.x.pad == pad && c.dz.pad == pad && c.x.N > 0 && c.x.H > 0 && c.x.W > 0,
+              "conv wgrad: x and dz must share one halo geometry with pad %d", pad);
+  RON_REQUIRE(c.x.coff == 0 && c.dz.coff == 0 && c.x.cstride == c.x.C && c.dz.cstride == c.dz.C && c.x.C % 64 == 0 && c.x.C > 0 &&
+              c.dz.C % 64 == 0 && c.Cout >= 1 && c.Cout <= c.dz.C, "conv wgrad: whole tensors with channels padded to 64 (cin %d, dz %d, cout %d)",
+              c.x.C, c.dz.C, c.Cout);
+  RON_REQUIRE(c.guard >= (int64_t)pad * c.x.Wp() + pad, "conv wgrad: x needs %lld guard pixels, has %lld", (long long)pad * c.x.Wp() + pad, (long long)c.guard);
+  const int64_t pixels = c.x.pixels();
+  RON_REQUIRE(pixels + kWgStep < ((int64_t)1 << 31), "conv wgrad: too many pixels");
+  p->taps = c.kh * c.kw;
+  p->tm = c.x.C == 64 ? 64 : kWgTile;
+  p->tn = c.dz.C == 64 ? 64 : kWgTile;
+  p->tiles_m = (c.x.C + p->tm - 1) / p->tm;
+  p->tiles_n = (c.dz.C + p->tn - 1) / p->tn;
+  p->steps = (int)((pixels + kWgStep - 1) / kWgStep);
+  p->slab_elems = (int64_t)p->taps * c.x.C * c.Cout;
+  // by shape: about four workgroups per CU (256 CUs; 32 KB of LDS each), slices of >= 8 steps
+  const int64_t base = (int64_t)p->taps * p->tiles_m * p->tiles_n;
+  int want = c.splitk;
+  if (want < 0) want = (int)std::min<int64_t>(std::max<int64_t>(1, 1024 / base), std::max(1, p->steps / 8));
+  RON_REQUIRE(want >= 1, "conv wgrad: pixel split %d", c.splitk);
+  want = std::min(want, p->steps);
+  // a forced split is capped where the slabs would reach 2 GiB (the sum kernel walks them serially per element)
+  want = (int)std::min<int64_t>(want, std::max<int64_t>(1, (((int64_t)1 << 31) - 1) / (p->slab_elems * 4)));
+  p->steps_per = (p->steps + want - 1) / want;
+  p->slices = (p->steps + p->steps_per - 1) / p->steps_per;       // no empty slice
+  RON_REQUIRE(base * p->slices < ((int64_t)1 << 31), "conv wgrad: grid too large");
+  return RON_OK;
+}
+
+template <bool BF16, int WBM, int WBN>
+int launch_wgrad_t(const WgradLaunch& c, const WgradPlan& p, hipStream_t s) {
+  WgradArgs a;
+  a.x = static_cast<const char*>(c.x.base); a.dz = static_cast<const char*>(c.dz.base);
+  a.out = p.slices > 1 ? static_cast<float*>(c.scratch) : c.dw;
+  a.slab_elems = p.slab_elems;
+  a.cin = c.x.C; a.cop = c.dz.C; a.cout = c.Cout;
+  a.Wp = c.x.Wp(); a.pad = c.x.pad; a.dil = c.dil; a.kw = c.kw; a.taps = p.taps;
+  a.tiles_m = p.tiles_m; a.tiles_n = p.tiles_n; a.steps = p.steps; a.steps_per = p.steps_per;
+  const unsigned grid = (unsigned)((int64_t)p.taps * p.tiles_m * p.tiles_n * p.slices);
+  RON_LAUNCH((conv_wgrad_tile_kernel<BF16, WBM, WBN>), dim3(grid), dim3(256), kWgLds, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  if (p.slices > 1) {
+    RON_LAUNCH(conv_wgrad_reduce_kernel, dim3(grid_for(p.slab_elems)), dim3(256), 0, s, static_cast<const float*>(c.scratch), p.slices, (long long)p.slab_elems, c.dw);
+    RON_HIP_CHECK(ron::launch_error());
+  }
+  return RON_OK;
+}
+
+template <bool BF16>
+int launch_wgrad_dtype(const WgradLaunch& c, const WgradPlan& p, hipStream_t s) {
+  if (p.tm == 64) return p.tn == 64 ? launch_wgrad_t<BF16, 2, 2>(c, p, s) : launch_wgrad_t<BF16, 2, 4>(c, p, s);
+  return p.tn == 64 ? launch_wgrad_t<BF16, 4, 2>(c, p, s) : launch_wgrad_t<BF16, 4, 4>(c, p, s);
+}
+
+}  // namespace
+
+int conv_wgrad_slices(const WgradLaunch& c) {
+  WgradPlan p;
+  return plan_wgrad(c, &p) == RON_OK ? p.slices : -1;
+}
+
+int64_t conv_wgrad_scratch_bytes(const WgradLaunch& c) {
+  WgradPlan p;
+  if (plan_wgrad(c, &p) != RON_OK) return -1;
+  return p.slices > 1 ? (int64_t)p.slices * p.slab_elems * 4 : 0;
+}
+
+int launch_conv_wgrad(const WgradLaunch& c, hipStream_t stream) {
+  WgradPlan p;
+  int rc = plan_wgrad(c, &p);
+  if (rc != RON_OK) return rc;
+  RON_REQUIRE(c.x.base != nullptr && c.dz.base != nullptr && c.dw != nullptr, "conv wgrad: NULL tensor");
+  RON_REQUIRE(p.slices == 1 || (c.scratch != nullptr && c.scratch_bytes >= (int64_t)p.slices * p.slab_elems * 4),
+              "conv wgrad: %d pixel slices need %lld bytes of scratch", p.slices, (long long)p.slices * p.slab_elems * 4);
+  return c.dtype == RON_DTYPE_BF16 ? launch_wgrad_dtype<true>(c, p, stream) : launch_wgrad_dtype<false>(c, p, stream);
+}
+
+// ---- ron_conv2d_backward_nhwc ------------------------------------------------------------------------------------------------------------
+namespace {
+
+// Everything the entry point decides on the host: the descriptor's checks and the carving of the workspace (offsets in bytes).
+struct BackwardPlan {
+  int pad = 0, cop = 0, npad = 0, taps = 0;
+  int64_t pixels = 0, rows = 0, guard = 0;      // halo pixels; rounded up to the K step; guard pixels of x on each side
+  int chunks = 0;
+  int64_t chunk_rows = 0;
+  int64_t off_dz = 0, off_x = 0, off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
+  int64_t dz_bytes = 0, x_bytes = 0, w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
+  ConvLaunch conv;          // the data gradient (pointers unset)
+  WgradLaunch wg;           // the weight gradient (pointers unset)
+};
+
+int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
+  RON_REQUIRE(d != nullptr, "NULL descriptor");
+  RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv backward: dtype %d: bf16 or fp16 only (fp32 and f16x3 have no backward)", d->dtype);
+  RON_REQUIRE(d->transpose == 0 && d->pool == 0 && d->center_from == 0 && d->in_cstride == 0 && d->in_coff == 0 && d->tile_cfg == -1,
+              "conv backward: a plain convolution (transpose, pool, center_from, in_cstride, in_coff = 0, tile_cfg = -1)");
+  RON_REQUIRE(d->stride == 1, "conv backward: stride %d: stride-1 SAME convolutions only", d->stride);
+  RON_REQUIRE(d->kh == d->kw && (d->kh == 1 || d->kh == 3), "conv backward: filter %d x %d: 1 x 1 or 3 x 3 only", d->kh, d->kw);
+  RON_REQUIRE(d->dilation >= 1, "conv backward: dilation %d", d->dilation);
+  RON_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cout >= 1, "conv backward: empty tensor");
+  RON_REQUIRE(d->cin > 0 && d->cin % 64 == 0, "conv backward: cin %d must be a multiple of 64 (the 3-channel stem is out of scope)", d->cin);
+  RON_REQUIRE(d->splitk == -1 || d->splitk >= 1, "conv backward: pixel split %d (-1 = by shape, 1 = off, S = forced)", d->splitk);
+  const int esz = 2;
+  P->pad = (d->kh - 1) * d->dilation / 2;
+  P->cop = (int)align_up(d->cout, 64);
+  P->taps = d->kh * d->kw;
+  P->npad = (int)align_up(d->cin, conv_n_tile(d->cin));
+  P->pixels = TensorView::halo_pixels(d->n, d->h, d->w, P->pad);
+  P->rows = align_up(P->pixels, kWgStep);
+  P->guard = (int64_t)P->pad * (d->w + P->pad) + P->pad;
+  P->dz_bytes = P->rows * P->cop * esz;
+  P->x_bytes = (P->rows + 2 * P->guard) * d->cin * esz;
+  P->w_bytes = (int64_t)P->npad * P->taps * P->cop * esz;
+  P->dx_bytes = TensorView::halo_pixels(d->n, d->h, d->w, 1) * d->cin * esz;
+  const int64_t lim = (int64_t)1 << 31;
+  RON_REQUIRE(P->dz_bytes < lim && P->x_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv backward: a packed tensor would reach 2 GiB");
+  // the data gradient as a forward launch over dz
+  ConvLaunch& c = P->conv;
+  c.dtype = d->dtype;
+  c.in.N = d->n; c.in.H = d->h; c.in.W = d->w; c.in.C = P->cop; c.in.cstride = P->cop; c.in.pad = P->pad;
+  c.in.bytes = P->pixels * P->cop * esz;
+  c.out.N = d->n; c.out.H = d->h; c.out.W = d->w; c.out.C = d->cin; c.out.cstride = d->cin; c.out.pad = 1;
+  c.out.bytes = P->dx_bytes;
+  c.wgt_bytes = P->w_bytes;
+  c.Cout = d->cin; c.Npad = P->npad;
+  c.kh = d->kh; c.kw = d->kw; c.stride = 1; c.dil = d->dilation; c.cpad = P->pad;
+  c.relu = 0; c.Ho = d->h; c.Wo = d->w;
+  c.splitk = -1;
+  P->sk_bytes = conv_scratch_bytes(c);
+  // the weight gradient
+  WgradLaunch& g = P->wg;
+  g.dtype = d->dtype;
+  g.x = c.in; g.x.C = d->cin; g.x.cstride = d->cin; g.x.bytes = P->pixels * d->cin * esz;
+  g.dz = c.in;
+  g.kh = d->kh; g.kw = d->kw; g.dil = d->dilation; g.Cout = d->cout; g.guard = P->guard; g.splitk = d->splitk;
+  P->slab_bytes = conv_wgrad_scratch_bytes(g);
+  if (P->slab_bytes < 0) return RON_ERR_INVALID;
+  // bias gradient: at most 512 chunks of >= 32 rows
+  P->chunk_rows = std::max<int64_t>(32, (P->rows + 511) / 512);
+  P->chunks = (int)((P->rows + P->chunk_rows - 1) / P->chunk_rows);
+  int64_t at = 0;
+  auto carve = [&](int64_t bytes) { const int64_t o = at; at += align_up(bytes, 256); return o; };
+  P->off_dz = carve(P->dz_bytes);
+  P->off_x = carve(P->x_bytes);
+  P->off_w = carve(P->w_bytes);
+  P->off_bias = carve((int64_t)P->npad * 4);
+  P->off_dx = carve(P->dx_bytes);
+  P->off_sk = carve(P->sk_bytes);
+  P->off_slab = carve(P->slab_bytes);
+  P->off_part = carve((int64_t)P->chunks * P->cop * 4);
+  P->total = at;
+  return RON_OK;
+}
+
+template <bool BF16>
+int launch_pack_halo(const float* src, const float* mask, void* out, const BackwardPlan& P, const ron_conv_desc* d, int csrc, int cdst,
+                     int64_t guard, hipStream_t s) {
+  PackArgs a;
+  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
+  a.rows = P.rows + 2 * guard; a.guard = guard;
+  a.N = d->n; a.H = d->h; a.W = d->w; a.pad = P.pad; a.Csrc = csrc; a.Cdst = cdst;
+  RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+template <bool BF16>
+int run_backward(const ron_conv_desc* d, const BackwardPlan& P, const float* x, const float* w, const float* y, const float* dy,
+                 float* dx, float* dw, float* dbias, char* ws, hipStream_t s) {
+  int rc;
+  void* dzbuf = ws + P.off_dz;
+  if ((rc = launch_pack_halo<BF16>(dy, d->relu ? y : nullptr, dzbuf, P, d, d->cout, P.cop, 0, s))) return rc;
+  if (dx != nullptr) {
+    WpackArgs wa;
+    wa.w = w; wa.out = reinterpret_cast<unsigned short*>(ws + P.off_w);
+    wa.taps = P.taps; wa.cin = d->cin; wa.cout = d->cout; wa.cop = P.cop; wa.npad = P.npad;
+    RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
+    RON_HIP_CHECK(ron::launch_error());
+    RON_HIP_CHECK(dev_memset_async(ws + P.off_bias, 0, (size_t)P.npad * 4, s));
+    ConvLaunch c = P.conv;
+    c.in.base = dzbuf; c.out.base = ws + P.off_dx;
+    c.wgt = ws + P.off_w; c.bias = reinterpret_cast<const float*>(ws + P.off_bias);
+    if (P.sk_bytes > 0) { c.scratch = ws + P.off_sk; c.scratch_bytes = P.sk_bytes; }
+    if ((rc = launch_conv(c, s))) return rc;
+    if ((rc = launch_unpack(c.out, d->dtype, 0, dx, s))) return rc;
+  }
+  if (dw != nullptr) {
+    if ((rc = launch_pack_halo<BF16>(x, nullptr, ws + P.off_x, P, d, d->cin, d->cin, P.guard, s))) return rc;
+    WgradLaunch g = P.wg;
+    g.x.base = ws + P.off_x + P.guard * d->cin * 2;
+    g.dz.base = dzbuf;
+    g.dw = dw;
+    if (P.slab_bytes > 0) { g.scratch = ws + P.off_slab; g.scratch_bytes = P.slab_bytes; }
+    if ((rc = launch_conv_wgrad(g, s))) return rc;
+  }
+  if (dbias != nullptr) {
+    float* part = reinterpret_cast<float*>(ws + P.off_part);
+    RON_LAUNCH(conv_bwd_colsum_kernel<BF16>, dim3(P.chunks, P.cop / 64), dim3(256), 0, s, static_cast<const unsigned short*>(dzbuf),
+               (long long)P.rows, P.cop, (long long)P.chunk_rows, part);
+    RON_HIP_CHECK(ron::launch_error());
+    RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.cop, dbias);
+    RON_HIP_CHECK(ron::launch_error());
+  }
+  return RON_OK;
+}
+
+}  // namespace
+}  // namespace ron
+
+extern "C" int64_t ron_conv2d_backward_workspace_bytes(const ron_conv_desc* d) {
+  ron::BackwardPlan P;
+  if (ron::plan_backward(d, &P) != RON_OK) return -1;
+  return P.total;
+}
+
+extern "C" int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
+                                        float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace ron;
+  BackwardPlan P;
+  int rc = plan_backward(d, &P);
+  if (rc != RON_OK) return rc;
+  RON_REQUIRE(dy != nullptr, "conv backward: dy is NULL");
+  RON_REQUIRE(!d->relu || y != nullptr, "conv backward: relu is set and y is NULL (the mask is y > 0)");
+  RON_REQUIRE(dx == nullptr || w != nullptr, "conv backward: dx needs w");
+  RON_REQUIRE(dw == nullptr || x != nullptr, "conv backward: dw needs x");
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "conv backward: workspace of %lld bytes, %lld needed (ron_conv2d_backward_workspace_bytes)",
+              (long long)workspace_bytes, (long long)P.total);
+  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "conv backward: the workspace must be 256-byte aligned");
+  RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "conv backward: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)");
+  if (dx != nullptr) {
+    // what launch_conv would refuse is refused here, before anything is enqueued
+    ConvLaunch c = P.conv;
+    c.in.base = workspace; c.out.base = workspace; c.wgt = workspace; c.bias = static_cast<const float*>(workspace);
+    if (P.sk_bytes > 0) { c.scratch = workspace; c.scratch_bytes = P.sk_bytes; }
+    int o[4];
+    if ((rc = conv_describe(c, o))) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  return d->dtype == RON_DTYPE_BF16 ? run_backward<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)
+                                    : run_backward<false>(d, P, x, w, y, dy, dx, dw, dbias, ws, s);
+}

@@ -496,3 +496,85 @@ def maxpool2x2_nhwc(x, dtype='bf16'):
     y = torch.empty((n, (h + 1) // 2, (w + 1) // 2, c), dtype=torch.float32, device=x.device)
     check(lib().ron_maxpool2x2_nhwc(ptr(x), n, h, w, c, _lib.DTYPES[dtype], ptr(y), current_stream()))
     return y
+
+
+# --------------------------------------------------------------------------- #
+# convolution backward (ron_conv2d_backward_nhwc): a real entry point - it enqueues on the current stream and never synchronises
+# --------------------------------------------------------------------------- #
+def _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk):
+    return _lib.ConvDesc(n, h, w, cin, cout, k, k, 1, dilation, int(relu), 0, _lib.DTYPES[dtype], -1, 0, 0, 0, splitk, 0)
+
+
+def conv2d_backward_workspace_bytes(n, h, w, cin, cout, k=3, dilation=1, relu=True, dtype='bf16', splitk=-1):
+    """Bytes of workspace conv2d_backward_nhwc needs for this convolution (host arithmetic; raises on a descriptor it refuses)."""
+    d = _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk)
+    nbytes = lib().ron_conv2d_backward_workspace_bytes(C.byref(d))
+    if nbytes < 0:
+        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
+    return int(nbytes)
+
+
+def conv2d_backward_nhwc(x, w, dy, y=None, relu=True, dilation=1, dtype='bf16', splitk=-1, need=('dx', 'dw', 'db'), workspace=None):
+    """Gradients of y = act(conv_SAME(x, w) + bias), stride 1: (dx, dw, db), None for those not in `need`.
+
+    x [N,H,W,Cin], dy and y [N,H,W,Cout] GPU fp32; w HWIO [k,k,Cin,Cout], a GPU fp32 tensor (a numpy array is uploaded).  With
+    `relu` the mask is y > 0, so the forward output is required.  Operands are rounded to `dtype` (bf16 / fp16), sums are fp32 in a
+    fixed order: dx comes back as storage-type values in fp32, dw [k,k,Cin,Cout] and db [Cout] as unrounded fp32 sums.
+    `splitk`: pixel slices of the weight gradient (-1 by shape, 1 off, S forced).  `workspace`: a uint8 GPU tensor of at least
+    conv2d_backward_workspace_bytes(...) bytes, or None for the cached per-device, per-stream buffer."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    if not hasattr(w, 'data_ptr'):
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
+    w = w.contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and dy.is_cuda and w.is_cuda
+    n, h, wd, cin = x.shape
+    k, cout = w.shape[0], w.shape[3]
+    assert tuple(w.shape) == (k, k, cin, cout) and tuple(dy.shape) == (n, h, wd, cout)
+    if relu and y is None:
+        raise _lib.RonError('conv2d_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
+    if y is not None:
+        y = y.contiguous()
+        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
+    unknown = set(need) - {'dx', 'dw', 'db'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    d = _backward_desc(n, h, wd, cin, cout, k, dilation, relu, dtype, splitk)
+    nbytes = lib().ron_conv2d_backward_workspace_bytes(C.byref(d))
+    if nbytes < 0:
+        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
+    ws = _workspace(dev, nbytes) if workspace is None else workspace
+    dx = torch.empty_like(x) if 'dx' in need else None
+    dw = torch.empty_like(w) if 'dw' in need else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
+    check(lib().ron_conv2d_backward_nhwc(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
+                                         ptr(ws), int(ws.numel()), current_stream()))
+    return dx, dw, db
+
+
+class _Conv2dNhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, relu, dilation, dtype):
+        # ron_conv2d_nhwc takes HOST weights and synchronises: a convenience for tests and small experiments, not the training path
+        b = None if bias is None else bias.detach().cpu().numpy()
+        y = conv2d_nhwc(x.detach(), w.detach().cpu().numpy(), b, dilation=dilation, relu=relu, dtype=dtype)
+        ctx.save_for_backward(x, w, y)
+        ctx.cfg = (relu, dilation, dtype, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        relu, dilation, dtype, has_bias = ctx.cfg
+        need = tuple(name for name, on in zip(('dx', 'dw', 'db'), (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                                                   has_bias and ctx.needs_input_grad[2])) if on)
+        dx, dw, db = conv2d_backward_nhwc(x, w, dy, y, relu=relu, dilation=dilation, dtype=dtype, need=need) if need else (None, None, None)
+        return dx, dw, db, None, None, None
+
+
+def conv2d_nhwc_fn(x, w, bias, relu=True, dilation=1, dtype='bf16'):
+    """act(conv_SAME(x, w) + bias), stride 1, as a torch.autograd.Function: x [N,H,W,Cin], w HWIO, bias [Cout] or None, GPU fp32 tensors.
+
+    The forward is ron_conv2d_nhwc, which packs the weights on the HOST (a device-to-host copy of w) and synchronises: a
+    convenience for tests and small experiments, not the training path.  The backward is ONE ron_conv2d_backward_nhwc call on the
+    current stream, computing only the gradients autograd asks for; tensors that do not require grad get None."""
+    return _Conv2dNhwcFn.apply(x, w, bias, relu, dilation, dtype)

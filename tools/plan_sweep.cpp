@@ -129,6 +129,46 @@ static int loss_arguments() {
   return 0;
 }
 
+// ron_conv2d_backward_nhwc in the dry run: the descriptor checks, the planner of the weight gradient (tiles, pixel slices), the data
+// gradient's forward plan and the carving of the workspace, over the case table of tests/conv_grad_cases.py plus the layer
+// shapes of tools/conv_backward_time.py, every dtype and pixel split; the workspace pointer is used for arithmetic only.
+static int conv_backward_arguments() {
+  struct Case { int n, h, w, cin, cout, k, dil; };
+  const Case cases[] = {{1, 1, 1, 64, 64, 3, 1},     {2, 5, 7, 64, 24, 3, 1},      {3, 3, 3, 128, 126, 3, 1},  {1, 10, 10, 64, 192, 3, 6},
+                        {2, 19, 19, 192, 64, 1, 1},  {1, 38, 38, 320, 256, 3, 1},  {2, 40, 40, 64, 64, 3, 1},
+                        {32, 320, 320, 64, 64, 3, 1}, {32, 160, 160, 128, 128, 3, 1}, {32, 80, 80, 256, 256, 3, 1}, {32, 40, 40, 512, 512, 3, 1},
+                        {32, 20, 20, 512, 512, 3, 1}, {32, 10, 10, 1024, 1024, 1, 1}, {32, 40, 40, 512, 210, 3, 1}};
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (const Case& c : cases) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      for (int splitk : {-1, 1, 2, 7, 1000000}) {
+        for (int relu : {0, 1}) {
+          ron_conv_desc d;
+          memset(&d, 0, sizeof d);
+          d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.cout = c.cout; d.kh = d.kw = c.k; d.stride = 1; d.dilation = c.dil;
+          d.relu = relu; d.dtype = dtype; d.tile_cfg = -1; d.splitk = splitk;
+          const int64_t bytes = ron_conv2d_backward_workspace_bytes(&d);
+          if (bytes <= 0 || bytes % 256 != 0) return 1;
+          CHECK(ron_conv2d_backward_nhwc(&d, f, f, relu ? f : nullptr, f, f, f, f, ws, bytes, nullptr));
+          CHECK(ron_conv2d_backward_nhwc(&d, nullptr, f, relu ? f : nullptr, f, f, nullptr, nullptr, ws, bytes, nullptr));
+          CHECK(ron_conv2d_backward_nhwc(&d, f, nullptr, relu ? f : nullptr, f, nullptr, f, f, ws, bytes, nullptr));
+          if (ron_conv2d_backward_nhwc(&d, f, f, relu ? f : nullptr, f, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+          if (relu && ron_conv2d_backward_nhwc(&d, f, f, nullptr, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          ron_conv_desc bad = d;
+          bad.stride = 2;
+          if (ron_conv2d_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.cin = 96;
+          if (ron_conv2d_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.dtype = RON_DTYPE_F16X3;
+          if (ron_conv2d_backward_nhwc(&bad, f, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (getenv("RON_PLAN_ONLY") == nullptr) {
     fprintf(stderr, "plan_sweep: run with RON_PLAN_ONLY=1 (a dry run: this binary holds no device code)\n");
@@ -180,6 +220,10 @@ int main(int argc, char** argv) {
   }
   if (loss_arguments()) {
     fprintf(stderr, "plan_sweep: ron_losses / ron_losses_grad argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (conv_backward_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_conv2d_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
