@@ -656,13 +656,57 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
  * factor of the weight gradient: -1 = by shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the
  * fp32 partial sums of the slices would reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned pointer and a
  * workspace that is too small included - is RON_ERR_INVALID with a message, before any HIP call.
- * Out of scope: the 3-channel stem, strided and transposed convolutions, pools, fp32 and f16x3 arithmetic.
+ * Out of scope: the 3-channel stem, strided and transposed convolutions, pools (the 2x2 stride-2 ones have entry points of
+ * their own below), fp32 and f16x3 arithmetic.
  * ron_conv2d_backward_workspace_bytes is host arithmetic only (it depends on d->splitk too); -1 + ron_last_error() on a
  * descriptor the call would refuse.
  * ---------------------------------------------------------------------------------------- */
 int64_t ron_conv2d_backward_workspace_bytes(const ron_conv_desc* d);
 int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
                              float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Backward of the 2x2 stride-2 SAME max-pool (slim.max_pool2d [2, 2], pool1 .. pool5: nets/ron_vgg_320.py:456..475,
+ * nets/ssd_vgg_300.py:450..462).  A real entry point like the convolution backward: it enqueues on `stream`, allocates
+ * nothing, never synchronises, needs no workspace and honours the dry-run mode.
+ *
+ * x [n,h,w,c] is the pool's input, dy [n,ceil(h/2),ceil(w/2),c], dx [n,h,w,c]: device fp32, 16-byte aligned.  With
+ * xs = round(x) to `dtype` (what ron_maxpool2x2_nhwc pools): dx[n,i,j,ch] = round(dy[n,i/2,j/2,ch]) if (i, j) is the FIRST
+ * position of its window, in the order (0,0) (0,1) (1,0) (1,1), whose xs equals the window's maximum, else 0 (TensorFlow's
+ * MaxPoolGrad).  The comparison is on the rounded values: inputs that agree after rounding are a tie, and so are -0.0 and
+ * +0.0.  On an odd map the last window holds one row and / or one column; positions that do not exist are neither read nor
+ * written.  A window that holds a NaN is outside the contract (the forward drops NaNs).
+ * Every element of dx is written exactly once by a plain store (no atomics, no cleared buffer): the same inputs give the
+ * same bytes.  Accepted: dtype bf16 / fp16, c a multiple of 8, n, h, w >= 1; anything else is RON_ERR_INVALID with a
+ * message, before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+int ron_maxpool2x2_backward_nhwc(const float* x, const float* dy, int n, int h, int w, int c, int dtype, float* dx, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Backward of the two 2x2 stride-2 operators of the reverse connections: the strided convolution (block7_reverse_conv_left,
+ * nets/ron_vgg_320.py:420) with d->transpose = 0 and the transposed convolution (the _deconv_right of the reverse connections,
+ * nets/ron_vgg_320.py:424) with d->transpose = 1.  `d` is read as ron_conv2d_nhwc reads it - n, h, w are the dimensions of
+ * the input x - with kh = kw = stride = 2 and dilation = 1:
+ *   transpose = 0: x [n,h,w,cin], w and dw HWIO [2,2,cin,cout], y and dy [n,h/2,w/2,cout]; h and w even, cin a multiple of
+ *                  64, any cout >= 1
+ *   transpose = 1: x [n,h,w,cin], w and dw [2,2,cout,cin] (the forward's layout), y and dy [n,2h,2w,cout]; cin and cout
+ *                  multiples of 64
+ * Everything else is the contract of ron_conv2d_backward_nhwc: all pointers are DEVICE fp32, w included; operands are
+ * rounded to d->dtype (bf16 or fp16) and accumulated in fp32; dz = round(dy * (y > 0)) when d->relu (y is this operator's own
+ * output, so a branch of a reverse connection passes its own activation: see DESIGN.md 4.8), else round(dy); dx
+ * [n,h,w,cin] is delivered as storage-type values in fp32; dw and dbias [cout] are unrounded fp32 sums in a fixed order (the
+ * bias gradient of the transposed convolution adds its four taps in tap order); the same inputs give the same bytes.  dx,
+ * dw, dbias may each be NULL; every element of a non-NULL output is written; x may be NULL when dw is, w when dx is.  The
+ * call enqueues on `stream`, allocates nothing, never synchronises, honours the dry-run mode and assumes nothing about the
+ * workspace's contents.  x, y and dy must be 16-byte aligned, the workspace 256-byte aligned.  pool, center_from,
+ * in_cstride, in_coff = 0 and tile_cfg = -1; d->splitk is the pixel split of the weight gradient (-1 = by shape, 1 = off,
+ * S = forced, capped as in ron_conv2d_backward_nhwc).  Anything else - a NULL y with relu set, a misaligned pointer, a
+ * workspace that is too small, a packed tensor that would reach 2 GiB - is RON_ERR_INVALID with a message, before any HIP
+ * call.  ron_conv2d_k2s2_backward_workspace_bytes is host arithmetic only; -1 + ron_last_error() on a refused descriptor.
+ * ---------------------------------------------------------------------------------------- */
+int64_t ron_conv2d_k2s2_backward_workspace_bytes(const ron_conv_desc* d);
+int ron_conv2d_k2s2_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
+                                  float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,4 +1,5 @@
-// Backward of the stride-1 SAME convolution (ron_conv2d_backward_nhwc): data, weight and bias gradients.
+// Backward of the stride-1 SAME convolution (ron_conv2d_backward_nhwc): data, weight and bias gradients.  The 2x2 stride-2 convolution and
+// transposed convolution (ron_conv2d_k2s2_backward_nhwc) reuse its kernels on space-to-depth views: the last section of this file.
 //
 //   dz    = round(dy * (y > 0))                              pack_halo_kernel (ReLU mask fused), a halo tensor of the storage type
 //   dx    = round(conv_SAME(dz, flipped / swapped weights))  launch_conv on dz (the forward's kernels), weights packed ON THE DEVICE
@@ -594,4 +595,350 @@ extern "C" int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, 
   char* ws = static_cast<char*>(workspace);
   return d->dtype == RON_DTYPE_BF16 ? run_backward<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)
                                     : run_backward<false>(d, P, x, w, y, dy, dx, dw, dbias, ws, s);
+}
+
+// ---- ron_conv2d_k2s2_backward_nhwc: the 2x2 stride-2 convolution and the 2x2 stride-2 transposed convolution ----------------------------
+// Kernel == stride: every input pixel meets every output pixel through exactly one tap, so with s2d = space-to-depth
+// ([n,2H,2W,C] -> [n,H,W,(ky,kx,C)]) and d2s its inverse both operators are 1x1 convolutions on the coarse H x W grid:
+//
+//   convolution (x [n,2H,2W,cin], w [2,2,cin,cout], dz [n,H,W,cout])
+//     dw.reshape(4 cin, cout) = s2d(xs)^T dz          launch_conv_wgrad, kh = 1: x := s2d(xs), dz := dz
+//     dx = d2s(dz @ ws.reshape(4 cin, cout)^T)        launch_conv, 1x1, 4 cin outputs; the depth-to-space happens in the unpack
+//     dbias = column sums of dz
+//   transposed (x [n,H,W,cin], w [2,2,cout,cin], dz [n,2H,2W,cout]), Dz = s2d(dz) [n,H,W,4 cout]
+//     dw.reshape(4 cout, cin) = Dz^T xs               launch_conv_wgrad with the operands' roles swapped: x := Dz, dz := xs
+//     dx = Dz @ ws.reshape(4 cout, cin)               launch_conv, 1x1, K = 4 cout
+//     dbias[co] = the four taps' column sums of Dz, added in tap order
+//
+// No new MFMA kernel.  New here: the pack that gathers space-to-depth while it masks, rounds and packs (no fp32 shuffle pass), the
+// weights pack for [4 cout] x [cin] (the transposed layout is already K-major per output row: no flip, no swap), the depth-to-space
+// unpack and the tap fold of the bias gradient.  The coarse grid has no halo (pad 0, no guard pixels): the only zeros the weight
+// gradient relies on are the rows from n H W up to the next multiple of 32, which both packs write.
+namespace ron {
+namespace {
+
+// dense fp32 [N,2H,2W,C] -> [rows][4 C] of the storage type: row = coarse pixel, column (ky * 2 + kx) * C + c; rows >= N H W zero
+struct S2dArgs {
+  const float* src;
+  const float* mask;        // null: no mask
+  unsigned short* out;
+  long long rows;
+  int N, H, W, C;           // the COARSE grid; C % 8 == 0
+};
+
+template <bool BF16>
+__global__ void k2s2_pack_s2d_kernel(S2dArgs a) {
+  // (every packed tensor is below 2 GiB, plan_k2s2: the 16-byte pieces and the pixels fit 32-bit arithmetic)
+  const unsigned vecs = a.C / 2;                    // 4 C / 8
+  const unsigned total = (unsigned)a.rows * vecs;
+  const unsigned pixels = (unsigned)a.N * a.H * a.W;
+  for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
+    const unsigned b = i / vecs;
+    const int k = (int)(i - b * vecs) * 8;
+    float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (b < pixels) {
+      const int t = k / a.C, c = k - t * a.C;
+      const unsigned r = b / a.W;
+      const int col = (int)(b - r * a.W);
+      const unsigned img = r / a.H;
+      const int row = (int)(r - img * a.H);
+      const long long s0 = (((long long)img * 2 * a.H + 2 * row + (t >> 1)) * 2 * a.W + 2 * col + (t & 1)) * a.C + c;
+      const float4 lo = *reinterpret_cast<const float4*>(a.src + s0), hi = *reinterpret_cast<const float4*>(a.src + s0 + 4);
+      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+      if (a.mask != nullptr) {
+        const float4 ml = *reinterpret_cast<const float4*>(a.mask + s0), mh = *reinterpret_cast<const float4*>(a.mask + s0 + 4);
+        const float m[8] = {ml.x, ml.y, ml.z, ml.w, mh.x, mh.y, mh.z, mh.w};
+#pragma unroll
+        for (int e = 0; e < 8; ++e) f[e] = m[e] > 0.f ? f[e] : 0.f;
+      }
+    }
+    uint4 o;
+    o.x = round_bits<BF16>(f[0]) | ((unsigned)round_bits<BF16>(f[1]) << 16);
+    o.y = round_bits<BF16>(f[2]) | ((unsigned)round_bits<BF16>(f[3]) << 16);
+    o.z = round_bits<BF16>(f[4]) | ((unsigned)round_bits<BF16>(f[5]) << 16);
+    o.w = round_bits<BF16>(f[6]) | ((unsigned)round_bits<BF16>(f[7]) << 16);
+    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = o;
+  }
+}
+
+// weights of the transposed convolution for its data gradient: fp32 [2,2,cout,cin] = [K = 4 cout][cin] on the device -> the blocked rows
+// of pack.h, rows[n = ci][k] = round(w[k, ci]) (zero for n >= cin): [Npad / 64][K / 64][64 rows][64 elements]
+template <bool BF16>
+__global__ void k2s2_pack_weights_kn_kernel(const float* w, unsigned short* out, int K, int cin, int npad) {
+  const int steps = K / 64;
+  const long long total = (long long)npad * (K / 8);
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int piece = (int)(i & 7);
+    const int nl = (int)((i >> 3) & 63);
+    const long long blk = i >> 9;
+    const int kt = (int)(blk % steps), nb = (int)(blk / steps);
+    const int n = nb * 64 + nl, k = kt * 64 + piece * 8;
+    unsigned short h[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) h[e] = round_bits<BF16>(n < cin ? w[(long long)(k + e) * cin + n] : 0.f);
+    uint4 o;
+    o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
+    o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
+    *reinterpret_cast<uint4*>(out + i * 8) = o;
+  }
+}
+
+// dx of the convolution: the 1x1 launch's output, a halo tensor [N,H,W,4 C] (pad 1) of the storage type -> dense fp32 [N,2H,2W,C]
+struct D2sArgs {
+  const unsigned short* in;
+  float* dx;
+  int N, H, W, C;           // the coarse grid; C = cin
+  int vec_store;            // dx is 16-byte aligned
+};
+
+template <bool BF16>
+__global__ void k2s2_unpack_d2s_kernel(D2sArgs a) {
+  const int groups = a.C / 8;
+  const long long total = (long long)a.N * 2 * a.H * 2 * a.W * groups;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
+    const int g = (int)(i % groups);
+    const long long pix = i / groups;
+    const int ox = (int)(pix % (2 * a.W));
+    const int oy = (int)((pix / (2 * a.W)) % (2 * a.H));
+    const long long img = pix / ((long long)4 * a.W * a.H);
+    const long long q = (img * (a.H + 1) + 1 + (oy >> 1)) * (a.W + 1) + 1 + (ox >> 1);
+    const uint4 d = *reinterpret_cast<const uint4*>(a.in + q * 4 * a.C + ((oy & 1) * 2 + (ox & 1)) * a.C + g * 8);
+    const unsigned u[4] = {d.x, d.y, d.z, d.w};
+    float f[8];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      f[2 * e] = bits_to_f<BF16>((unsigned short)(u[e] & 0xFFFFu));
+      f[2 * e + 1] = bits_to_f<BF16>((unsigned short)(u[e] >> 16));
+    }
+    float* o = a.dx + i * 8;
+    if (a.vec_store) {
+      *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);
+      *reinterpret_cast<float4*>(o + 4) = make_float4(f[4], f[5], f[6], f[7]);
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = f[e];
+    }
+  }
+}
+
+// bias gradient of the transposed convolution: per channel the four taps' column sums of Dz, each summed like
+// conv_bwd_colsum_final_kernel does (lanes strided over the chunks, a fixed tree), then added in tap order
+__global__ __launch_bounds__(64) void k2s2_colsum_fold_kernel(const float* partial, int chunks, int cols, int cout, float* dbias) {
+  const int c = blockIdx.x, lane = threadIdx.x;
+  float total = 0.f;
+  for (int t = 0; t < 4; ++t) {
+    float s = 0.f;
+    for (int k = lane; k < chunks; k += 64) s += partial[(long long)k * cols + t * cout + c];
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) s += __shfl_xor(s, d, 64);
+    total = t == 0 ? s : total + s;
+  }
+  if (lane == 0) dbias[c] = total;
+}
+
+struct K2Plan {
+  int H = 0, W = 0;             // the coarse grid
+  int ca = 0, cz = 0;           // channels of the two packed operands: A (s2d gathered) and Z (dense)
+  int npad = 0, nout = 0;       // rows of the packed weights; outputs of the data-gradient launch
+  int kconv = 0;                // K of the data-gradient launch = channels of its input
+  int sum_cols = 0;             // columns of the tensor the bias gradient sums
+  int64_t pixels = 0, rows = 0;
+  int chunks = 0;
+  int64_t chunk_rows = 0;
+  int64_t off_a = 0, off_z = 0, off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
+  int64_t a_bytes = 0, z_bytes = 0, w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
+  ConvLaunch conv;
+  WgradLaunch wg;
+};
+
+int plan_k2s2(const ron_conv_desc* d, K2Plan* P) {
+  RON_REQUIRE(d != nullptr, "NULL descriptor");
+  RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv k2s2 backward: dtype %d: bf16 or fp16 only (fp32 and f16x3 have no backward)", d->dtype);
+  RON_REQUIRE(d->pool == 0 && d->center_from == 0 && d->in_cstride == 0 && d->in_coff == 0 && d->tile_cfg == -1,
+              "conv k2s2 backward: a plain operator (pool, center_from, in_cstride, in_coff = 0, tile_cfg = -1)");
+  RON_REQUIRE(d->kh == 2 && d->kw == 2 && d->stride == 2, "conv k2s2 backward: filter %d x %d, stride %d: 2 x 2 stride 2 only", d->kh, d->kw, d->stride);
+  RON_REQUIRE(d->dilation == 1, "conv k2s2 backward: dilation %d: 1 only", d->dilation);
+  RON_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cout >= 1, "conv k2s2 backward: empty tensor");
+  RON_REQUIRE(d->cin > 0 && d->cin % 64 == 0, "conv k2s2 backward: cin %d must be a multiple of 64", d->cin);
+  RON_REQUIRE(d->splitk == -1 || d->splitk >= 1, "conv k2s2 backward: pixel split %d (-1 = by shape, 1 = off, S = forced)", d->splitk);
+  const bool tr = d->transpose != 0;
+  if (tr) RON_REQUIRE(d->cout % 64 == 0, "conv k2s2 backward: transposed: cout %d must be a multiple of 64", d->cout);
+  else RON_REQUIRE(d->h % 2 == 0 && d->w % 2 == 0, "conv k2s2 backward: map %d x %d: the strided convolution needs even sides", d->h, d->w);
+  const int esz = 2;
+  const int64_t lim = (int64_t)1 << 31;
+  P->H = tr ? d->h : d->h / 2;
+  P->W = tr ? d->w : d->w / 2;
+  RON_REQUIRE((int64_t)d->n * P->H * P->W + kWgStep < lim, "conv k2s2 backward: too many pixels");
+  const int cop = (int)align_up(d->cout, 64);
+  P->ca = tr ? 4 * d->cout : 4 * d->cin;
+  P->cz = tr ? d->cin : cop;
+  P->kconv = tr ? P->ca : P->cz;
+  P->nout = tr ? d->cin : 4 * d->cin;
+  P->npad = (int)align_up(P->nout, conv_n_tile(P->nout));
+  P->sum_cols = tr ? P->ca : P->cz;
+  P->pixels = (int64_t)d->n * P->H * P->W;
+  P->rows = align_up(P->pixels, kWgStep);
+  P->a_bytes = P->rows * P->ca * esz;
+  P->z_bytes = P->rows * P->cz * esz;
+  P->w_bytes = (int64_t)P->npad * P->kconv * esz;
+  P->dx_bytes = TensorView::halo_pixels(d->n, P->H, P->W, 1) * P->nout * esz;
+  RON_REQUIRE(P->a_bytes < lim && P->z_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv k2s2 backward: a packed tensor would reach 2 GiB");
+  // the data gradient: a 1x1 forward launch on the coarse grid
+  ConvLaunch& c = P->conv;
+  c.dtype = d->dtype;
+  c.in.N = d->n; c.in.H = P->H; c.in.W = P->W; c.in.C = P->kconv; c.in.cstride = P->kconv; c.in.pad = 0;
+  c.in.bytes = P->pixels * P->kconv * esz;
+  c.out.N = d->n; c.out.H = P->H; c.out.W = P->W; c.out.C = P->nout; c.out.cstride = P->nout; c.out.pad = 1;
+  c.out.bytes = P->dx_bytes;
+  c.wgt_bytes = P->w_bytes;
+  c.Cout = P->nout; c.Npad = P->npad;
+  c.kh = 1; c.kw = 1; c.stride = 1; c.dil = 1; c.cpad = 0;
+  c.relu = 0; c.Ho = P->H; c.Wo = P->W;
+  c.splitk = -1;
+  P->sk_bytes = conv_scratch_bytes(c);
+  // the weight gradient: x := A, dz := Z
+  WgradLaunch& g = P->wg;
+  g.dtype = d->dtype;
+  g.x = c.in; g.x.C = P->ca; g.x.cstride = P->ca; g.x.bytes = P->pixels * P->ca * esz;
+  g.dz = c.in; g.dz.C = P->cz; g.dz.cstride = P->cz; g.dz.bytes = P->pixels * P->cz * esz;
+  g.kh = 1; g.kw = 1; g.dil = 1; g.Cout = tr ? d->cin : d->cout; g.guard = 0; g.splitk = d->splitk;
+  P->slab_bytes = conv_wgrad_scratch_bytes(g);
+  if (P->slab_bytes < 0) return RON_ERR_INVALID;
+  P->chunk_rows = std::max<int64_t>(32, (P->rows + 511) / 512);
+  P->chunks = (int)((P->rows + P->chunk_rows - 1) / P->chunk_rows);
+  int64_t at = 0;
+  auto carve = [&](int64_t bytes) { const int64_t o = at; at += align_up(bytes, 256); return o; };
+  P->off_a = carve(P->a_bytes);
+  P->off_z = carve(P->z_bytes);
+  P->off_w = carve(P->w_bytes);
+  P->off_bias = carve((int64_t)P->npad * 4);
+  P->off_dx = carve(P->dx_bytes);
+  P->off_sk = carve(P->sk_bytes);
+  P->off_slab = carve(P->slab_bytes);
+  P->off_part = carve((int64_t)P->chunks * P->sum_cols * 4);
+  P->total = at;
+  return RON_OK;
+}
+
+template <bool BF16>
+int k2s2_pack_s2d(const float* src, const float* mask, void* out, const K2Plan& P, int n, int c, hipStream_t s) {
+  S2dArgs a;
+  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
+  a.rows = P.rows; a.N = n; a.H = P.H; a.W = P.W; a.C = c;
+  RON_LAUNCH(k2s2_pack_s2d_kernel<BF16>, dim3(grid_for(a.rows * (c / 2))), dim3(256), 0, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+// a dense fp32 tensor on the coarse grid -> [rows][cdst] (conv_bwd_pack_halo_kernel without halo or guard)
+template <bool BF16>
+int k2s2_pack_dense(const float* src, const float* mask, void* out, const K2Plan& P, int n, int csrc, int cdst, hipStream_t s) {
+  PackArgs a;
+  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
+  a.rows = P.rows; a.guard = 0;
+  a.N = n; a.H = P.H; a.W = P.W; a.pad = 0; a.Csrc = csrc; a.Cdst = cdst;
+  RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+template <bool BF16>
+int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const float* w, const float* y, const float* dy,
+             float* dx, float* dw, float* dbias, char* ws, hipStream_t s) {
+  int rc;
+  const bool tr = d->transpose != 0;
+  const float* mask = d->relu ? y : nullptr;
+  void* abuf = ws + P.off_a;
+  void* zbuf = ws + P.off_z;
+  // dz: the dense operand of the convolution, the gathered one of the transposed convolution
+  void* dzbuf = tr ? abuf : zbuf;
+  if (tr) rc = k2s2_pack_s2d<BF16>(dy, mask, abuf, P, d->n, d->cout, s);
+  else rc = k2s2_pack_dense<BF16>(dy, mask, zbuf, P, d->n, d->cout, P.cz, s);
+  if (rc) return rc;
+  if (dx != nullptr) {
+    unsigned short* wout = reinterpret_cast<unsigned short*>(ws + P.off_w);
+    if (tr) {
+      RON_LAUNCH(k2s2_pack_weights_kn_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, w, wout, P.kconv, d->cin, P.npad);
+    } else {
+      // HWIO [2,2,cin,cout] = [4 cin][cout]: the rows of the launch as they stand (conv_bwd_pack_weights_kernel with a single tap)
+      WpackArgs wa;
+      wa.w = w; wa.out = wout;
+      wa.taps = 1; wa.cin = 4 * d->cin; wa.cout = d->cout; wa.cop = P.cz; wa.npad = P.npad;
+      RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
+    }
+    RON_HIP_CHECK(ron::launch_error());
+    RON_HIP_CHECK(dev_memset_async(ws + P.off_bias, 0, (size_t)P.npad * 4, s));
+    ConvLaunch c = P.conv;
+    c.in.base = dzbuf; c.out.base = ws + P.off_dx;
+    c.wgt = ws + P.off_w; c.bias = reinterpret_cast<const float*>(ws + P.off_bias);
+    if (P.sk_bytes > 0) { c.scratch = ws + P.off_sk; c.scratch_bytes = P.sk_bytes; }
+    if ((rc = launch_conv(c, s))) return rc;
+    if (tr) {
+      if ((rc = launch_unpack(c.out, d->dtype, 0, dx, s))) return rc;
+    } else {
+      D2sArgs u;
+      u.in = reinterpret_cast<const unsigned short*>(ws + P.off_dx); u.dx = dx;
+      u.N = d->n; u.H = P.H; u.W = P.W; u.C = d->cin; u.vec_store = ((uintptr_t)dx & 15) == 0;
+      RON_LAUNCH(k2s2_unpack_d2s_kernel<BF16>, dim3(grid_for((long long)d->n * d->h * d->w * (d->cin / 8))), dim3(256), 0, s, u);
+      RON_HIP_CHECK(ron::launch_error());
+    }
+  }
+  if (dw != nullptr) {
+    if (tr) rc = k2s2_pack_dense<BF16>(x, nullptr, zbuf, P, d->n, d->cin, d->cin, s);
+    else rc = k2s2_pack_s2d<BF16>(x, nullptr, abuf, P, d->n, d->cin, s);
+    if (rc) return rc;
+    WgradLaunch g = P.wg;
+    g.x.base = abuf;
+    g.dz.base = zbuf;
+    g.dw = dw;
+    if (P.slab_bytes > 0) { g.scratch = ws + P.off_slab; g.scratch_bytes = P.slab_bytes; }
+    if ((rc = launch_conv_wgrad(g, s))) return rc;
+  }
+  if (dbias != nullptr) {
+    float* part = reinterpret_cast<float*>(ws + P.off_part);
+    RON_LAUNCH(conv_bwd_colsum_kernel<BF16>, dim3(P.chunks, P.sum_cols / 64), dim3(256), 0, s, static_cast<const unsigned short*>(dzbuf),
+               (long long)P.rows, P.sum_cols, (long long)P.chunk_rows, part);
+    RON_HIP_CHECK(ron::launch_error());
+    if (tr) RON_LAUNCH(k2s2_colsum_fold_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.sum_cols, d->cout, dbias);
+    else RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.sum_cols, dbias);
+    RON_HIP_CHECK(ron::launch_error());
+  }
+  return RON_OK;
+}
+
+}  // namespace
+}  // namespace ron
+
+extern "C" int64_t ron_conv2d_k2s2_backward_workspace_bytes(const ron_conv_desc* d) {
+  ron::K2Plan P;
+  if (ron::plan_k2s2(d, &P) != RON_OK) return -1;
+  return P.total;
+}
+
+extern "C" int ron_conv2d_k2s2_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
+                                             float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace ron;
+  K2Plan P;
+  int rc = plan_k2s2(d, &P);
+  if (rc != RON_OK) return rc;
+  RON_REQUIRE(dy != nullptr, "conv k2s2 backward: dy is NULL");
+  RON_REQUIRE(!d->relu || y != nullptr, "conv k2s2 backward: relu is set and y is NULL (the mask is y > 0)");
+  RON_REQUIRE(dx == nullptr || w != nullptr, "conv k2s2 backward: dx needs w");
+  RON_REQUIRE(dw == nullptr || x != nullptr, "conv k2s2 backward: dw needs x");
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "conv k2s2 backward: workspace of %lld bytes, %lld needed (ron_conv2d_k2s2_backward_workspace_bytes)",
+              (long long)workspace_bytes, (long long)P.total);
+  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "conv k2s2 backward: the workspace must be 256-byte aligned");
+  RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "conv k2s2 backward: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)");
+  if (dx != nullptr) {
+    // what launch_conv would refuse is refused here, before anything is enqueued
+    ConvLaunch c = P.conv;
+    c.in.base = workspace; c.out.base = workspace; c.wgt = workspace; c.bias = static_cast<const float*>(workspace);
+    if (P.sk_bytes > 0) { c.scratch = workspace; c.scratch_bytes = P.sk_bytes; }
+    int o[4];
+    if ((rc = conv_describe(c, o))) return rc;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  return d->dtype == RON_DTYPE_BF16 ? run_k2s2<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)
+                                    : run_k2s2<false>(d, P, x, w, y, dy, dx, dw, dbias, ws, s);
 }

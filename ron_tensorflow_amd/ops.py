@@ -578,3 +578,115 @@ def conv2d_nhwc_fn(x, w, bias, relu=True, dilation=1, dtype='bf16'):
     convenience for tests and small experiments, not the training path.  The backward is ONE ron_conv2d_backward_nhwc call on the
     current stream, computing only the gradients autograd asks for; tensors that do not require grad get None."""
     return _Conv2dNhwcFn.apply(x, w, bias, relu, dilation, dtype)
+
+
+# --------------------------------------------------------------------------- #
+# backward of the 2x2 pool and of the 2x2 stride-2 convolutions (ron_maxpool2x2_backward_nhwc, ron_conv2d_k2s2_backward_nhwc):
+# real entry points like the convolution backward - they enqueue on the current stream and never synchronise
+# --------------------------------------------------------------------------- #
+def maxpool2x2_backward_nhwc(x, dy, dtype='bf16'):
+    """Gradient of maxpool2x2_nhwc at its input: x [N,H,W,C] (the pool's input), dy [N,ceil(H/2),ceil(W/2),C] GPU fp32 -> dx
+    [N,H,W,C].  round(dy) goes to the first position (row-major in the window) whose rounded input equals the window's maximum,
+    zero to the others (TensorFlow's MaxPoolGrad); every element of dx is written."""
+    x, dy = x.contiguous(), dy.contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and x.is_cuda and dy.is_cuda
+    n, h, w, c = x.shape
+    assert tuple(dy.shape) == (n, (h + 1) // 2, (w + 1) // 2, c), 'dy %s does not belong to x %s' % (tuple(dy.shape), tuple(x.shape))
+    dx = torch.empty_like(x)
+    check(lib().ron_maxpool2x2_backward_nhwc(ptr(x), ptr(dy), n, h, w, c, _lib.DTYPES[dtype], ptr(dx), current_stream()))
+    return dx
+
+
+def _k2s2_desc(n, h, w, cin, cout, relu, transpose, dtype, splitk):
+    return _lib.ConvDesc(n, h, w, cin, cout, 2, 2, 2, 1, int(relu), int(transpose), _lib.DTYPES[dtype], -1, 0, 0, 0, splitk, 0)
+
+
+def conv2d_k2s2_backward_workspace_bytes(n, h, w, cin, cout, relu=True, transpose=False, dtype='bf16', splitk=-1):
+    """Bytes of workspace conv2d_k2s2_backward_nhwc needs (n, h, w: the input x; host arithmetic; raises on a refused descriptor)."""
+    d = _k2s2_desc(n, h, w, cin, cout, relu, transpose, dtype, splitk)
+    nbytes = lib().ron_conv2d_k2s2_backward_workspace_bytes(C.byref(d))
+    if nbytes < 0:
+        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
+    return int(nbytes)
+
+
+def conv2d_k2s2_backward_nhwc(x, w, dy, y=None, relu=True, transpose=False, dtype='bf16', splitk=-1, need=('dx', 'dw', 'db'), workspace=None):
+    """Gradients of the 2x2 stride-2 convolution (x [N,H,W,Cin], w HWIO [2,2,Cin,Cout], y and dy [N,H/2,W/2,Cout]) or, with
+    `transpose`, of the 2x2 stride-2 transposed convolution (w [2,2,Cout,Cin], y and dy [N,2H,2W,Cout]): (dx, dw, db), None for
+    those not in `need`.  Everything else as conv2d_backward_nhwc: GPU fp32 tensors (a numpy w is uploaded), the mask is y > 0
+    with `relu`, dx comes back as storage-type values in fp32, dw (shaped like w) and db [Cout] as unrounded fp32 sums."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    if not hasattr(w, 'data_ptr'):
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
+    w = w.contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and dy.is_cuda and w.is_cuda
+    n, h, wd, cin = x.shape
+    cout = w.shape[2] if transpose else w.shape[3]
+    assert tuple(w.shape) == ((2, 2, cout, cin) if transpose else (2, 2, cin, cout)), 'w %s' % (tuple(w.shape),)
+    assert tuple(dy.shape) == ((n, 2 * h, 2 * wd, cout) if transpose else (n, h // 2, wd // 2, cout)), 'dy %s' % (tuple(dy.shape),)
+    if relu and y is None:
+        raise _lib.RonError('conv2d_k2s2_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
+    if y is not None:
+        y = y.contiguous()
+        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
+    unknown = set(need) - {'dx', 'dw', 'db'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    d = _k2s2_desc(n, h, wd, cin, cout, relu, transpose, dtype, splitk)
+    nbytes = lib().ron_conv2d_k2s2_backward_workspace_bytes(C.byref(d))
+    if nbytes < 0:
+        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
+    ws = _workspace(dev, nbytes) if workspace is None else workspace
+    dx = torch.empty_like(x) if 'dx' in need else None
+    dw = torch.empty_like(w) if 'dw' in need else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
+    check(lib().ron_conv2d_k2s2_backward_nhwc(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
+                                              ptr(ws), int(ws.numel()), current_stream()))
+    return dx, dw, db
+
+
+class _MaxPool2x2NhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dtype):
+        ctx.save_for_backward(x)
+        ctx.dtype = dtype
+        return maxpool2x2_nhwc(x.detach(), dtype=dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return (maxpool2x2_backward_nhwc(x, dy, ctx.dtype) if ctx.needs_input_grad[0] else None), None
+
+
+def maxpool2x2_nhwc_fn(x, dtype='bf16'):
+    """maxpool2x2_nhwc as a torch.autograd.Function: the forward is the test operator ron_maxpool2x2_nhwc (it synchronises), the
+    backward ONE ron_maxpool2x2_backward_nhwc call on the current stream (none when x does not require grad)."""
+    return _MaxPool2x2NhwcFn.apply(x, dtype)
+
+
+class _Conv2dK2s2NhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, relu, transpose, dtype):
+        b = None if bias is None else bias.detach().cpu().numpy()
+        y = conv2d_nhwc(x.detach(), w.detach().cpu().numpy(), b, stride=2, relu=relu, transpose=transpose, dtype=dtype)
+        ctx.save_for_backward(x, w, y)
+        ctx.cfg = (relu, transpose, dtype, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        relu, transpose, dtype, has_bias = ctx.cfg
+        need = tuple(name for name, on in zip(('dx', 'dw', 'db'), (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                                                   has_bias and ctx.needs_input_grad[2])) if on)
+        dx, dw, db = (conv2d_k2s2_backward_nhwc(x, w, dy, y, relu=relu, transpose=transpose, dtype=dtype, need=need) if need
+                      else (None, None, None))
+        return dx, dw, db, None, None, None
+
+
+def conv2d_k2s2_nhwc_fn(x, w, bias, relu=True, transpose=False, dtype='bf16'):
+    """act(conv(x, w) + bias) for the 2x2 stride-2 convolution (w HWIO) or, with `transpose`, the 2x2 stride-2 transposed
+    convolution (w [2,2,Cout,Cin]) as a torch.autograd.Function on GPU fp32 tensors.  The forward is ron_conv2d_nhwc (host weights,
+    synchronises: tests and small experiments; its transposed form wants Cout a multiple of 128); the backward is ONE
+    ron_conv2d_k2s2_backward_nhwc call on the current stream, computing only the gradients autograd asks for."""
+    return _Conv2dK2s2NhwcFn.apply(x, w, bias, relu, transpose, dtype)

@@ -169,6 +169,72 @@ static int conv_backward_arguments() {
   return 0;
 }
 
+// ron_maxpool2x2_backward_nhwc and ron_conv2d_k2s2_backward_nhwc in the dry run: the case tables of tests/op_grad_cases.py plus the
+// shapes of tools/op_backward_time.py, every dtype and pixel split, and the refusals; pointers are used for arithmetic only.
+static int op_backward_arguments() {
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  struct Pool { int n, h, w, c; };
+  const Pool pools[] = {{1, 1, 1, 8}, {1, 2, 2, 8}, {2, 5, 7, 8}, {1, 4, 6, 72}, {2, 9, 8, 64}, {1, 38, 38, 512},
+                        {32, 320, 320, 64}, {32, 160, 160, 128}, {32, 80, 80, 256}, {32, 40, 40, 512}, {32, 20, 20, 512}, {64, 75, 75, 256}};
+  for (const Pool& p : pools) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      CHECK(ron_maxpool2x2_backward_nhwc(f, f, p.n, p.h, p.w, p.c, dtype, f, nullptr));
+      if (ron_maxpool2x2_backward_nhwc(f, f, p.n, p.h, p.w, p.c + 4, dtype, f, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_maxpool2x2_backward_nhwc(f, f, p.n, 0, p.w, p.c, dtype, f, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_maxpool2x2_backward_nhwc(f, f + 1, p.n, p.h, p.w, p.c, dtype, f, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_maxpool2x2_backward_nhwc(f, f, p.n, p.h, p.w, p.c, dtype, nullptr, nullptr) != RON_ERR_INVALID) return 1;
+    }
+    if (ron_maxpool2x2_backward_nhwc(f, f, p.n, p.h, p.w, p.c, RON_DTYPE_F32, f, nullptr) != RON_ERR_INVALID) return 1;
+    if (ron_maxpool2x2_backward_nhwc(f, f, p.n, p.h, p.w, p.c, RON_DTYPE_F16X3, f, nullptr) != RON_ERR_INVALID) return 1;
+  }
+  struct Case { int n, h, w, cin, cout, transpose; };
+  const Case cases[] = {{1, 2, 2, 64, 64, 0},   {2, 6, 10, 64, 24, 0},  {3, 4, 4, 128, 126, 0},  {1, 10, 10, 320, 192, 0}, {2, 40, 40, 64, 64, 0},
+                        {1, 1, 1, 64, 64, 1},   {2, 3, 5, 64, 128, 1},  {3, 2, 2, 192, 64, 1},   {1, 20, 20, 512, 512, 1}, {2, 19, 19, 128, 64, 1},
+                        {32, 10, 10, 1024, 512, 0}, {32, 10, 10, 4096, 512, 0}, {32, 5, 5, 512, 512, 1}, {32, 10, 10, 512, 512, 1},
+                        {32, 20, 20, 512, 512, 1}, {32, 2, 2, 64, 1, 0}};
+  for (const Case& c : cases) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      for (int splitk : {-1, 1, 2, 7, 1000000}) {
+        for (int relu : {0, 1}) {
+          ron_conv_desc d;
+          memset(&d, 0, sizeof d);
+          d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.cout = c.cout; d.kh = d.kw = 2; d.stride = 2; d.dilation = 1;
+          d.relu = relu; d.transpose = c.transpose; d.dtype = dtype; d.tile_cfg = -1; d.splitk = splitk;
+          const int64_t bytes = ron_conv2d_k2s2_backward_workspace_bytes(&d);
+          if (bytes <= 0 || bytes % 256 != 0) return 1;
+          CHECK(ron_conv2d_k2s2_backward_nhwc(&d, f, f, relu ? f : nullptr, f, f, f, f, ws, bytes, nullptr));
+          CHECK(ron_conv2d_k2s2_backward_nhwc(&d, nullptr, f, relu ? f : nullptr, f, f, nullptr, nullptr, ws, bytes, nullptr));
+          CHECK(ron_conv2d_k2s2_backward_nhwc(&d, f, nullptr, relu ? f : nullptr, f, nullptr, f, f, ws, bytes, nullptr));
+          CHECK(ron_conv2d_k2s2_backward_nhwc(&d, f, f, relu ? f : nullptr, f, f + 1, f, f, ws, bytes, nullptr));      // a dx that is only 4-byte aligned
+          if (ron_conv2d_k2s2_backward_nhwc(&d, f, f, relu ? f : nullptr, f, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+          if (relu && ron_conv2d_k2s2_backward_nhwc(&d, f, f, nullptr, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          if (ron_conv2d_k2s2_backward_nhwc(&d, f, f, f, f + 1, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          ron_conv_desc bad = d;
+          bad.stride = 1;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.kh = bad.kw = 3;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.dilation = 2;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.cin = 96;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.pool = 1;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.splitk = 0;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d;
+          if (c.transpose) bad.cout = 24; else bad.h += 1;
+          if (ron_conv2d_k2s2_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.dtype = RON_DTYPE_F16X3;
+          if (ron_conv2d_k2s2_backward_nhwc(&bad, f, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (getenv("RON_PLAN_ONLY") == nullptr) {
     fprintf(stderr, "plan_sweep: run with RON_PLAN_ONLY=1 (a dry run: this binary holds no device code)\n");
@@ -224,6 +290,10 @@ int main(int argc, char** argv) {
   }
   if (conv_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_conv2d_backward_nhwc planning / argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (op_backward_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_maxpool2x2_backward_nhwc / ron_conv2d_k2s2_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
