@@ -586,6 +586,14 @@ int ron_profile_reset(ron_ctx* ctx);
  * and synchronise the stream (test / tooling use, not for graph capture).
  * `dtype` selects the arithmetic (operands rounded to bf16/f16, fp32 accumulate).
  * transpose != 0: slim.conv2d_transpose with kernel = stride (weights [kh,kw,cout,cin]).
+ *
+ * The envelope of ron_conv_desc, the same for every entry point that takes one (the kernels carry these fields in a few bits
+ * each; a value beyond them is refused, never wrapped):
+ *   kh, kw 1 .. 15; stride 1 .. 7; transposed kernel == stride 1 .. 7; dilation 1 .. 31; SAME padding (kh - 1) * dilation / 2 <= 63;
+ *   relu, pool, transpose 0 or 1; n, h, w, cin, cout >= 1.
+ * Filters are square (kh == kw); at stride 1 they are odd (an even filter's SAME padding is one pixel wider behind than in front,
+ * which the shared halo cannot hold); a strided convolution has kernel == stride on a map that stride divides.  Anything else
+ * is RON_ERR_INVALID with a message, before any allocation or launch.
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
   int32_t n, h, w, cin, cout;
@@ -651,8 +659,8 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
  * each be NULL (not computed); every element of a non-NULL output is written.  x may be NULL when dw is, w when dx is.
  * x, y and dy must be 16-byte aligned (they are read 16 bytes at a time), the workspace 256-byte aligned.
  *
- * Accepted descriptors: stride 1, kh == kw in {1, 3}, dilation >= 1, dtype bf16 / fp16, cin a multiple of 64, any
- * cout >= 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1.  d->splitk is the pixel-split
+ * Accepted descriptors: stride 1, kh == kw in {1, 3}, dilation 1 .. 31 (the envelope of ron_conv_desc above: the data
+ * gradient is a forward launch), dtype bf16 / fp16, cin a multiple of 64, any cout >= 1; relu 0 or 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1.  d->splitk is the pixel-split
  * factor of the weight gradient: -1 = by shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the
  * fp32 partial sums of the slices would reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned pointer and a
  * workspace that is too small included - is RON_ERR_INVALID with a message, before any HIP call.

@@ -554,7 +554,40 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& p, typename Tr::ac
   conv_epilogue_r<Tr, MR, NR, MT, EPA>(p, AccArray<Tr, MR, NR>{acc}, s_out_off, row0, fh, n_glob, n_store, tap_off, s_out2_off);
 }
 
-// Geometry / pointers of a launch -> kernel arguments (tiling fields are the caller's).
+// The size the comment in ConvArgs records: a field that no longer fits is refused (check_conv_fields), never widened.
+static_assert(sizeof(ConvArgs) == 208, "ConvArgs grew: the kernels' scalar registers carry exactly this much (see the comment in ConvArgs)");
+
+// Each limit of conv_mfma.h survives the narrowing into its bitfield.
+constexpr bool conv_limits_are_the_fields() {
+  ConvArgs a = ConvArgs();
+  a.kh = kConvMaxFilter; a.kw = kConvMaxFilter; a.stride = kConvMaxStride; a.up = kConvMaxStride; a.dil = kConvMaxDilation;
+  a.cpad = kConvMaxPad; a.in_org = kConvMaxInOrigin; a.out_pad = kConvMaxOutPad; a.out2_pad = kConvMaxOutPad; a.m_fastest = kConvMaxTileOrder;
+  return a.kh == kConvMaxFilter && a.kw == kConvMaxFilter && a.stride == kConvMaxStride && a.up == kConvMaxStride &&
+         a.dil == kConvMaxDilation && a.cpad == kConvMaxPad && a.in_org == kConvMaxInOrigin && a.out_pad == kConvMaxOutPad &&
+         a.out2_pad == kConvMaxOutPad && a.m_fastest == kConvMaxTileOrder;
+}
+static_assert(conv_limits_are_the_fields(), "the limits of conv_mfma.h and the bitfields of ConvArgs disagree");
+
+// What fill_conv_args narrows into the bitfields of ConvArgs, checked at full width first: every path that fills kernel arguments
+// (launch_conv / conv_describe, the grouped launch, the patch kernel) calls this before it does.
+inline int check_conv_fields(const ConvLaunch& c) {
+  RON_REQUIRE(c.in.N >= 1 && c.in.H >= 1 && c.in.W >= 1 && c.in.C >= 1 && c.Ho >= 1 && c.Wo >= 1 && c.Cout >= 1,
+              "conv: empty tensor (n %d, map %d x %d, cin %d, output %d x %d, cout %d)", c.in.N, c.in.H, c.in.W, c.in.C, c.Ho, c.Wo, c.Cout);
+  RON_REQUIRE(c.kh >= 1 && c.kh <= kConvMaxFilter && c.kw >= 1 && c.kw <= kConvMaxFilter, "conv: filter %d x %d: 1 .. %d", c.kh, c.kw, kConvMaxFilter);
+  RON_REQUIRE(c.stride >= 1 && c.stride <= kConvMaxStride, "conv: stride %d: 1 .. %d", c.stride, kConvMaxStride);
+  RON_REQUIRE(c.dil >= 1 && c.dil <= kConvMaxDilation, "conv: dilation %d: 1 .. %d", c.dil, kConvMaxDilation);
+  RON_REQUIRE(c.up >= 0 && c.up <= kConvMaxStride, "transposed conv: kernel == stride %d: 1 .. %d", c.up, kConvMaxStride);
+  RON_REQUIRE(c.cpad >= 0 && c.cpad <= kConvMaxPad, "conv: padding %d: 0 .. %d", c.cpad, kConvMaxPad);
+  RON_REQUIRE(c.in.pad >= c.cpad && c.in.pad - c.cpad <= kConvMaxInOrigin, "conv: input halo %d, conv padding %d: the halo may be 0 .. %d wider",
+              c.in.pad, c.cpad, kConvMaxInOrigin);
+  RON_REQUIRE(c.out.pad >= 0 && c.out.pad <= kConvMaxOutPad && c.out2.pad >= 0 && c.out2.pad <= kConvMaxOutPad,
+              "conv: output halo %d / %d: 0 .. %d", c.out.pad, c.out2.pad, kConvMaxOutPad);
+  RON_REQUIRE((c.relu == 0 || c.relu == 1) && (c.pool == 0 || c.pool == 1) && (c.out_f32 == 0 || c.out_f32 == 1),
+              "conv: relu %d, pool %d, out_f32 %d: each 0 or 1", c.relu, c.pool, c.out_f32);
+  return RON_OK;
+}
+
+// Geometry / pointers of a launch -> kernel arguments (tiling fields are the caller's).  check_conv_fields(c) first.
 inline void fill_conv_args(const ConvLaunch& c, ConvArgs* out) {
   ConvArgs a = ConvArgs();
   const int chunk = kRowBytes / (int)dtype_size(c.dtype);

@@ -80,6 +80,21 @@ enum {
 inline bool conv_cfg_taps_inner(int cfg) { return cfg == kCfgIgemm256TapsInner || cfg == kCfgIgemm128EarlyTapsInner; }
 inline bool conv_cfg_is_patch(int cfg) { return cfg >= kCfgPatch256 && cfg <= kCfgPatch64; }
 
+// The envelope of the conv entry points: the largest value of each geometry field, which is what its bitfield in the kernel
+// arguments holds (ConvArgs, conv_device.h: a static_assert there ties the two).  A value beyond it would wrap silently - dilation 32
+// to 0, a 17 x 17 filter to 1 x 1 - so it is refused: by check_conv_desc at the descriptor, by check_conv_fields where a ConvLaunch
+// is narrowed into ConvArgs.  The same numbers: ron_conv_desc in include/ron_hip.h, INTEGRATION.md, tests/conv_envelope_cases.py.
+constexpr int kConvMaxFilter = 15;       // kh, kw
+constexpr int kConvMaxStride = 7;        // stride, and kernel == stride of a transposed conv (`up`)
+constexpr int kConvMaxDilation = 31;
+constexpr int kConvMaxPad = 63;          // SAME padding (kh - 1) * dilation / 2
+constexpr int kConvMaxInOrigin = 31;     // input halo beyond the conv's own padding (in.pad - cpad)
+constexpr int kConvMaxOutPad = 15;       // halo of an output view
+constexpr int kConvMaxTileOrder = 63;    // ConvArgs::m_fastest
+// The descriptor of a single-operator entry point, before any arithmetic on it: sizes, filter, stride and dilation >= 1 and inside
+// the envelope, the flags 0 or 1.  RON_OK, or RON_ERR_INVALID with the message set.
+int check_conv_desc(const ron_conv_desc* d);
+
 int launch_conv(const ConvLaunch& c, hipStream_t stream);
 // what launch_conv would do with `c`: out = {tile configuration (kCfg*), split-K factor, tile order (ConvArgs::m_fastest), K order (taps_inner)}
 int conv_describe(const ConvLaunch& c, int out[4]);

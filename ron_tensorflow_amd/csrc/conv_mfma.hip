@@ -69,6 +69,22 @@ int conv_k_chunk(int dtype) { return kRowBytes / (int)dtype_size(dtype); }
 int conv_n_tile(int cout) { return cout <= 64 ? 64 : 128; }
 int conv_num_cfgs() { return kNumCfgs; }
 
+int check_conv_desc(const ron_conv_desc* d) {
+  RON_REQUIRE(d != nullptr, "NULL descriptor");
+  RON_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1 && d->cin >= 1 && d->cout >= 1, "conv: empty tensor (n %d, map %d x %d, cin %d, cout %d)",
+              d->n, d->h, d->w, d->cin, d->cout);
+  RON_REQUIRE(d->kh >= 1 && d->kh <= kConvMaxFilter && d->kw >= 1 && d->kw <= kConvMaxFilter, "conv: filter %d x %d: 1 .. %d", d->kh, d->kw, kConvMaxFilter);
+  RON_REQUIRE(d->stride >= 1 && d->stride <= kConvMaxStride, "conv: stride %d: 1 .. %d", d->stride, kConvMaxStride);
+  RON_REQUIRE(d->dilation >= 1 && d->dilation <= kConvMaxDilation, "conv: dilation %d: 1 .. %d", d->dilation, kConvMaxDilation);
+  RON_REQUIRE((d->relu == 0 || d->relu == 1) && (d->pool == 0 || d->pool == 1) && (d->transpose == 0 || d->transpose == 1),
+              "conv: relu %d, pool %d, transpose %d: each 0 or 1", d->relu, d->pool, d->transpose);
+  if (!d->transpose && d->stride == 1) {
+    const int pad = (std::max(d->kh, d->kw) - 1) * d->dilation / 2;
+    RON_REQUIRE(pad <= kConvMaxPad, "conv: %d x %d filter at dilation %d: SAME padding %d, at most %d", d->kh, d->kw, d->dilation, pad, kConvMaxPad);
+  }
+  return RON_OK;
+}
+
 static bool igemm_is256(int cfg) { return cfg == kCfgIgemm256 || cfg == kCfgIgemm256TapsInner; }
 static int igemm_bm(int cfg) { return (igemm_is256(cfg) || cfg == kCfgIgemm256x128) ? 256 : 128; }
 static int igemm_bn(int cfg) { return igemm_is256(cfg) ? 256 : (cfg == kCfgIgemm128x64 ? 64 : 128); }
@@ -290,6 +306,10 @@ int launch_conv(const ConvLaunch& c, hipStream_t stream) {
 
 static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out) {
   ConvArgs& a = *a_out;
+  {
+    const int rc = check_conv_fields(c);      // before the pickers divide by any of it
+    if (rc != RON_OK) return rc;
+  }
   int cfg = c.cfg >= 0 ? c.cfg : conv_pick_cfg(c);
   *cfg_out = cfg;
   RON_REQUIRE(cfg >= 0 && cfg < kNumCfgs, "conv: tile config %d out of range [0, %d)", cfg, kNumCfgs);
@@ -339,7 +359,9 @@ static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out) {
     a.partial = (float*)c.scratch;
     if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
   }
-  a.m_fastest = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, a.KT);
+  const int tile_order = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, a.KT);
+  RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "conv: tile order %d: 0 .. %d", tile_order, kConvMaxTileOrder);
+  a.m_fastest = tile_order;
   a.pos_major = pick_pos_major(c, cfg, BM);
   a.taps_inner = conv_cfg_taps_inner(cfg) ? 1 : 0;
   // the 256 x 128 tile: taps innermost by the rule of the other tiles (stride-1 filters that neither split K nor skip filter rows)
@@ -584,6 +606,10 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
     RON_REQUIRE(c.Npad % BN == 0 && !c.pool, "conv group: Npad %d not a multiple of the N tile %d, or a fused pool", c.Npad, BN);
     if (c.up > 0) RON_REQUIRE(c.up_cout % BN == 0, "transposed conv: channels per tap %d not a multiple of %d", c.up_cout, BN);
     ConvArgs& a = g.op[k];
+    {
+      const int rc = check_conv_fields(c);
+      if (rc != RON_OK) return rc;
+    }
     fill_conv_args(c, &a);
     RON_REQUIRE((int64_t)c.Npad * a.K * esz == c.wgt_bytes, "conv group: packed weight size mismatch");
     a.tiles_n = c.Npad / BN;
@@ -597,7 +623,9 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
       if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
       else { used += need; any_split = true; }
     }
-    a.m_fastest = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, group_4w ? a.kt_split : 0);
+    const int tile_order = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, group_4w ? a.kt_split : 0);
+    RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "conv group: tile order %d: 0 .. %d", tile_order, kConvMaxTileOrder);
+    a.m_fastest = tile_order;
     a.pos_major = pick_pos_major(c, mcfg, BM);
     // K order of the member, by the rules of a launch of its own (conv_pick_cfg): taps innermost for stride-1 filters that neither
     // split K nor skip filter rows - on the 256 x 256 tile where the long columns are at most two tiles wide, on 128 x 128 always

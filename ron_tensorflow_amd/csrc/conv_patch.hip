@@ -498,6 +498,10 @@ static int patch_args(const ConvLaunch& c, int cfg, PatchArgs* out, int* grid) {
   const int esz = (int)dtype_size(c.dtype);
   RON_REQUIRE(c.in.bytes > 0 && c.in.bytes < (int64_t)1 << 32 && c.wgt_bytes < (int64_t)1 << 32, "conv: allocations must be < 4 GiB");
   RON_REQUIRE(c.out.pixels() * c.out.cstride < (int64_t)1 << 31, "conv: output too large for 32-bit offsets");
+  {
+    const int rc = check_conv_fields(c);
+    if (rc != RON_OK) return rc;
+  }
   PatchArgs a = PatchArgs();
   fill_conv_args(c, &a.c);
   RON_REQUIRE((int64_t)c.Npad * a.c.K * esz == c.wgt_bytes, "conv: packed weight size mismatch");

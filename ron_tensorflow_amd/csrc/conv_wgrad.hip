@@ -446,13 +446,14 @@ struct BackwardPlan {
 };
 
 int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
-  RON_REQUIRE(d != nullptr, "NULL descriptor");
+  if (int rc0 = check_conv_desc(d)) return rc0;       // sizes, filter, stride, dilation inside the envelope of the forward; flags 0 or 1
   RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv backward: dtype %d: bf16 or fp16 only (fp32 and f16x3 have no backward)", d->dtype);
   RON_REQUIRE(d->transpose == 0 && d->pool == 0 && d->center_from == 0 && d->in_cstride == 0 && d->in_coff == 0 && d->tile_cfg == -1,
               "conv backward: a plain convolution (transpose, pool, center_from, in_cstride, in_coff = 0, tile_cfg = -1)");
   RON_REQUIRE(d->stride == 1, "conv backward: stride %d: stride-1 SAME convolutions only", d->stride);
   RON_REQUIRE(d->kh == d->kw && (d->kh == 1 || d->kh == 3), "conv backward: filter %d x %d: 1 x 1 or 3 x 3 only", d->kh, d->kw);
-  RON_REQUIRE(d->dilation >= 1, "conv backward: dilation %d", d->dilation);
+  RON_REQUIRE(d->dilation >= 1 && d->dilation <= kConvMaxDilation, "conv backward: dilation %d: 1 .. %d (the data gradient is a forward launch)",
+              d->dilation, kConvMaxDilation);
   RON_REQUIRE(d->n > 0 && d->h > 0 && d->w > 0 && d->cout >= 1, "conv backward: empty tensor");
   RON_REQUIRE(d->cin > 0 && d->cin % 64 == 0, "conv backward: cin %d must be a multiple of 64 (the 3-channel stem is out of scope)", d->cin);
   RON_REQUIRE(d->splitk == -1 || d->splitk >= 1, "conv backward: pixel split %d (-1 = by shape, 1 = off, S = forced)", d->splitk);
@@ -752,7 +753,7 @@ struct K2Plan {
 };
 
 int plan_k2s2(const ron_conv_desc* d, K2Plan* P) {
-  RON_REQUIRE(d != nullptr, "NULL descriptor");
+  if (int rc0 = check_conv_desc(d)) return rc0;       // flags 0 or 1, sizes >= 1
   RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv k2s2 backward: dtype %d: bf16 or fp16 only (fp32 and f16x3 have no backward)", d->dtype);
   RON_REQUIRE(d->pool == 0 && d->center_from == 0 && d->in_cstride == 0 && d->in_coff == 0 && d->tile_cfg == -1,
               "conv k2s2 backward: a plain operator (pool, center_from, in_cstride, in_coff = 0, tile_cfg = -1)");

@@ -36,7 +36,15 @@ struct ConvSetup {
 // Packs weights like ron_finalize_weights does, uploads them and allocates the halo tensors.
 int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool with_residual, ConvSetup* S) {
   using namespace ron;
+  // the descriptor itself, before any arithmetic on it (a stride of 0 used to reach the divisions below)
+  {
+    const int rc = check_conv_desc(d);
+    if (rc != RON_OK) return rc;
+  }
   RON_REQUIRE(d->dtype >= 0 && d->dtype <= RON_DTYPE_F16X3, "bad dtype");
+  RON_REQUIRE(d->kh == d->kw, "conv: filter %d x %d: square filters only (one SAME padding for both axes)", d->kh, d->kw);
+  // an even filter's SAME padding is one pixel wider behind than in front: the shared halo has one width, so it is refused
+  RON_REQUIRE(d->transpose || d->stride > 1 || (d->kh & 1), "conv: %d x %d filter at stride 1: odd filters only", d->kh, d->kw);
   const int esz = (int)dtype_size(d->dtype);
   const int chunk = conv_k_chunk(d->dtype);
   S->is_c3 = (!d->transpose && d->cin == 3 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->dilation == 1);
@@ -184,6 +192,7 @@ extern "C" int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, con
                                      float* y_full, void* stream) {
   using namespace ron;
   RON_REQUIRE(d && x && w && y_pooled && y_full, "NULL argument");
+  if (int rc0 = check_conv_desc(d)) return rc0;
   RON_REQUIRE(d->pool && !d->transpose && d->stride == 1 && d->cin % conv_k_chunk(d->dtype) == 0, "two-output pooled convolution: a plain stride-1 convolution with pool set");
   hipStream_t s = (hipStream_t)stream;
   ConvSetup S;
@@ -208,6 +217,7 @@ extern "C" int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]) {
   using namespace ron;
   RON_REQUIRE(d != nullptr && out != nullptr, "NULL argument");
   RON_REQUIRE(!(d->cin == 3), "the 3-channel stem has a kernel of its own");
+  if (int rc0 = check_conv_desc(d)) return rc0;       // (before the weights are sized from it)
   const size_t wn = (size_t)d->kh * d->kw * d->cin * d->cout;
   std::vector<float> w(wn, 0.f);
   ConvSetup S;
@@ -226,6 +236,7 @@ extern "C" int ron_conv2d_heads_nhwc(const ron_conv_desc* d, int split_first, co
                                      float* y_first, float* y_second, void* stream) {
   using namespace ron;
   RON_REQUIRE(d && x && w && y_first && y_second, "NULL argument");
+  if (int rc0 = check_conv_desc(d)) return rc0;
   RON_REQUIRE(!d->transpose && !d->pool && d->center_from == 0 && d->stride == 1 && d->cin % conv_k_chunk(d->dtype) == 0,
               "two-output convolution: a plain stride-1 convolution");
   RON_REQUIRE(split_first > 0 && split_first < d->cout, "two-output convolution: %d of %d channels in the first output", split_first, d->cout);
@@ -276,6 +287,7 @@ extern "C" int ron_conv2d_bench(const ron_conv_desc* d, int warmup, int iters, f
   using namespace ron;
   RON_REQUIRE(d && ms_per_launch && iters > 0 && warmup >= 0, "bad argument");
   RON_REQUIRE(!(d->cin == 3), "the 3-channel stem is not benchmarked through this entry");
+  if (int rc0 = check_conv_desc(d)) return rc0;
   const size_t wn = (size_t)d->kh * d->kw * d->cin * d->cout;
   std::vector<float> w(wn), b(d->cout);
   uint32_t st = 12345u;

@@ -451,14 +451,14 @@ def conv2d_nhwc(x, w, bias=None, residual=None, stride=1, dilation=1, relu=True,
     return y
 
 
-def conv2d_pool2_nhwc(x, w, bias=None, relu=True, dtype='bf16', tile_cfg=-1):
+def conv2d_pool2_nhwc(x, w, bias=None, relu=True, dtype='bf16', tile_cfg=-1, dilation=1):
     """3x3-style stride-1 convolution with the fused SAME 2x2 pool AND the un-pooled map from the same launch (ron_conv2d_pool2_nhwc:
     what the graph does for conv4_3 / conv5_3 with fuse_pools): (pooled [N,ceil(H/2),ceil(W/2),Cout], full [N,H,W,Cout])."""
     x = x.contiguous()
     w = np.ascontiguousarray(w, dtype=np.float32)
     n, h, wd, cin = x.shape
     kh, kw, _, cout = w.shape
-    d = _lib.ConvDesc(n, h, wd, cin, cout, kh, kw, 1, 1, int(relu), 0, _lib.DTYPES[dtype], tile_cfg, 0, 0, 1, 1, 0)
+    d = _lib.ConvDesc(n, h, wd, cin, cout, kh, kw, 1, dilation, int(relu), 0, _lib.DTYPES[dtype], tile_cfg, 0, 0, 1, 1, 0)
     yp = torch.empty((n, (h + 1) // 2, (wd + 1) // 2, cout), dtype=torch.float32, device=x.device)
     yf = torch.empty((n, h, wd, cout), dtype=torch.float32, device=x.device)
     b = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)

@@ -26,7 +26,7 @@ def inputs(kind, case, seed=0):
     lattice: x, dy integers in [-2, 2]; y = relu(integers in [-1, 3]), 40 % exact zeros; w in {-1, 0, 1} with at most 64 non-zeros per
     INPUT channel (the data gradient sums over taps and output channels: conv_bounds.lattice_weights bounds the non-zeros of the
     forward's output channels, so it is drawn for the swapped shape and transposed): |dx| <= 2 * 64, every partial sum an integer."""
-    n, h, w, cin, cout, k, _ = CASES[case]
+    n, h, w, cin, cout, k, _ = CASES[case] if isinstance(case, str) else case      # (a case of another table: tests/conv_envelope_cases.py)
     rs = np.random.RandomState(100 + seed)
     if kind == 'lattice':
         x = rs.randint(-2, 3, size=(n, h, w, cin)).astype(np.float32)

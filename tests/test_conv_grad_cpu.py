@@ -143,6 +143,9 @@ bad = {
     'f16x3': desc(*b, dtype='f16x3'),
     'tile_cfg': desc(*b, tile_cfg=1),
     'splitk 0': desc(*b, splitk=0),
+    'dilation 32': desc(2, 40, 40, 64, 24, 3, 32),          # the data gradient is a forward launch: its dilation field ends at 31
+    'dilation 0': desc(2, 5, 7, 64, 24, 3, 0),
+    '1x1 dilation 32': desc(2, 5, 7, 64, 24, 1, 32),
 }
 for name, d in bad.items():
     nbytes = L.ron_conv2d_backward_workspace_bytes(C.byref(d))
@@ -198,7 +201,7 @@ def test_accepted_descriptors_plan_in_the_dry_run(dry_run):
 
 def test_refusals(dry_run):
     want = ['stride 2', 'transpose', 'pool', 'k = 5', 'cin = 96', 'cin = 3', 'fp32', 'f16x3', 'relu with NULL y', 'short workspace']
-    for name in want + ['tile_cfg', 'splitk 0', 'misaligned dy']:
+    for name in want + ['tile_cfg', 'splitk 0', 'misaligned dy', 'dilation 32', 'dilation 0', '1x1 dilation 32']:
         nbytes, msg_b, rc, msg = dry_run['refused'][name]
         assert nbytes == -1 and msg_b, (name, nbytes, msg_b)
         assert rc == -1 and msg, '%s: status %d (%s), RON_ERR_INVALID (-1) expected' % (name, rc, msg)

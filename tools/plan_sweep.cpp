@@ -235,6 +235,81 @@ static int op_backward_arguments() {
   return 0;
 }
 
+// The argument envelope of ron_conv_desc (include/ron_hip.h): for every field limit - 1 and limit plan, limit + 1 is refused, through
+// ron_conv_plan and the backward's workspace query; zeros, negatives and flags other than 0 / 1 are refused before any arithmetic on
+// them (a stride of 0 used to reach a division).  The shapes are those of tests/conv_envelope_cases.py.
+static int conv_envelope() {
+  auto desc = [](int n, int h, int w, int cin, int cout, int k, int stride, int dil, int transpose, int dtype) {
+    ron_conv_desc d;
+    memset(&d, 0, sizeof d);
+    d.n = n; d.h = h; d.w = w; d.cin = cin; d.cout = cout; d.kh = d.kw = k; d.stride = stride; d.dilation = dil;
+    d.relu = 1; d.transpose = transpose; d.dtype = dtype; d.tile_cfg = -1; d.splitk = -1;
+    return d;
+  };
+  int32_t plan[4];
+  for (int dtype : {(int)RON_DTYPE_F32, (int)RON_DTYPE_BF16, (int)RON_DTYPE_F16, (int)RON_DTYPE_F16X3}) {
+    struct Row { ron_conv_desc d; bool ok; };
+    const Row rows[] = {
+        {desc(1, 32, 32, 64, 64, 3, 1, 30, 0, dtype), true},   {desc(1, 32, 32, 64, 64, 3, 1, 31, 0, dtype), true},   {desc(1, 40, 40, 64, 64, 3, 1, 32, 0, dtype), false},
+        {desc(1, 8, 9, 64, 64, 13, 1, 1, 0, dtype), true},     {desc(1, 8, 9, 64, 64, 15, 1, 1, 0, dtype), true},     {desc(1, 18, 18, 64, 64, 17, 1, 1, 0, dtype), false},
+        {desc(1, 16, 16, 64, 64, 16, 1, 1, 0, dtype), false},  {desc(1, 16, 16, 64, 64, 16, 16, 1, 0, dtype), false},
+        {desc(2, 12, 18, 64, 64, 6, 6, 1, 0, dtype), true},    {desc(2, 14, 21, 64, 64, 7, 7, 1, 0, dtype), true},    {desc(2, 16, 16, 64, 64, 8, 8, 1, 0, dtype), false},
+        {desc(1, 2, 3, 64, 128, 6, 6, 1, 1, dtype), true},     {desc(1, 2, 3, 64, 128, 7, 7, 1, 1, dtype), true},     {desc(1, 2, 2, 64, 128, 8, 8, 1, 1, dtype), false},
+        {desc(1, 3, 64, 64, 64, 5, 1, 31, 0, dtype), true},    {desc(1, 3, 64, 64, 64, 7, 1, 21, 0, dtype), true},    {desc(1, 3, 72, 64, 64, 7, 1, 22, 0, dtype), false},
+        {desc(1, 3, 72, 64, 64, 5, 1, 32, 0, dtype), false},   {desc(2, 28, 28, 64, 128, 7, 1, 9, 0, dtype), true},   {desc(1, 30, 16, 64, 64, 15, 1, 4, 0, dtype), true},
+        {desc(1, 8, 8, 64, 64, 2, 1, 1, 0, dtype), false},     {desc(1, 8, 8, 64, 64, 4, 1, 1, 0, dtype), false},
+    };
+    for (const Row& r : rows) {
+      const int rc = ron_conv_plan(&r.d, plan);
+      if (rc != (r.ok ? RON_OK : RON_ERR_INVALID)) {
+        fprintf(stderr, "conv envelope: %d x %d stride %d dilation %d transpose %d dtype %d: status %d\n", r.d.kh, r.d.kw, r.d.stride, r.d.dilation, r.d.transpose, dtype, rc);
+        return 1;
+      }
+      if (r.ok && !(plan[2] >= 0 && plan[2] <= 63)) return 1;
+      for (int pool : {0, 1}) {                     // the fused pool where it applies: plain stride-1 convolutions
+        if (r.d.transpose || r.d.stride != 1) continue;
+        ron_conv_desc dp = r.d;
+        dp.pool = pool;
+        if (ron_conv_plan(&dp, plan) != (r.ok ? RON_OK : RON_ERR_INVALID)) return 1;
+      }
+    }
+    // zeros, negatives, flags: one field at a time on a plain 3x3
+    const ron_conv_desc base = desc(1, 8, 8, 64, 64, 3, 1, 1, 0, dtype);
+    for (int v : {0, -1, -64, 2, INT32_MIN}) {
+      ron_conv_desc bad[12];
+      for (ron_conv_desc& b : bad) b = base;
+      bad[0].n = v; bad[1].h = v; bad[2].w = v; bad[3].cin = v; bad[4].cout = v; bad[5].kh = bad[5].kw = v; bad[6].stride = v; bad[7].dilation = v;
+      bad[8].relu = v; bad[9].pool = v; bad[10].transpose = v; bad[11].kh = v;
+      for (int i = 0; i < 12; ++i) {
+        if (v == 2 && i <= 4) continue;                                    // (a size of 2 is a size)
+        if (v == 2 && i == 7) continue;                                    // (... and a dilation of 2 a dilation)
+        if (v == 0 && i >= 8 && i <= 10) continue;                         // (a flag of 0 is a flag)
+        if (ron_conv_plan(&bad[i], plan) != RON_ERR_INVALID) { fprintf(stderr, "conv envelope: field %d = %d accepted\n", i, v); return 1; }
+        if (ron_conv2d_backward_workspace_bytes(&bad[i]) != -1) { fprintf(stderr, "conv envelope: backward: field %d = %d accepted\n", i, v); return 1; }
+        if (ron_conv2d_k2s2_backward_workspace_bytes(&bad[i]) != -1) return 1;
+      }
+    }
+  }
+  // the backward's workspace query and plan at the last dilation, 3x3 and 1x1, and one beyond
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+    for (int k : {1, 3}) {
+      for (int dil : {30, 31, 32}) {
+        ron_conv_desc d = desc(k == 1 ? 2 : 1, k == 1 ? 5 : 40, k == 1 ? 7 : 40, 64, k == 1 ? 24 : 64, k, 1, dil, 0, dtype);
+        const int64_t bytes = ron_conv2d_backward_workspace_bytes(&d);
+        if (dil > 31) {
+          if (bytes != -1 || ron_conv2d_backward_nhwc(&d, f, f, f, f, f, f, f, ws, (int64_t)1 << 40, nullptr) != RON_ERR_INVALID) return 1;
+          continue;
+        }
+        if (bytes <= 0 || bytes % 256 != 0) return 1;
+        CHECK(ron_conv2d_backward_nhwc(&d, f, f, f, f, f, f, f, ws, bytes, nullptr));
+      }
+    }
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (getenv("RON_PLAN_ONLY") == nullptr) {
     fprintf(stderr, "plan_sweep: run with RON_PLAN_ONLY=1 (a dry run: this binary holds no device code)\n");
@@ -294,6 +369,10 @@ int main(int argc, char** argv) {
   }
   if (op_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_maxpool2x2_backward_nhwc / ron_conv2d_k2s2_backward_nhwc planning / argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (conv_envelope()) {
+    fprintf(stderr, "plan_sweep: the argument envelope of ron_conv_desc: %s\n", ron_last_error());
     return 1;
   }
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
