@@ -430,19 +430,119 @@ int launch_conv_wgrad(const WgradLaunch& c, hipStream_t stream) {
   return c.dtype == RON_DTYPE_BF16 ? launch_wgrad_dtype<true>(c, p, stream) : launch_wgrad_dtype<false>(c, p, stream);
 }
 
-// ---- ron_conv2d_backward_nhwc ------------------------------------------------------------------------------------------------------------
+// ---- what the two backward entry points share: the tail of the plan, the checks of a call, the three launch steps ----------------------
 namespace {
 
-// Everything the entry point decides on the host: the descriptor's checks and the carving of the workspace (offsets in bytes).
-struct BackwardPlan {
-  int pad = 0, cop = 0, npad = 0, taps = 0;
-  int64_t pixels = 0, rows = 0, guard = 0;      // halo pixels; rounded up to the K step; guard pixels of x on each side
+// What both operators decide on the host behind their own descriptor checks (offsets and sizes in bytes).  The operator fills rows,
+// sum_cols, conv and wg and carves its own operand buffers; finish_plan does the rest.
+struct BackwardCore {
+  int64_t rows = 0;         // rows of the packed operands: the pixels rounded up to the K step
+  int sum_cols = 0;         // columns of the tensor the bias gradient sums
   int chunks = 0;
   int64_t chunk_rows = 0;
-  int64_t off_dz = 0, off_x = 0, off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
-  int64_t dz_bytes = 0, x_bytes = 0, w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
+  int64_t off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
+  int64_t w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
   ConvLaunch conv;          // the data gradient (pointers unset)
   WgradLaunch wg;           // the weight gradient (pointers unset)
+};
+
+int64_t carve(BackwardCore* P, int64_t bytes) {
+  const int64_t o = P->total;
+  P->total += align_up(bytes, 256);
+  return o;
+}
+
+int finish_plan(BackwardCore* P) {
+  P->conv.out.bytes = P->dx_bytes;
+  P->conv.wgt_bytes = P->w_bytes;
+  P->sk_bytes = conv_scratch_bytes(P->conv);
+  P->slab_bytes = conv_wgrad_scratch_bytes(P->wg);
+  if (P->slab_bytes < 0) return RON_ERR_INVALID;
+  // bias gradient: at most 512 chunks of >= 32 rows
+  P->chunk_rows = std::max<int64_t>(32, (P->rows + 511) / 512);
+  P->chunks = (int)((P->rows + P->chunk_rows - 1) / P->chunk_rows);
+  P->off_w = carve(P, P->w_bytes);
+  P->off_bias = carve(P, (int64_t)P->conv.Npad * 4);
+  P->off_dx = carve(P, P->dx_bytes);
+  P->off_sk = carve(P, P->sk_bytes);
+  P->off_slab = carve(P, P->slab_bytes);
+  P->off_part = carve(P, (int64_t)P->chunks * P->sum_cols * 4);
+  return RON_OK;
+}
+
+// the checks of a call behind its plan; `what` starts every message, `sizer` is the entry that gives the workspace's size
+int check_backward_call(const char* what, const char* sizer, const ron_conv_desc* d, const BackwardCore& P, const float* x,
+                        const float* w, const float* y, const float* dy, const float* dx, const float* dw, void* workspace,
+                        int64_t workspace_bytes) {
+  RON_REQUIRE(dy != nullptr, "%s: dy is NULL", what);
+  RON_REQUIRE(!d->relu || y != nullptr, "%s: relu is set and y is NULL (the mask is y > 0)", what);
+  RON_REQUIRE(dx == nullptr || w != nullptr, "%s: dx needs w", what);
+  RON_REQUIRE(dw == nullptr || x != nullptr, "%s: dw needs x", what);
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (%s)", what,
+              (long long)workspace_bytes, (long long)P.total, sizer);
+  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
+  RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "%s: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)", what);
+  if (dx != nullptr) {
+    // what launch_conv would refuse is refused here, before anything is enqueued
+    ConvLaunch c = P.conv;
+    c.in.base = workspace; c.out.base = workspace; c.wgt = workspace; c.bias = static_cast<const float*>(workspace);
+    if (P.sk_bytes > 0) { c.scratch = workspace; c.scratch_bytes = P.sk_bytes; }
+    int o[4];
+    if (int rc = conv_describe(c, o)) return rc;
+  }
+  return RON_OK;
+}
+
+// dense fp32 [n,h,w,csrc] -> `rows` + 2 `guard` pixels of cdst channels in the halo geometry of `pad` (0: a dense tensor)
+template <bool BF16>
+int launch_pack_halo(const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc, int cdst,
+                     int64_t guard, hipStream_t s) {
+  PackArgs a;
+  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
+  a.rows = rows + 2 * guard; a.guard = guard;
+  a.N = n; a.H = h; a.W = w; a.pad = pad; a.Csrc = csrc; a.Cdst = cdst;
+  RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+// the data gradient behind the weights' pack: zero bias, the forward launch over dz; *out is the halo tensor it wrote
+int launch_data_grad(const BackwardCore& P, void* dzbuf, char* ws, hipStream_t s, TensorView* out) {
+  RON_HIP_CHECK(dev_memset_async(ws + P.off_bias, 0, (size_t)P.conv.Npad * 4, s));
+  ConvLaunch c = P.conv;
+  c.in.base = dzbuf; c.out.base = ws + P.off_dx;
+  c.wgt = ws + P.off_w; c.bias = reinterpret_cast<const float*>(ws + P.off_bias);
+  if (P.sk_bytes > 0) { c.scratch = ws + P.off_sk; c.scratch_bytes = P.sk_bytes; }
+  *out = c.out;
+  return launch_conv(c, s);
+}
+
+// the weight gradient of the packed operands
+int launch_weight_grad(const BackwardCore& P, void* xbase, void* dzbase, float* dw, char* ws, hipStream_t s) {
+  WgradLaunch g = P.wg;
+  g.x.base = xbase;
+  g.dz.base = dzbase;
+  g.dw = dw;
+  if (P.slab_bytes > 0) { g.scratch = ws + P.off_slab; g.scratch_bytes = P.slab_bytes; }
+  return launch_conv_wgrad(g, s);
+}
+
+// pass 1 of the bias gradient: the chunks' column sums of dz; returns them ([chunks][sum_cols]) for the operator's second pass
+template <bool BF16>
+int launch_colsum(const BackwardCore& P, const void* dzbuf, char* ws, hipStream_t s, const float** part) {
+  *part = reinterpret_cast<const float*>(ws + P.off_part);
+  RON_LAUNCH(conv_bwd_colsum_kernel<BF16>, dim3(P.chunks, P.sum_cols / 64), dim3(256), 0, s, static_cast<const unsigned short*>(dzbuf),
+             (long long)P.rows, P.sum_cols, (long long)P.chunk_rows, reinterpret_cast<float*>(ws + P.off_part));
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+// ---- ron_conv2d_backward_nhwc ------------------------------------------------------------------------------------------------------------
+// Everything the entry point decides on the host: the descriptor's checks and the carving of the workspace.
+struct BackwardPlan : BackwardCore {
+  int pad = 0, cop = 0, npad = 0, taps = 0;
+  int64_t pixels = 0, guard = 0;                // halo pixels; guard pixels of x on each side
+  int64_t off_dz = 0, off_x = 0;
 };
 
 int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
@@ -460,65 +560,37 @@ int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
   const int esz = 2;
   P->pad = (d->kh - 1) * d->dilation / 2;
   P->cop = (int)align_up(d->cout, 64);
+  P->sum_cols = P->cop;
   P->taps = d->kh * d->kw;
   P->npad = (int)align_up(d->cin, conv_n_tile(d->cin));
   P->pixels = TensorView::halo_pixels(d->n, d->h, d->w, P->pad);
   P->rows = align_up(P->pixels, kWgStep);
   P->guard = (int64_t)P->pad * (d->w + P->pad) + P->pad;
-  P->dz_bytes = P->rows * P->cop * esz;
-  P->x_bytes = (P->rows + 2 * P->guard) * d->cin * esz;
+  const int64_t dz_bytes = P->rows * P->cop * esz;
+  const int64_t x_bytes = (P->rows + 2 * P->guard) * d->cin * esz;
   P->w_bytes = (int64_t)P->npad * P->taps * P->cop * esz;
   P->dx_bytes = TensorView::halo_pixels(d->n, d->h, d->w, 1) * d->cin * esz;
   const int64_t lim = (int64_t)1 << 31;
-  RON_REQUIRE(P->dz_bytes < lim && P->x_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv backward: a packed tensor would reach 2 GiB");
+  RON_REQUIRE(dz_bytes < lim && x_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv backward: a packed tensor would reach 2 GiB");
   // the data gradient as a forward launch over dz
   ConvLaunch& c = P->conv;
   c.dtype = d->dtype;
   c.in.N = d->n; c.in.H = d->h; c.in.W = d->w; c.in.C = P->cop; c.in.cstride = P->cop; c.in.pad = P->pad;
   c.in.bytes = P->pixels * P->cop * esz;
   c.out.N = d->n; c.out.H = d->h; c.out.W = d->w; c.out.C = d->cin; c.out.cstride = d->cin; c.out.pad = 1;
-  c.out.bytes = P->dx_bytes;
-  c.wgt_bytes = P->w_bytes;
   c.Cout = d->cin; c.Npad = P->npad;
   c.kh = d->kh; c.kw = d->kw; c.stride = 1; c.dil = d->dilation; c.cpad = P->pad;
   c.relu = 0; c.Ho = d->h; c.Wo = d->w;
   c.splitk = -1;
-  P->sk_bytes = conv_scratch_bytes(c);
   // the weight gradient
   WgradLaunch& g = P->wg;
   g.dtype = d->dtype;
   g.x = c.in; g.x.C = d->cin; g.x.cstride = d->cin; g.x.bytes = P->pixels * d->cin * esz;
   g.dz = c.in;
   g.kh = d->kh; g.kw = d->kw; g.dil = d->dilation; g.Cout = d->cout; g.guard = P->guard; g.splitk = d->splitk;
-  P->slab_bytes = conv_wgrad_scratch_bytes(g);
-  if (P->slab_bytes < 0) return RON_ERR_INVALID;
-  // bias gradient: at most 512 chunks of >= 32 rows
-  P->chunk_rows = std::max<int64_t>(32, (P->rows + 511) / 512);
-  P->chunks = (int)((P->rows + P->chunk_rows - 1) / P->chunk_rows);
-  int64_t at = 0;
-  auto carve = [&](int64_t bytes) { const int64_t o = at; at += align_up(bytes, 256); return o; };
-  P->off_dz = carve(P->dz_bytes);
-  P->off_x = carve(P->x_bytes);
-  P->off_w = carve(P->w_bytes);
-  P->off_bias = carve((int64_t)P->npad * 4);
-  P->off_dx = carve(P->dx_bytes);
-  P->off_sk = carve(P->sk_bytes);
-  P->off_slab = carve(P->slab_bytes);
-  P->off_part = carve((int64_t)P->chunks * P->cop * 4);
-  P->total = at;
-  return RON_OK;
-}
-
-template <bool BF16>
-int launch_pack_halo(const float* src, const float* mask, void* out, const BackwardPlan& P, const ron_conv_desc* d, int csrc, int cdst,
-                     int64_t guard, hipStream_t s) {
-  PackArgs a;
-  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
-  a.rows = P.rows + 2 * guard; a.guard = guard;
-  a.N = d->n; a.H = d->h; a.W = d->w; a.pad = P.pad; a.Csrc = csrc; a.Cdst = cdst;
-  RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
-  RON_HIP_CHECK(ron::launch_error());
-  return RON_OK;
+  P->off_dz = carve(P, dz_bytes);
+  P->off_x = carve(P, x_bytes);
+  return finish_plan(P);
 }
 
 template <bool BF16>
@@ -526,36 +598,26 @@ int run_backward(const ron_conv_desc* d, const BackwardPlan& P, const float* x, 
                  float* dx, float* dw, float* dbias, char* ws, hipStream_t s) {
   int rc;
   void* dzbuf = ws + P.off_dz;
-  if ((rc = launch_pack_halo<BF16>(dy, d->relu ? y : nullptr, dzbuf, P, d, d->cout, P.cop, 0, s))) return rc;
+  if ((rc = launch_pack_halo<BF16>(dy, d->relu ? y : nullptr, dzbuf, P.rows, d->n, d->h, d->w, P.pad, d->cout, P.cop, 0, s))) return rc;
   if (dx != nullptr) {
     WpackArgs wa;
     wa.w = w; wa.out = reinterpret_cast<unsigned short*>(ws + P.off_w);
     wa.taps = P.taps; wa.cin = d->cin; wa.cout = d->cout; wa.cop = P.cop; wa.npad = P.npad;
     RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
     RON_HIP_CHECK(ron::launch_error());
-    RON_HIP_CHECK(dev_memset_async(ws + P.off_bias, 0, (size_t)P.npad * 4, s));
-    ConvLaunch c = P.conv;
-    c.in.base = dzbuf; c.out.base = ws + P.off_dx;
-    c.wgt = ws + P.off_w; c.bias = reinterpret_cast<const float*>(ws + P.off_bias);
-    if (P.sk_bytes > 0) { c.scratch = ws + P.off_sk; c.scratch_bytes = P.sk_bytes; }
-    if ((rc = launch_conv(c, s))) return rc;
-    if ((rc = launch_unpack(c.out, d->dtype, 0, dx, s))) return rc;
+    TensorView out;
+    if ((rc = launch_data_grad(P, dzbuf, ws, s, &out))) return rc;
+    if ((rc = launch_unpack(out, d->dtype, 0, dx, s))) return rc;
   }
   if (dw != nullptr) {
-    if ((rc = launch_pack_halo<BF16>(x, nullptr, ws + P.off_x, P, d, d->cin, d->cin, P.guard, s))) return rc;
-    WgradLaunch g = P.wg;
-    g.x.base = ws + P.off_x + P.guard * d->cin * 2;
-    g.dz.base = dzbuf;
-    g.dw = dw;
-    if (P.slab_bytes > 0) { g.scratch = ws + P.off_slab; g.scratch_bytes = P.slab_bytes; }
-    if ((rc = launch_conv_wgrad(g, s))) return rc;
+    char* xbuf = ws + P.off_x;
+    if ((rc = launch_pack_halo<BF16>(x, nullptr, xbuf, P.rows, d->n, d->h, d->w, P.pad, d->cin, d->cin, P.guard, s))) return rc;
+    if ((rc = launch_weight_grad(P, xbuf + P.guard * d->cin * 2, dzbuf, dw, ws, s))) return rc;
   }
   if (dbias != nullptr) {
-    float* part = reinterpret_cast<float*>(ws + P.off_part);
-    RON_LAUNCH(conv_bwd_colsum_kernel<BF16>, dim3(P.chunks, P.cop / 64), dim3(256), 0, s, static_cast<const unsigned short*>(dzbuf),
-               (long long)P.rows, P.cop, (long long)P.chunk_rows, part);
-    RON_HIP_CHECK(ron::launch_error());
-    RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.cop, dbias);
+    const float* part;
+    if ((rc = launch_colsum<BF16>(P, dzbuf, ws, s, &part))) return rc;
+    RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, part, P.chunks, P.cop, dbias);
     RON_HIP_CHECK(ron::launch_error());
   }
   return RON_OK;
@@ -574,24 +636,10 @@ extern "C" int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, 
                                         float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace ron;
   BackwardPlan P;
-  int rc = plan_backward(d, &P);
-  if (rc != RON_OK) return rc;
-  RON_REQUIRE(dy != nullptr, "conv backward: dy is NULL");
-  RON_REQUIRE(!d->relu || y != nullptr, "conv backward: relu is set and y is NULL (the mask is y > 0)");
-  RON_REQUIRE(dx == nullptr || w != nullptr, "conv backward: dx needs w");
-  RON_REQUIRE(dw == nullptr || x != nullptr, "conv backward: dw needs x");
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "conv backward: workspace of %lld bytes, %lld needed (ron_conv2d_backward_workspace_bytes)",
-              (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "conv backward: the workspace must be 256-byte aligned");
-  RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "conv backward: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)");
-  if (dx != nullptr) {
-    // what launch_conv would refuse is refused here, before anything is enqueued
-    ConvLaunch c = P.conv;
-    c.in.base = workspace; c.out.base = workspace; c.wgt = workspace; c.bias = static_cast<const float*>(workspace);
-    if (P.sk_bytes > 0) { c.scratch = workspace; c.scratch_bytes = P.sk_bytes; }
-    int o[4];
-    if ((rc = conv_describe(c, o))) return rc;
-  }
+  if (int rc = plan_backward(d, &P)) return rc;
+  if (int rc = check_backward_call("conv backward", "ron_conv2d_backward_workspace_bytes", d, P, x, w, y, dy, dx, dw, workspace,
+                                   workspace_bytes))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   return d->dtype == RON_DTYPE_BF16 ? run_backward<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)
@@ -737,19 +785,13 @@ __global__ __launch_bounds__(64) void k2s2_colsum_fold_kernel(const float* parti
   if (lane == 0) dbias[c] = total;
 }
 
-struct K2Plan {
+struct K2Plan : BackwardCore {
   int H = 0, W = 0;             // the coarse grid
   int ca = 0, cz = 0;           // channels of the two packed operands: A (s2d gathered) and Z (dense)
   int npad = 0, nout = 0;       // rows of the packed weights; outputs of the data-gradient launch
   int kconv = 0;                // K of the data-gradient launch = channels of its input
-  int sum_cols = 0;             // columns of the tensor the bias gradient sums
-  int64_t pixels = 0, rows = 0;
-  int chunks = 0;
-  int64_t chunk_rows = 0;
-  int64_t off_a = 0, off_z = 0, off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
-  int64_t a_bytes = 0, z_bytes = 0, w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
-  ConvLaunch conv;
-  WgradLaunch wg;
+  int64_t pixels = 0;
+  int64_t off_a = 0, off_z = 0;
 };
 
 int plan_k2s2(const ron_conv_desc* d, K2Plan* P) {
@@ -779,46 +821,29 @@ int plan_k2s2(const ron_conv_desc* d, K2Plan* P) {
   P->sum_cols = tr ? P->ca : P->cz;
   P->pixels = (int64_t)d->n * P->H * P->W;
   P->rows = align_up(P->pixels, kWgStep);
-  P->a_bytes = P->rows * P->ca * esz;
-  P->z_bytes = P->rows * P->cz * esz;
+  const int64_t a_bytes = P->rows * P->ca * esz, z_bytes = P->rows * P->cz * esz;
   P->w_bytes = (int64_t)P->npad * P->kconv * esz;
   P->dx_bytes = TensorView::halo_pixels(d->n, P->H, P->W, 1) * P->nout * esz;
-  RON_REQUIRE(P->a_bytes < lim && P->z_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv k2s2 backward: a packed tensor would reach 2 GiB");
+  RON_REQUIRE(a_bytes < lim && z_bytes < lim && P->w_bytes < lim && P->dx_bytes < lim, "conv k2s2 backward: a packed tensor would reach 2 GiB");
   // the data gradient: a 1x1 forward launch on the coarse grid
   ConvLaunch& c = P->conv;
   c.dtype = d->dtype;
   c.in.N = d->n; c.in.H = P->H; c.in.W = P->W; c.in.C = P->kconv; c.in.cstride = P->kconv; c.in.pad = 0;
   c.in.bytes = P->pixels * P->kconv * esz;
   c.out.N = d->n; c.out.H = P->H; c.out.W = P->W; c.out.C = P->nout; c.out.cstride = P->nout; c.out.pad = 1;
-  c.out.bytes = P->dx_bytes;
-  c.wgt_bytes = P->w_bytes;
   c.Cout = P->nout; c.Npad = P->npad;
   c.kh = 1; c.kw = 1; c.stride = 1; c.dil = 1; c.cpad = 0;
   c.relu = 0; c.Ho = P->H; c.Wo = P->W;
   c.splitk = -1;
-  P->sk_bytes = conv_scratch_bytes(c);
   // the weight gradient: x := A, dz := Z
   WgradLaunch& g = P->wg;
   g.dtype = d->dtype;
   g.x = c.in; g.x.C = P->ca; g.x.cstride = P->ca; g.x.bytes = P->pixels * P->ca * esz;
   g.dz = c.in; g.dz.C = P->cz; g.dz.cstride = P->cz; g.dz.bytes = P->pixels * P->cz * esz;
   g.kh = 1; g.kw = 1; g.dil = 1; g.Cout = tr ? d->cin : d->cout; g.guard = 0; g.splitk = d->splitk;
-  P->slab_bytes = conv_wgrad_scratch_bytes(g);
-  if (P->slab_bytes < 0) return RON_ERR_INVALID;
-  P->chunk_rows = std::max<int64_t>(32, (P->rows + 511) / 512);
-  P->chunks = (int)((P->rows + P->chunk_rows - 1) / P->chunk_rows);
-  int64_t at = 0;
-  auto carve = [&](int64_t bytes) { const int64_t o = at; at += align_up(bytes, 256); return o; };
-  P->off_a = carve(P->a_bytes);
-  P->off_z = carve(P->z_bytes);
-  P->off_w = carve(P->w_bytes);
-  P->off_bias = carve((int64_t)P->npad * 4);
-  P->off_dx = carve(P->dx_bytes);
-  P->off_sk = carve(P->sk_bytes);
-  P->off_slab = carve(P->slab_bytes);
-  P->off_part = carve((int64_t)P->chunks * P->sum_cols * 4);
-  P->total = at;
-  return RON_OK;
+  P->off_a = carve(P, a_bytes);
+  P->off_z = carve(P, z_bytes);
+  return finish_plan(P);
 }
 
 template <bool BF16>
@@ -827,18 +852,6 @@ int k2s2_pack_s2d(const float* src, const float* mask, void* out, const K2Plan& 
   a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
   a.rows = P.rows; a.N = n; a.H = P.H; a.W = P.W; a.C = c;
   RON_LAUNCH(k2s2_pack_s2d_kernel<BF16>, dim3(grid_for(a.rows * (c / 2))), dim3(256), 0, s, a);
-  RON_HIP_CHECK(ron::launch_error());
-  return RON_OK;
-}
-
-// a dense fp32 tensor on the coarse grid -> [rows][cdst] (conv_bwd_pack_halo_kernel without halo or guard)
-template <bool BF16>
-int k2s2_pack_dense(const float* src, const float* mask, void* out, const K2Plan& P, int n, int csrc, int cdst, hipStream_t s) {
-  PackArgs a;
-  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
-  a.rows = P.rows; a.guard = 0;
-  a.N = n; a.H = P.H; a.W = P.W; a.pad = 0; a.Csrc = csrc; a.Cdst = cdst;
-  RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
 }
@@ -854,7 +867,7 @@ int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const floa
   // dz: the dense operand of the convolution, the gathered one of the transposed convolution
   void* dzbuf = tr ? abuf : zbuf;
   if (tr) rc = k2s2_pack_s2d<BF16>(dy, mask, abuf, P, d->n, d->cout, s);
-  else rc = k2s2_pack_dense<BF16>(dy, mask, zbuf, P, d->n, d->cout, P.cz, s);
+  else rc = launch_pack_halo<BF16>(dy, mask, zbuf, P.rows, d->n, P.H, P.W, 0, d->cout, P.cz, 0, s);
   if (rc) return rc;
   if (dx != nullptr) {
     unsigned short* wout = reinterpret_cast<unsigned short*>(ws + P.off_w);
@@ -868,14 +881,10 @@ int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const floa
       RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
     }
     RON_HIP_CHECK(ron::launch_error());
-    RON_HIP_CHECK(dev_memset_async(ws + P.off_bias, 0, (size_t)P.npad * 4, s));
-    ConvLaunch c = P.conv;
-    c.in.base = dzbuf; c.out.base = ws + P.off_dx;
-    c.wgt = ws + P.off_w; c.bias = reinterpret_cast<const float*>(ws + P.off_bias);
-    if (P.sk_bytes > 0) { c.scratch = ws + P.off_sk; c.scratch_bytes = P.sk_bytes; }
-    if ((rc = launch_conv(c, s))) return rc;
+    TensorView out;
+    if ((rc = launch_data_grad(P, dzbuf, ws, s, &out))) return rc;
     if (tr) {
-      if ((rc = launch_unpack(c.out, d->dtype, 0, dx, s))) return rc;
+      if ((rc = launch_unpack(out, d->dtype, 0, dx, s))) return rc;
     } else {
       D2sArgs u;
       u.in = reinterpret_cast<const unsigned short*>(ws + P.off_dx); u.dx = dx;
@@ -885,23 +894,16 @@ int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const floa
     }
   }
   if (dw != nullptr) {
-    if (tr) rc = k2s2_pack_dense<BF16>(x, nullptr, zbuf, P, d->n, d->cin, d->cin, s);
+    if (tr) rc = launch_pack_halo<BF16>(x, nullptr, zbuf, P.rows, d->n, P.H, P.W, 0, d->cin, d->cin, 0, s);
     else rc = k2s2_pack_s2d<BF16>(x, nullptr, abuf, P, d->n, d->cin, s);
     if (rc) return rc;
-    WgradLaunch g = P.wg;
-    g.x.base = abuf;
-    g.dz.base = zbuf;
-    g.dw = dw;
-    if (P.slab_bytes > 0) { g.scratch = ws + P.off_slab; g.scratch_bytes = P.slab_bytes; }
-    if ((rc = launch_conv_wgrad(g, s))) return rc;
+    if ((rc = launch_weight_grad(P, abuf, zbuf, dw, ws, s))) return rc;
   }
   if (dbias != nullptr) {
-    float* part = reinterpret_cast<float*>(ws + P.off_part);
-    RON_LAUNCH(conv_bwd_colsum_kernel<BF16>, dim3(P.chunks, P.sum_cols / 64), dim3(256), 0, s, static_cast<const unsigned short*>(dzbuf),
-               (long long)P.rows, P.sum_cols, (long long)P.chunk_rows, part);
-    RON_HIP_CHECK(ron::launch_error());
-    if (tr) RON_LAUNCH(k2s2_colsum_fold_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.sum_cols, d->cout, dbias);
-    else RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, static_cast<const float*>(part), P.chunks, P.sum_cols, dbias);
+    const float* part;
+    if ((rc = launch_colsum<BF16>(P, dzbuf, ws, s, &part))) return rc;
+    if (tr) RON_LAUNCH(k2s2_colsum_fold_kernel, dim3(d->cout), dim3(64), 0, s, part, P.chunks, P.sum_cols, d->cout, dbias);
+    else RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(d->cout), dim3(64), 0, s, part, P.chunks, P.sum_cols, dbias);
     RON_HIP_CHECK(ron::launch_error());
   }
   return RON_OK;
@@ -920,24 +922,10 @@ extern "C" int ron_conv2d_k2s2_backward_nhwc(const ron_conv_desc* d, const float
                                              float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
   using namespace ron;
   K2Plan P;
-  int rc = plan_k2s2(d, &P);
-  if (rc != RON_OK) return rc;
-  RON_REQUIRE(dy != nullptr, "conv k2s2 backward: dy is NULL");
-  RON_REQUIRE(!d->relu || y != nullptr, "conv k2s2 backward: relu is set and y is NULL (the mask is y > 0)");
-  RON_REQUIRE(dx == nullptr || w != nullptr, "conv k2s2 backward: dx needs w");
-  RON_REQUIRE(dw == nullptr || x != nullptr, "conv k2s2 backward: dw needs x");
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "conv k2s2 backward: workspace of %lld bytes, %lld needed (ron_conv2d_k2s2_backward_workspace_bytes)",
-              (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "conv k2s2 backward: the workspace must be 256-byte aligned");
-  RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "conv k2s2 backward: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)");
-  if (dx != nullptr) {
-    // what launch_conv would refuse is refused here, before anything is enqueued
-    ConvLaunch c = P.conv;
-    c.in.base = workspace; c.out.base = workspace; c.wgt = workspace; c.bias = static_cast<const float*>(workspace);
-    if (P.sk_bytes > 0) { c.scratch = workspace; c.scratch_bytes = P.sk_bytes; }
-    int o[4];
-    if ((rc = conv_describe(c, o))) return rc;
-  }
+  if (int rc = plan_k2s2(d, &P)) return rc;
+  if (int rc = check_backward_call("conv k2s2 backward", "ron_conv2d_k2s2_backward_workspace_bytes", d, P, x, w, y, dy, dx, dw,
+                                   workspace, workspace_bytes))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   return d->dtype == RON_DTYPE_BF16 ? run_k2s2<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)

@@ -21,12 +21,11 @@
 
 #include <math.h>
 
-#include "common.h"
+#include "loss_device.h"
 
 namespace ron {
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kHistRows = 1024;            // rows of one workgroup of a digit pass (4 per thread)
 constexpr int kSegs = RON_MAX_LAYERS;      // most segments of a call
 constexpr int kDigits = 4;
@@ -53,26 +52,10 @@ struct SsdGradDev {
   float* d_loc[RON_MAX_LAYERS];
 };
 
-__device__ inline void locate_row(const SsdDev& p, long long r, int* layer, long long* j) {
-  int l = 0;
-  while (l + 1 < p.num_layers && r >= p.row_off[l + 1]) ++l;
-  *layer = l;
-  *j = r - p.row_off[l];
-}
-
 __device__ inline int segment_of(const SsdDev& p, long long r) {
   int s = 0;
   while (s + 1 < p.num_segs && r >= p.seg_off[s + 1]) ++s;
   return s;
-}
-
-// sparse softmax cross-entropy of one row, as cross_entropy of targets.hip forms it
-__device__ inline float cross_entropy(const float* x, int c, int label) {
-  float mx = x[0];
-  for (int i = 1; i < c; ++i) mx = fmaxf(mx, x[i]);
-  float sum = 0.f;
-  for (int i = 0; i < c; ++i) sum += expf(x[i] - mx);
-  return label < c ? (logf(sum) + mx) - x[label] : __uint_as_float(0x7fc00000u);
 }
 
 // custom_layers.abs_smooth, one coordinate
@@ -240,13 +223,9 @@ __device__ inline Scales segment_scales(const SsdDev& p, int n_pos, int n_mined)
   return s;
 }
 
-constexpr int kGradTileFloats = 8192;      // LDS tile of class logits: rows x (C | 1) floats, 32 KiB
-
 // One workgroup owns the 256 rows it owned in ssd_rows_kernel.  A thread forms its row's three terms; they are added per segment in
 // double and stored as the workgroup's partial sums.  With kGrad the thread also writes the row's localisation gradient (16 bytes
-// per lane) and the class rows go through LDS as in loss_grad_kernel of targets.hip: rows of the positive and the mined set are
-// loaded with consecutive lanes on consecutive floats, a thread takes its own row's maximum and sum in index order, and every
-// element of d_cls leaves with consecutive lanes on consecutive floats.
+// per lane), and the rows of the positive and the mined set go through LDS (class_grad_pass), each with its segment's scale.
 template <bool kGrad>
 __global__ __launch_bounds__(kThreads) void ssd_sum_kernel(SsdDev p, SsdGradDev q, const int32_t* __restrict__ cnt,
                                                            const unsigned* __restrict__ hist, const unsigned* __restrict__ keys,
@@ -284,7 +263,7 @@ __global__ __launch_bounds__(kThreads) void ssd_sum_kernel(SsdDev p, SsdGradDev 
     float4 gl = make_float4(0.f, 0.f, 0.f, 0.f);
     if (pos) {
       const long long g = p.gclasses[l][j];
-      lab = (int)(g < 0 ? 0 : (g > C ? C : g));
+      lab = clip_label(g, C);
       v_pos = (double)cross_entropy(src, C, lab);
       const float4 a = *(reinterpret_cast<const float4*>(p.loc[l]) + j);
       const float4 b = *(reinterpret_cast<const float4*>(p.gloc[l]) + j);
@@ -312,65 +291,16 @@ __global__ __launch_bounds__(kThreads) void ssd_sum_kernel(SsdDev p, SsdGradDev 
     red[1][t] = seg == s ? v_neg : 0.0;
     red[2][t] = seg == s ? v_loc : 0.0;
     __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-      if (t < off)
-        for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + off];
-      __syncthreads();
-    }
+    reduce3(red);
     if (t < 3) partials[((size_t)blockIdx.x * p.num_segs + s) * 3 + t] = red[t][0];
     __syncthreads();
   }
   if (!kGrad) return;
 
-  __shared__ float tile[kGradTileFloats];
-  __shared__ const float* row_src[kThreads];       // the row's logits (null: the row does not exist)
-  __shared__ float* row_dst[kThreads];
-  __shared__ int row_lab[kThreads];                // clipped label of a positive row, 0 of a mined row, -1 outside both
-  __shared__ float row_mx[kThreads], row_sum[kThreads], row_scale[kThreads];
-  row_src[t] = src;
-  row_dst[t] = dst;
-  row_lab[t] = lab;
+  __shared__ ClassGradLds lds;                     // (row_lab: clipped label of a positive row, 0 of a mined row, -1 outside both)
+  __shared__ float row_scale[kThreads];
   row_scale[t] = scale;
-  const int stride = C | 1;                                               // odd: a thread per row walks the banks without conflict
-  const int chunk = kGradTileFloats / stride < kThreads ? kGradTileFloats / stride : kThreads;      // >= 63 rows (C <= 128)
-  const int dq = kThreads / C, dr = kThreads - dq * C;
-  for (int r0 = 0; r0 < kThreads; r0 += chunk) {
-    const int nrows = kThreads - r0 < chunk ? kThreads - r0 : chunk;
-    const int nelem = nrows * C;
-    __syncthreads();                                                      // row_*[] written; the previous chunk's tile consumed
-    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
-      if (row_lab[r0 + row] >= 0) tile[row * stride + k] = row_src[r0 + row][k];
-      row += dq; k += dr;
-      if (k >= C) { k -= C; ++row; }
-    }
-    __syncthreads();
-    if (t >= r0 && t < r0 + nrows && lab >= 0) {
-      const float* x = tile + (t - r0) * stride;
-      float mx = x[0];
-      for (int i = 1; i < C; ++i) mx = fmaxf(mx, x[i]);
-      float sum = 0.f;
-      for (int i = 0; i < C; ++i) sum += expf(x[i] - mx);
-      row_mx[t] = mx;
-      row_sum[t] = sum;
-    }
-    __syncthreads();
-    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
-      float* out = row_dst[r0 + row];
-      if (out != nullptr) {
-        const int rl = row_lab[r0 + row];
-        float v = 0.f;
-        if (rl >= C) {
-          v = __uint_as_float(0x7fc00000u);                               // label out of range: the forward's row is NaN
-        } else if (rl >= 0) {
-          const float pk = expf(tile[row * stride + k] - row_mx[r0 + row]) / row_sum[r0 + row];
-          v = (pk - (k == rl ? 1.f : 0.f)) * row_scale[r0 + row];
-        }
-        out[k] = v;
-      }
-      row += dq; k += dr;
-      if (k >= C) { k -= C; ++row; }
-    }
-  }
+  class_grad_pass(lds, C, src, dst, lab, [](int row) { return row_scale[row]; });
 }
 
 // One workgroup: per segment the partial sums of its workgroups in a fixed order, then the four losses and the counts.
@@ -389,11 +319,7 @@ __global__ __launch_bounds__(kThreads) void ssd_final_kernel(SsdDev p, const int
       for (int k = 0; k < 3; ++k) acc[k] += partials[((size_t)w * p.num_segs + s) * 3 + k];
     for (int k = 0; k < 3; ++k) red[k][t] = acc[k];
     __syncthreads();
-    for (int off = kThreads / 2; off > 0; off >>= 1) {
-      if (t < off)
-        for (int k = 0; k < 3; ++k) red[k][t] += red[k][t + off];
-      __syncthreads();
-    }
+    reduce3(red);
     if (t < 3) seg_sum[s][t] = red[t][0];
     __syncthreads();
   }
@@ -424,22 +350,6 @@ __global__ __launch_bounds__(kThreads) void ssd_final_kernel(SsdDev p, const int
   losses[1] = l_neg;
   losses[2] = l_loc;
   losses[3] = (l_pos + l_neg) + l_loc;
-}
-
-int check_layers(const ron_heads* h, const char* what) {
-  RON_REQUIRE(h != nullptr, "%s: null argument", what);
-  RON_REQUIRE(h->num_layers >= 1 && h->num_layers <= RON_MAX_LAYERS, "%s: %d layers not in [1, %d]", what, h->num_layers,
-              RON_MAX_LAYERS);
-  for (int l = 0; l < h->num_layers; ++l)
-    RON_REQUIRE(h->feat_h[l] > 0 && h->feat_w[l] > 0 && h->num_anchors[l] > 0 && h->num_anchors[l] <= RON_MAX_ANCHORS_PER_CELL,
-                "%s: bad shape of layer %d", what, l);
-  return RON_OK;
-}
-
-int64_t count_rows(const ron_heads* heads, int n) {
-  int64_t rows = 0;
-  for (int l = 0; l < heads->num_layers; ++l) rows += (int64_t)n * heads->feat_h[l] * heads->feat_w[l] * heads->num_anchors[l];
-  return rows;
 }
 
 struct Layout {

@@ -18,13 +18,12 @@
 
 #include <math.h>
 
-#include "common.h"
+#include "loss_device.h"
 
 namespace ron {
 namespace {
 
 typedef unsigned long long u64;
-constexpr int kThreads = 256;
 
 struct EncodeDev {
   int num_layers;
@@ -205,13 +204,6 @@ struct LossDev {
 constexpr int kNumCounts = 6;
 constexpr int64_t kPartialsOffset = 64;   // bytes: the double partial sums [workgroups][3] start here
 
-__device__ inline void locate_row(const LossDev& p, long long r, int* layer, long long* j) {
-  int l = 0;
-  while (l + 1 < p.num_layers && r >= p.row_off[l + 1]) ++l;
-  *layer = l;
-  *j = r - p.row_off[l];
-}
-
 // adds a 0 / 1 flag over the workgroup and lets one thread add the sum to a global counter
 __device__ inline void count_flag(bool flag, int* lds_slot, int32_t* counter) {
   const int c = __popcll(__ballot(flag));
@@ -247,15 +239,6 @@ __device__ inline float select_probability(float ratio, int n_pos, int n_neg) {
   return n_neg > 0 ? (float)sel / (float)n_neg : 0.f;
 }
 
-// sparse softmax cross-entropy of one row, log-sum-exp with the maximum subtracted
-__device__ inline float cross_entropy(const float* x, int c, int label) {
-  float mx = x[0];
-  for (int i = 1; i < c; ++i) mx = fmaxf(mx, x[i]);
-  float sum = 0.f;
-  for (int i = 0; i < c; ++i) sum += expf(x[i] - mx);
-  return label < c ? (logf(sum) + mx) - x[label] : __uint_as_float(0x7fc00000u);
-}
-
 // custom_layers.modified_smooth_l1, sigma 3 (custom_layers.py:31-49), one coordinate
 __device__ inline float smooth_l1(float pred, float target) {
   const float d = pred - target;
@@ -285,10 +268,7 @@ __global__ __launch_bounds__(kThreads) void loss_rows_kernel(LossDev p, const fl
     const bool om = p.objp[l][j] > p.objness_threshold;
     in_obj = (neg && rand_obj[r] < p_obj) || pos;
     in_cls = (neg && om && rand_cls[r] < p_cls) || (pos && om);
-    if (in_cls) {
-      const long long lab = g < 0 ? 0 : (g > p.num_classes ? p.num_classes : g);
-      v_cls = (double)cross_entropy(p.cls[l] + j * p.num_classes, p.num_classes, (int)lab);
-    }
+    if (in_cls) v_cls = (double)cross_entropy(p.cls[l] + j * p.num_classes, p.num_classes, clip_label(g, p.num_classes));
     if (in_obj) v_obj = (double)cross_entropy(p.obj[l] + j * 2, 2, pos ? 1 : 0);
     if (pos && om) {
       const float* a = p.loc[l] + j * 4;
@@ -301,11 +281,7 @@ __global__ __launch_bounds__(kThreads) void loss_rows_kernel(LossDev p, const fl
   red[2][threadIdx.x] = v_loc;
   count_flag(in_obj, &c[0], &counts[4]);
   count_flag(in_cls, &c[1], &counts[5]);           // (both calls synchronise the workgroup: red[] is complete)
-  for (int off = kThreads / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  reduce3(red);
   if (threadIdx.x < 3) partials[(size_t)blockIdx.x * 3 + threadIdx.x] = red[threadIdx.x][0];
 }
 
@@ -318,11 +294,7 @@ __global__ __launch_bounds__(kThreads) void loss_final_kernel(const double* __re
     for (int k = 0; k < 3; ++k) acc[k] += partials[(size_t)i * 3 + k];
   for (int k = 0; k < 3; ++k) red[k][threadIdx.x] = acc[k];
   __syncthreads();
-  for (int off = kThreads / 2; off > 0; off >>= 1) {
-    if (threadIdx.x < off)
-      for (int k = 0; k < 3; ++k) red[k][threadIdx.x] += red[k][threadIdx.x + off];
-    __syncthreads();
-  }
+  reduce3(red);
   if (threadIdx.x == 0) {
     const int n_pos = counts[0], n_cls_pos = counts[2], n_obj_set = counts[4], n_cls_set = counts[5];
     // tf.reduce_mean over tf.boolean_mask: an empty set is 0 / 0 = NaN (:750, :759, :772)
@@ -344,8 +316,6 @@ struct GradDev {
   float* d_loc[RON_MAX_LAYERS];
 };
 
-constexpr int kGradTileFloats = 8192;     // LDS tile of class logits: rows x (C | 1) floats, 32 KiB
-
 // d modified_smooth_l1 / d pred, one coordinate: 9 d in the square branch, sign(d) in the linear one; the branch test is the forward's
 __device__ inline float smooth_l1_grad(float pred, float target, float s) {
   const float d = pred - target;
@@ -353,18 +323,12 @@ __device__ inline float smooth_l1_grad(float pred, float target, float s) {
 }
 
 // One workgroup owns the same 256 rows as in loss_rows_kernel.  A thread forms its row's sets and writes the row's objectness and
-// localisation gradients (8 and 16 bytes per lane: contiguous across lanes).  The class rows go through LDS: the workgroup's rows of
-// the class set are loaded with consecutive lanes on consecutive floats, a thread takes its own row's maximum and sum (in index
-// order, like cross_entropy) from LDS at an odd row stride, and the gradient leaves with consecutive lanes on consecutive floats
-// again.  Rows x (C | 1) floats that do not fit the tile are taken in several chunks of rows.
+// localisation gradients (8 and 16 bytes per lane: contiguous across lanes).  The rows of the class set go through LDS
+// (class_grad_pass); their scale is the same for every row and stays in a register.
 __global__ __launch_bounds__(kThreads) void loss_grad_kernel(LossDev p, GradDev q, const float* __restrict__ rand_obj,
                                                              const float* __restrict__ rand_cls, const int32_t* __restrict__ counts,
                                                              float w_cls, float w_obj, float w_loc) {
-  __shared__ float tile[kGradTileFloats];
-  __shared__ const float* row_src[kThreads];       // the row's logits (null: the row does not exist)
-  __shared__ float* row_dst[kThreads];
-  __shared__ int row_lab[kThreads];                // clipped label of a row of the class set, -1 outside it
-  __shared__ float row_mx[kThreads], row_sum[kThreads];
+  __shared__ ClassGradLds lds;
   const int t = threadIdx.x;
   const int C = p.num_classes;
   const int n_pos = counts[0], n_cls_pos = counts[2];
@@ -388,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void loss_grad_kernel(LossDev p, GradDev 
     const bool in_cls = (neg && om && rand_cls[r] < p_cls) || (pos && om);
     src = p.cls[l] + j * C;
     dst = q.d_cls[l] + j * C;
-    if (in_cls) lab = (int)(g < 0 ? 0 : (g > C ? C : g));
+    if (in_cls) lab = clip_label(g, C);
     float2 go = make_float2(0.f, 0.f);
     if (in_obj) {
       const float2 x = *(reinterpret_cast<const float2*>(p.obj[l]) + j);
@@ -408,59 +372,29 @@ __global__ __launch_bounds__(kThreads) void loss_grad_kernel(LossDev p, GradDev 
     }
     *(reinterpret_cast<float4*>(q.d_loc[l]) + j) = gl;
   }
-  row_src[t] = src;
-  row_dst[t] = dst;
-  row_lab[t] = lab;
-  const int stride = C | 1;                                               // odd: a thread per row walks the banks without conflict
-  const int chunk = kGradTileFloats / stride < kThreads ? kGradTileFloats / stride : kThreads;      // >= 63 rows (C <= 128)
-  const int dq = kThreads / C, dr = kThreads - dq * C;
-  for (int r0 = 0; r0 < kThreads; r0 += chunk) {
-    const int nrows = kThreads - r0 < chunk ? kThreads - r0 : chunk;
-    const int nelem = nrows * C;
-    __syncthreads();                                                      // row_*[] written; the previous chunk's tile consumed
-    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
-      if (row_lab[r0 + row] >= 0) tile[row * stride + k] = row_src[r0 + row][k];
-      row += dq; k += dr;
-      if (k >= C) { k -= C; ++row; }
-    }
-    __syncthreads();
-    if (t >= r0 && t < r0 + nrows && lab >= 0) {
-      const float* x = tile + (t - r0) * stride;
-      float mx = x[0];
-      for (int i = 1; i < C; ++i) mx = fmaxf(mx, x[i]);
-      float sum = 0.f;
-      for (int i = 0; i < C; ++i) sum += expf(x[i] - mx);
-      row_mx[t] = mx;
-      row_sum[t] = sum;
-    }
-    __syncthreads();
-    for (int e = t, row = t / C, k = t - (t / C) * C; e < nelem; e += kThreads) {
-      float* out = row_dst[r0 + row];
-      if (out != nullptr) {
-        const int rl = row_lab[r0 + row];
-        float v = 0.f;
-        if (rl >= C) {
-          v = __uint_as_float(0x7fc00000u);                               // label out of range: the forward's row is NaN
-        } else if (rl >= 0) {
-          const float pk = expf(tile[row * stride + k] - row_mx[r0 + row]) / row_sum[r0 + row];
-          v = (pk - (k == rl ? 1.f : 0.f)) * s_cls;
-        }
-        out[k] = v;
-      }
-      row += dq; k += dr;
-      if (k >= C) { k -= C; ++row; }
-    }
-  }
+  class_grad_pass(lds, C, src, dst, lab, [s_cls](int) { return s_cls; });
 }
 
-int check_layers(const ron_heads* h, const char* what) {
-  RON_REQUIRE(h != nullptr, "%s: null argument", what);
-  RON_REQUIRE(h->num_layers >= 1 && h->num_layers <= RON_MAX_LAYERS, "%s: %d layers not in [1, %d]", what, h->num_layers,
-              RON_MAX_LAYERS);
-  for (int l = 0; l < h->num_layers; ++l)
-    RON_REQUIRE(h->feat_h[l] > 0 && h->feat_w[l] > 0 && h->num_anchors[l] > 0 && h->num_anchors[l] <= RON_MAX_ANCHORS_PER_CELL,
-                "%s: bad shape of layer %d", what, l);
-  return RON_OK;
+// workspace: the counters, then the partial sums of every workgroup
+struct Layout {
+  int64_t rows, wgs, bytes;
+};
+
+Layout workspace_layout(const ron_heads* heads, int n) {
+  Layout w;
+  w.rows = count_rows(heads, n);
+  w.wgs = (w.rows + kThreads - 1) / kThreads;
+  w.bytes = kPartialsOffset + w.wgs * 3 * (int64_t)sizeof(double);
+  return w;
+}
+
+int64_t workspace_bytes(const char* what, const ron_heads* heads, int n) {
+  if (check_layers(heads, what) != RON_OK) return -1;
+  if (n <= 0) {
+    set_error("%s: bad batch %d", what, n);
+    return -1;
+  }
+  return workspace_layout(heads, n).bytes;
 }
 
 }  // namespace
@@ -521,20 +455,12 @@ extern "C" int ron_bboxes_encode(const ron_heads* anchors, int n, const int32_t*
   return RON_OK;
 }
 
-static int64_t loss_rows(const ron_heads* heads, int n) {
-  int64_t rows = 0;
-  for (int l = 0; l < heads->num_layers; ++l) rows += (int64_t)n * heads->feat_h[l] * heads->feat_w[l] * heads->num_anchors[l];
-  return rows;
+extern "C" int64_t ron_losses_workspace_bytes(const ron_heads* heads, int n) {
+  return ron::workspace_bytes("ron_losses_workspace_bytes", heads, n);
 }
 
-extern "C" int64_t ron_losses_workspace_bytes(const ron_heads* heads, int n) {
-  if (ron::check_layers(heads, "ron_losses_workspace_bytes") != RON_OK) return -1;
-  if (n <= 0) {
-    ron::set_error("ron_losses_workspace_bytes: bad batch %d", n);
-    return -1;
-  }
-  const int64_t wgs = (loss_rows(heads, n) + ron::kThreads - 1) / ron::kThreads;
-  return ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
+extern "C" int64_t ron_losses_grad_workspace_bytes(const ron_heads* heads, int n) {
+  return ron::workspace_bytes("ron_losses_grad_workspace_bytes", heads, n);
 }
 
 // what ron_losses and ron_losses_grad share: the arguments checked, the kernels' parameter block filled
@@ -563,13 +489,12 @@ static int loss_setup(const char* what, const ron_heads* heads, const float* con
   RON_REQUIRE(rows < (1ll << 24) * 64, "%s: too many rows", what);
   p.objness_threshold = cfg->objness_threshold;
   p.negative_ratio = cfg->negative_ratio;
-  const int64_t wgs = (rows + ron::kThreads - 1) / ron::kThreads;
-  const int64_t need = ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "%s: workspace of %lld bytes, %lld needed", what,
-              (long long)workspace_bytes, (long long)need);
+  const ron::Layout w = ron::workspace_layout(heads, n);
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= w.bytes, "%s: workspace of %lld bytes, %lld needed", what,
+              (long long)workspace_bytes, (long long)w.bytes);
   RON_REQUIRE(((uintptr_t)workspace & 7) == 0, "%s: workspace must be 8-byte aligned", what);
   *out = p;
-  *out_wgs = wgs;
+  *out_wgs = w.wgs;
   return RON_OK;
 }
 
@@ -600,16 +525,6 @@ extern "C" int ron_losses(const ron_heads* heads, const float* const* objness_pr
   if (int rc = loss_forward(p, wgs, rand_objness, rand_cls, cfg, workspace, losses, counts, (hipStream_t)stream)) return rc;
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
-}
-
-extern "C" int64_t ron_losses_grad_workspace_bytes(const ron_heads* heads, int n) {
-  if (ron::check_layers(heads, "ron_losses_grad_workspace_bytes") != RON_OK) return -1;
-  if (n <= 0) {
-    ron::set_error("ron_losses_grad_workspace_bytes: bad batch %d", n);
-    return -1;
-  }
-  const int64_t wgs = (loss_rows(heads, n) + ron::kThreads - 1) / ron::kThreads;
-  return ron::kPartialsOffset + wgs * 3 * (int64_t)sizeof(double);
 }
 
 extern "C" int ron_losses_grad(const ron_heads* heads, const float* const* objness_pred, const ron_targets* targets, int n,

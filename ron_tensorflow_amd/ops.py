@@ -127,6 +127,13 @@ def _workspace(device, nbytes):
     return ent[0]
 
 
+def _sized_workspace(device, nbytes):
+    """The scratch for the result of a *_workspace_bytes entry; a negative result raises with the library's message."""
+    if nbytes < 0:
+        check(-1)
+    return _workspace(device, nbytes)
+
+
 def post_np(cls, obj, loc, anchors_dev, num_classes=None, objectness_thres=0.03, select_threshold=0.01,
             nms_threshold=0.45, top_k=400, bbox_img=(0., 0., 1., 1.), prior_scaling=(0.1, 0.1, 0.2, 0.2),
             cls_is_prob=False, obj_is_prob=False, loc_decoded=False, want_sorted=False):
@@ -151,9 +158,7 @@ def post_np(cls, obj, loc, anchors_dev, num_classes=None, objectness_thres=0.03,
     cfg.input_flags = ((_lib.RON_IN_CLS_IS_PROB if cls_is_prob else 0) | (_lib.RON_IN_OBJ_IS_PROB if obj_is_prob else 0) |
                        (_lib.RON_IN_LOC_DECODED if loc_decoded else 0))
     nbytes = lib().ron_post_np_workspace_bytes(C.byref(heads), n)
-    if nbytes < 0:
-        check(-1)
-    ws = _workspace(dev, nbytes)
+    ws = _sized_workspace(dev, nbytes)
     out = DetectionBuffers(n, top_k, dev)
     srt = DetectionBuffers(n, top_k, dev) if want_sorted else None
     n_cand = torch.zeros((n,), dtype=torch.int32, device=dev)
@@ -266,15 +271,31 @@ def bboxes_encode(glabels, gbboxes, anchors_dev, shapes, img_shape, allowed_bord
         out.gclasses[i], out.glocalisations[i] = gcl[i].data_ptr(), glo[i].data_ptr()
         out.gscores[i], out.gbboxes[i] = gsc[i].data_ptr(), gbb[i].data_ptr()
     nbytes = lib().ron_bboxes_encode_workspace_bytes(n, g)
-    if nbytes < 0:
-        check(-1)
-    ws = _workspace(dev, nbytes)
+    ws = _sized_workspace(dev, nbytes)
     borders = (C.c_int32 * len(shapes))(*[int(b) for b in allowed_borders[:len(shapes)]])
     ps = (C.c_float * 4)(*prior_scaling)
     check(lib().ron_bboxes_encode(C.byref(heads), n, ptr(glabels), ptr(gbboxes), g, int(img_shape[0]), int(img_shape[1]), borders,
                                   float(positive_threshold), float(ignore_threshold), ps, ptr(ws), nbytes, C.byref(out),
                                   current_stream()))
     return gcl, glo, gsc, gbb
+
+
+def _check_layer_tensors(i, *specs):
+    """Every (name, tensor, shape, dtype) of layer i is a GPU tensor of that shape and type."""
+    for name, t, want, dt in specs:
+        assert t.is_cuda and t.dtype == dt and tuple(t.shape) == want, '%s[%d] must be a %s GPU tensor %s' % (name, i, dt, want)
+
+
+def _grad_outputs(out_grads, names, likes, dev):
+    """The per-layer gradient lists of a *_grad call, one per list of `likes`: `out_grads` checked, or new tensors."""
+    if out_grads is None:
+        out_grads = tuple([torch.empty(t.shape, dtype=torch.float32, device=dev) for t in lst] for lst in likes)
+    for i in range(len(likes[0])):
+        for name, grads, like in zip(names, out_grads, likes):
+            t = grads[i]
+            assert t.is_cuda and t.dtype == torch.float32 and t.shape == like[i].shape and t.is_contiguous(), \
+                '%s[%d] must be a contiguous float32 GPU tensor %s' % (name, i, tuple(like[i].shape))
+    return out_grads
 
 
 LOSS_COUNTS = ('n_pos', 'n_neg', 'n_cls_pos', 'n_cls_neg', 'n_objness_set', 'n_cls_set')
@@ -291,11 +312,10 @@ def _losses_call(grad, logits, localisations, objness_logits, objness_pred, gcla
     rows = 0
     for i in range(len(logits)):
         shp = tuple(logits[i].shape[:4])
-        for name, t, want, dt in (('objness_logits', objness_logits[i], shp + (2,), torch.float32),
-                                  ('localisations', localisations[i], shp + (4,), torch.float32),
-                                  ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
-                                  ('gclasses', gclasses[i], shp, torch.int64)):
-            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == want, '%s[%d] must be a %s GPU tensor %s' % (name, i, dt, want)
+        _check_layer_tensors(i, ('objness_logits', objness_logits[i], shp + (2,), torch.float32),
+                             ('localisations', localisations[i], shp + (4,), torch.float32),
+                             ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
+                             ('gclasses', gclasses[i], shp, torch.int64))
         op = objness_pred[i]
         assert op.is_cuda and op.dtype == torch.float32 and op.numel() == gclasses[i].numel(), 'objness_pred[%d]: one float32 per anchor' % i
         tensors = [op.contiguous(), gclasses[i].contiguous(), glocalisations[i].contiguous()]
@@ -307,9 +327,7 @@ def _losses_call(grad, logits, localisations, objness_logits, objness_pred, gcla
     rand_objness, rand_cls = rand_objness.contiguous(), rand_cls.contiguous()
     cfg = _lib.LossCfg(float(objness_threshold), float(negative_ratio), float(alpha), float(beta))
     nbytes = (lib().ron_losses_grad_workspace_bytes if grad else lib().ron_losses_workspace_bytes)(C.byref(heads), n)
-    if nbytes < 0:
-        check(-1)
-    ws = _workspace(dev, nbytes)
+    ws = _sized_workspace(dev, nbytes)
     out = torch.empty((4,), dtype=torch.float32, device=dev)
     counts = torch.empty((6,), dtype=torch.int32, device=dev)
     if not grad:
@@ -318,15 +336,9 @@ def _losses_call(grad, logits, localisations, objness_logits, objness_pred, gcla
         del keep
         return out, counts
     hg = _lib.HeadGrads()
-    if out_grads is None:
-        out_grads = tuple([torch.empty(t.shape, dtype=torch.float32, device=dev) for t in lst]
-                          for lst in (logits, objness_logits, localisations))
-    d_cls, d_obj, d_loc = out_grads
+    d_cls, d_obj, d_loc = _grad_outputs(out_grads, ('d_logits', 'd_objness_logits', 'd_localisations'),
+                                        (logits, objness_logits, localisations), dev)
     for i in range(len(logits)):
-        for name, t, like in (('d_logits', d_cls[i], logits[i]), ('d_objness_logits', d_obj[i], objness_logits[i]),
-                              ('d_localisations', d_loc[i], localisations[i])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.shape == like.shape and t.is_contiguous(), \
-                '%s[%d] must be a contiguous float32 GPU tensor %s' % (name, i, tuple(like.shape))
         hg.d_cls[i], hg.d_obj[i], hg.d_loc[i] = d_cls[i].data_ptr(), d_obj[i].data_ptr(), d_loc[i].data_ptr()
     check(lib().ron_losses_grad(C.byref(heads), objp, C.byref(tg), n, ptr(rand_objness), ptr(rand_cls), C.byref(cfg), ptr(ws), nbytes,
                                 ptr(out), ptr(counts), C.byref(hg), current_stream()))
@@ -370,20 +382,16 @@ def _ssd_losses_call(grad, logits, localisations, gclasses, glocalisations, gsco
     rows = 0
     for i in range(len(logits)):
         shp = tuple(logits[i].shape[:4])
-        for name, t, want, dt in (('localisations', localisations[i], shp + (4,), torch.float32),
-                                  ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
-                                  ('gscores', gscores[i], shp, torch.float32),
-                                  ('gclasses', gclasses[i], shp, torch.int64)):
-            assert t.is_cuda and t.dtype == dt and tuple(t.shape) == want, '%s[%d] must be a %s GPU tensor %s' % (name, i, dt, want)
+        _check_layer_tensors(i, ('localisations', localisations[i], shp + (4,), torch.float32),
+                             ('glocalisations', glocalisations[i], shp + (4,), torch.float32),
+                             ('gscores', gscores[i], shp, torch.float32), ('gclasses', gclasses[i], shp, torch.int64))
         tensors = [gclasses[i].contiguous(), glocalisations[i].contiguous(), gscores[i].contiguous()]
         keep.append(tensors)
         tg.gclasses[i], tg.glocalisations[i], tg.gscores[i] = (t.data_ptr() for t in tensors)
         rows += gclasses[i].numel()
     cfg = _lib.SsdLossCfg(SSD_MINING[mining], float(match_threshold), float(negative_ratio), float(alpha))
     nbytes = (lib().ron_ssd_losses_grad_workspace_bytes if grad else lib().ron_ssd_losses_workspace_bytes)(C.byref(heads), n)
-    if nbytes < 0:
-        check(-1)
-    ws = _workspace(dev, nbytes)
+    ws = _sized_workspace(dev, nbytes)
     segs = 1 if mining == 'batch' else len(logits)
     out = torch.empty((4,), dtype=torch.float32, device=dev)
     counts = torch.empty((segs, 4), dtype=torch.int32, device=dev)
@@ -394,13 +402,8 @@ def _ssd_losses_call(grad, logits, localisations, gclasses, glocalisations, gsco
         del keep
         return out, counts, nvalues
     hg = _lib.HeadGrads()
-    if out_grads is None:
-        out_grads = tuple([torch.empty(t.shape, dtype=torch.float32, device=dev) for t in lst] for lst in (logits, localisations))
-    d_cls, d_loc = out_grads
+    d_cls, d_loc = _grad_outputs(out_grads, ('d_logits', 'd_localisations'), (logits, localisations), dev)
     for i in range(len(logits)):
-        for name, t, like in (('d_logits', d_cls[i], logits[i]), ('d_localisations', d_loc[i], localisations[i])):
-            assert t.is_cuda and t.dtype == torch.float32 and t.shape == like.shape and t.is_contiguous(), \
-                '%s[%d] must be a contiguous float32 GPU tensor %s' % (name, i, tuple(like.shape))
         hg.d_cls[i], hg.d_loc[i] = d_cls[i].data_ptr(), d_loc[i].data_ptr()
     check(lib().ron_ssd_losses_grad(C.byref(heads), C.byref(tg), n, C.byref(cfg), ptr(ws), nbytes, ptr(out), ptr(counts), ptr(nvalues),
                                     C.byref(hg), current_stream()))
@@ -505,13 +508,52 @@ def _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk):
     return _lib.ConvDesc(n, h, w, cin, cout, k, k, 1, dilation, int(relu), 0, _lib.DTYPES[dtype], -1, 0, 0, 0, splitk, 0)
 
 
-def conv2d_backward_workspace_bytes(n, h, w, cin, cout, k=3, dilation=1, relu=True, dtype='bf16', splitk=-1):
-    """Bytes of workspace conv2d_backward_nhwc needs for this convolution (host arithmetic; raises on a descriptor it refuses)."""
-    d = _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk)
-    nbytes = lib().ron_conv2d_backward_workspace_bytes(C.byref(d))
+def _desc_workspace_bytes(op, d):
+    """ron_<op>_workspace_bytes of a descriptor; raises on one the library refuses."""
+    nbytes = getattr(lib(), 'ron_%s_workspace_bytes' % op)(C.byref(d))
     if nbytes < 0:
         raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
     return int(nbytes)
+
+
+def _conv_backward_call(op, describe, x, w, dy, y, relu, need, workspace):
+    """What conv2d_backward_nhwc and conv2d_k2s2_backward_nhwc (`op`: the name without _nhwc) share: the arguments made contiguous
+    GPU tensors, `describe(x, w, dy)` (the operator's shape assertions; returns cout and a function that builds the descriptor),
+    the checks of y and need, the workspace, the outputs and the call of ron_<op>_nhwc."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    if not hasattr(w, 'data_ptr'):
+        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
+    w = w.contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and dy.is_cuda and w.is_cuda
+    cout, desc = describe(x, w, dy)
+    if relu and y is None:
+        raise _lib.RonError('%s_nhwc: relu=True needs the forward output y (the mask is y > 0)' % op)
+    if y is not None:
+        y = y.contiguous()
+        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
+    unknown = set(need) - {'dx', 'dw', 'db'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    d = desc()
+    nbytes = _desc_workspace_bytes(op, d)
+    ws = _workspace(dev, nbytes) if workspace is None else workspace
+    dx = torch.empty_like(x) if 'dx' in need else None
+    dw = torch.empty_like(w) if 'dw' in need else None
+    db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
+    check(getattr(lib(), 'ron_%s_nhwc' % op)(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
+                                              ptr(ws), int(ws.numel()), current_stream()))
+    return dx, dw, db
+
+
+def _needed_grads(ctx, has_bias):
+    """The `need` of a convolution's autograd backward: the gradients autograd asks for (db only where there is a bias)."""
+    return tuple(name for name, on in zip(('dx', 'dw', 'db'), (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
+                                                               has_bias and ctx.needs_input_grad[2])) if on)
+
+
+def conv2d_backward_workspace_bytes(n, h, w, cin, cout, k=3, dilation=1, relu=True, dtype='bf16', splitk=-1):
+    """Bytes of workspace conv2d_backward_nhwc needs for this convolution (host arithmetic; raises on a descriptor it refuses)."""
+    return _desc_workspace_bytes('conv2d_backward', _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk))
 
 
 def conv2d_backward_nhwc(x, w, dy, y=None, relu=True, dilation=1, dtype='bf16', splitk=-1, need=('dx', 'dw', 'db'), workspace=None):
@@ -522,33 +564,12 @@ def conv2d_backward_nhwc(x, w, dy, y=None, relu=True, dilation=1, dtype='bf16', 
     fixed order: dx comes back as storage-type values in fp32, dw [k,k,Cin,Cout] and db [Cout] as unrounded fp32 sums.
     `splitk`: pixel slices of the weight gradient (-1 by shape, 1 off, S forced).  `workspace`: a uint8 GPU tensor of at least
     conv2d_backward_workspace_bytes(...) bytes, or None for the cached per-device, per-stream buffer."""
-    x, dy = x.contiguous(), dy.contiguous()
-    dev = x.device
-    if not hasattr(w, 'data_ptr'):
-        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
-    w = w.contiguous()
-    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and dy.is_cuda and w.is_cuda
-    n, h, wd, cin = x.shape
-    k, cout = w.shape[0], w.shape[3]
-    assert tuple(w.shape) == (k, k, cin, cout) and tuple(dy.shape) == (n, h, wd, cout)
-    if relu and y is None:
-        raise _lib.RonError('conv2d_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
-    if y is not None:
-        y = y.contiguous()
-        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
-    unknown = set(need) - {'dx', 'dw', 'db'}
-    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
-    d = _backward_desc(n, h, wd, cin, cout, k, dilation, relu, dtype, splitk)
-    nbytes = lib().ron_conv2d_backward_workspace_bytes(C.byref(d))
-    if nbytes < 0:
-        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
-    ws = _workspace(dev, nbytes) if workspace is None else workspace
-    dx = torch.empty_like(x) if 'dx' in need else None
-    dw = torch.empty_like(w) if 'dw' in need else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
-    check(lib().ron_conv2d_backward_nhwc(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
-                                         ptr(ws), int(ws.numel()), current_stream()))
-    return dx, dw, db
+    def describe(x, w, dy):
+        n, h, wd, cin = x.shape
+        k, cout = w.shape[0], w.shape[3]
+        assert tuple(w.shape) == (k, k, cin, cout) and tuple(dy.shape) == (n, h, wd, cout)
+        return cout, lambda: _backward_desc(n, h, wd, cin, cout, k, dilation, relu, dtype, splitk)
+    return _conv_backward_call('conv2d_backward', describe, x, w, dy, y, relu, need, workspace)
 
 
 class _Conv2dNhwcFn(torch.autograd.Function):
@@ -565,8 +586,7 @@ class _Conv2dNhwcFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
         relu, dilation, dtype, has_bias = ctx.cfg
-        need = tuple(name for name, on in zip(('dx', 'dw', 'db'), (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                                                   has_bias and ctx.needs_input_grad[2])) if on)
+        need = _needed_grads(ctx, has_bias)
         dx, dw, db = conv2d_backward_nhwc(x, w, dy, y, relu=relu, dilation=dilation, dtype=dtype, need=need) if need else (None, None, None)
         return dx, dw, db, None, None, None
 
@@ -603,11 +623,7 @@ def _k2s2_desc(n, h, w, cin, cout, relu, transpose, dtype, splitk):
 
 def conv2d_k2s2_backward_workspace_bytes(n, h, w, cin, cout, relu=True, transpose=False, dtype='bf16', splitk=-1):
     """Bytes of workspace conv2d_k2s2_backward_nhwc needs (n, h, w: the input x; host arithmetic; raises on a refused descriptor)."""
-    d = _k2s2_desc(n, h, w, cin, cout, relu, transpose, dtype, splitk)
-    nbytes = lib().ron_conv2d_k2s2_backward_workspace_bytes(C.byref(d))
-    if nbytes < 0:
-        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
-    return int(nbytes)
+    return _desc_workspace_bytes('conv2d_k2s2_backward', _k2s2_desc(n, h, w, cin, cout, relu, transpose, dtype, splitk))
 
 
 def conv2d_k2s2_backward_nhwc(x, w, dy, y=None, relu=True, transpose=False, dtype='bf16', splitk=-1, need=('dx', 'dw', 'db'), workspace=None):
@@ -615,34 +631,13 @@ def conv2d_k2s2_backward_nhwc(x, w, dy, y=None, relu=True, transpose=False, dtyp
     `transpose`, of the 2x2 stride-2 transposed convolution (w [2,2,Cout,Cin], y and dy [N,2H,2W,Cout]): (dx, dw, db), None for
     those not in `need`.  Everything else as conv2d_backward_nhwc: GPU fp32 tensors (a numpy w is uploaded), the mask is y > 0
     with `relu`, dx comes back as storage-type values in fp32, dw (shaped like w) and db [Cout] as unrounded fp32 sums."""
-    x, dy = x.contiguous(), dy.contiguous()
-    dev = x.device
-    if not hasattr(w, 'data_ptr'):
-        w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(dev)
-    w = w.contiguous()
-    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and w.dtype == torch.float32 and x.is_cuda and dy.is_cuda and w.is_cuda
-    n, h, wd, cin = x.shape
-    cout = w.shape[2] if transpose else w.shape[3]
-    assert tuple(w.shape) == ((2, 2, cout, cin) if transpose else (2, 2, cin, cout)), 'w %s' % (tuple(w.shape),)
-    assert tuple(dy.shape) == ((n, 2 * h, 2 * wd, cout) if transpose else (n, h // 2, wd // 2, cout)), 'dy %s' % (tuple(dy.shape),)
-    if relu and y is None:
-        raise _lib.RonError('conv2d_k2s2_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
-    if y is not None:
-        y = y.contiguous()
-        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
-    unknown = set(need) - {'dx', 'dw', 'db'}
-    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
-    d = _k2s2_desc(n, h, wd, cin, cout, relu, transpose, dtype, splitk)
-    nbytes = lib().ron_conv2d_k2s2_backward_workspace_bytes(C.byref(d))
-    if nbytes < 0:
-        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
-    ws = _workspace(dev, nbytes) if workspace is None else workspace
-    dx = torch.empty_like(x) if 'dx' in need else None
-    dw = torch.empty_like(w) if 'dw' in need else None
-    db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
-    check(lib().ron_conv2d_k2s2_backward_nhwc(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
-                                              ptr(ws), int(ws.numel()), current_stream()))
-    return dx, dw, db
+    def describe(x, w, dy):
+        n, h, wd, cin = x.shape
+        cout = w.shape[2] if transpose else w.shape[3]
+        assert tuple(w.shape) == ((2, 2, cout, cin) if transpose else (2, 2, cin, cout)), 'w %s' % (tuple(w.shape),)
+        assert tuple(dy.shape) == ((n, 2 * h, 2 * wd, cout) if transpose else (n, h // 2, wd // 2, cout)), 'dy %s' % (tuple(dy.shape),)
+        return cout, lambda: _k2s2_desc(n, h, wd, cin, cout, relu, transpose, dtype, splitk)
+    return _conv_backward_call('conv2d_k2s2_backward', describe, x, w, dy, y, relu, need, workspace)
 
 
 class _MaxPool2x2NhwcFn(torch.autograd.Function):
@@ -677,8 +672,7 @@ class _Conv2dK2s2NhwcFn(torch.autograd.Function):
     def backward(ctx, dy):
         x, w, y = ctx.saved_tensors
         relu, transpose, dtype, has_bias = ctx.cfg
-        need = tuple(name for name, on in zip(('dx', 'dw', 'db'), (ctx.needs_input_grad[0], ctx.needs_input_grad[1],
-                                                                   has_bias and ctx.needs_input_grad[2])) if on)
+        need = _needed_grads(ctx, has_bias)
         dx, dw, db = (conv2d_k2s2_backward_nhwc(x, w, dy, y, relu=relu, transpose=transpose, dtype=dtype, need=need) if need
                       else (None, None, None))
         return dx, dw, db, None, None, None
