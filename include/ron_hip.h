@@ -716,6 +716,51 @@ int64_t ron_conv2d_k2s2_backward_workspace_bytes(const ron_conv_desc* d);
 int ron_conv2d_k2s2_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
                                   float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Training-mode batch normalisation (slim.batch_norm under ron_arg_scope(is_training=True), nets/ron_vgg_320.py:616-624:
+ * fused=True, decay=0.997, epsilon=1e-5, scale=True; every _conv_left and _objectness, reg_bbox/Conv2d_0_3x3 and the two
+ * inception concatenations of pred_cls_module), forward and backward.  Real entry points like the convolution backward: they
+ * enqueue on `stream`, allocate nothing, never synchronise, honour the dry-run mode, assume nothing about the workspace's
+ * contents and use no atomics; all sums run in a fixed order that depends only on the descriptor (the launch geometry is a
+ * function of the shape alone), so the same inputs give the same bytes.
+ *
+ * All pointers are DEVICE fp32: x, y, dy, dx [n,h,w,c]; gamma, beta, mean, var, moving_mean, moving_var, dgamma, dbeta [c].
+ * With M = n h w and xs = round(x) to d->dtype (bf16 / fp16: a convolution's output as this library stores it):
+ *   forward   mean = sum(xs) / M;  var = sum((xs - mean)^2) / M (the BIASED variance: the one that normalises; never formed as
+ *             E[x^2] - mean^2);  rstd = 1 / sqrt(var + eps);  y = round(act(gamma (xs - mean) rstd + beta)), delivered as
+ *             storage-type values in fp32 as ron_conv2d_nhwc delivers y; act is ReLU when d->relu.  gamma, beta, the statistics
+ *             and all arithmetic between the two roundings are fp32.  mean and var are outputs: the backward reads them and
+ *             recomputes rstd with the same expression.
+ *   moving    in place, both or neither (both NULL skips them): moving_mean = decay moving_mean + (1 - decay) mean and
+ *             moving_var = decay moving_var + (1 - decay) var M / max(M - 1, 1): assign_moving_average(zero_debias=False) on the
+ *             Bessel-corrected variance FusedBatchNorm returns, regrouped so that decay 0 gives the batch statistic and decay 1
+ *             leaves the tensor unchanged bit for bit.
+ *   backward  dz = round(dy (y > 0)) when d->relu (y is this operator's own output, read only then), else round(dy);
+ *             xhat = (xs - mean) rstd;  dbeta = sum(dz), dgamma = sum(dz xhat): fp32 sums, not rounded further;
+ *             dx = round(gamma rstd (dz - dbeta / M - xhat dgamma / M)), storage-type values in fp32: it goes straight into
+ *             ron_conv2d_backward_nhwc (relu = 0) as its dy.  dx, dgamma, dbeta may each be NULL; every element of a non-NULL
+ *             output is written by a plain store.
+ * Accepted: dtype bf16 / fp16, c a multiple of 8, n, h, w >= 1, M <= 2^24 (the count stays exact in fp32), eps >= 0 and
+ * finite, 0 <= decay <= 1, relu 0 / 1, every tensor pointer 16-byte aligned, the workspace 256-byte aligned and at least
+ * ron_batchnorm_workspace_bytes(d) bytes (host arithmetic; one size serves both directions; -1 + ron_last_error() on a refused
+ * descriptor).  Anything else - a NULL y with relu set, moving_mean without moving_var or the other way round - is
+ * RON_ERR_INVALID with a message, before any HIP call.
+ * ---------------------------------------------------------------------------------------- */
+typedef struct {
+  int32_t n, h, w, c;
+  int32_t dtype; /* RON_DTYPE_BF16 or RON_DTYPE_F16 */
+  int32_t relu;
+  float eps;
+  float decay;   /* of the moving statistics (the backward ignores it beyond the range check) */
+} ron_bn_desc;
+int64_t ron_batchnorm_workspace_bytes(const ron_bn_desc* d);
+int ron_batchnorm_train_nhwc(const ron_bn_desc* d, const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                             float* var, float* moving_mean, float* moving_var, void* workspace, int64_t workspace_bytes,
+                             void* stream);
+int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x, const float* y, const float* dy, const float* gamma,
+                                const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, void* workspace,
+                                int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -109,6 +109,11 @@ class ConvDesc(C.Structure):
                 ('center_from', C.c_int32)]
 
 
+class BnDesc(C.Structure):
+    _fields_ = [('n', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('c', C.c_int32), ('dtype', C.c_int32), ('relu', C.c_int32),
+                ('eps', C.c_float), ('decay', C.c_float)]
+
+
 # every symbol include/ron_hip.h declares: (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -189,6 +194,9 @@ SIGNATURES = {
     'ron_maxpool2x2_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     'ron_conv2d_k2s2_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_k2s2_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_batchnorm_workspace_bytes': (C.c_int64, [C.POINTER(BnDesc)]),
+    'ron_batchnorm_train_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_batchnorm_backward_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

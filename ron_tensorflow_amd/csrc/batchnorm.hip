@@ -1,0 +1,510 @@
+// Training-mode batch normalisation, forward and backward (ron_batchnorm_train_nhwc, ron_batchnorm_backward_nhwc): the twenty
+// slim.batch_norm layers of the RON heads under ron_arg_scope(is_training=True) (nets/ron_vgg_320.py:616-624), each followed by ReLU.
+//
+//   M = n h w, xs = round(x) to the storage type (a convolution's output as this library stores it)
+//   forward   mean = sum(xs) / M, var = sum((xs - mean)^2) / M (biased: the one that normalises), rstd = 1 / sqrt(var + eps)
+//             y = round(act(gamma (xs - mean) rstd + beta))
+//             moving_mean = decay moving_mean + (1 - decay) mean,  moving_var likewise with var M / max(M - 1, 1)
+//   backward  dz = round(dy (y > 0)) with relu, else round(dy);  xhat = (xs - mean) rstd
+//             dbeta = sum(dz), dgamma = sum(dz xhat), dx = round(gamma rstd (dz - dbeta / M - xhat dgamma / M))
+//
+// Bandwidth bound, so the fewest passes over the fp32 tensors: the forward reads x twice and writes y, the backward reads x, dy (and
+// y) twice and writes dx.  Every pass has the same geometry, a function of the shape alone (plan):
+//
+//   a lane owns 4 adjacent channels (one 16-byte access); `lpr` lanes side by side cover a row's channel tile, 64 / lpr rows share a
+//   wave, a workgroup of 4 waves covers `rpb` rows at a time; the rows are cut into `slices` slices of `slice_rows` rows (a power of
+//   two, a multiple of rpb), blockIdx.x = slice, blockIdx.y = channel tile; inside a slice row lane rl takes rows rl, rl + rpb, ...
+//
+// Statistics in ONE read of x, never as E[x^2] - mean^2: a lane shifts by the first value it meets (K), adds d = xs - K and d^2,
+// and ends with (count, mean = K + s1 / count, M2 = s2 - s1^2 / count); the row lanes of a workgroup, then a channel's slices, are
+// merged with Chan's formula behind a fixed binary tree (lane i with lane i + stride, the stride halving).  All counts follow
+// from the shape, so the same inputs give the same bytes; with M and hence every count a power of two each merge joins equal counts
+// and small-integer inputs come out exact.  The gradient sums take the same route with plain additions.  No atomics anywhere.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cmath>
+
+#include "common.h"
+
+namespace ron {
+namespace {
+
+constexpr int kBnThreads = 256;
+constexpr int kBnMaxSlices = 1024;      // 4 per thread of the merge kernels
+constexpr int64_t kBnMaxRows = (int64_t)1 << 24;      // counts stay exact in fp32
+
+__device__ __forceinline__ float bn_round_bf16(float f) {
+  const unsigned u = __float_as_uint(f);
+  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return f;
+  return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
+}
+template <bool BF16> __device__ __forceinline__ float bn_round(float f) { return BF16 ? bn_round_bf16(f) : (float)(_Float16)f; }
+
+// the geometry every kernel of an operator call shares
+struct BnGeom {
+  long long rows;           // M
+  long long slice_rows;
+  int c, cg;                // channels, groups of 4 channels
+  int lpr, lpr_log2;        // lanes per row of a channel tile (a power of two <= 64)
+  int rpb;                  // rows a workgroup covers at a time: 256 / lpr
+  int slices, tiles;
+};
+
+struct BnPlan : BnGeom {
+  int64_t off_part = 0, off_fin = 0, total = 0;
+};
+
+struct Stat4 { float v[4]; };
+
+__device__ __forceinline__ void load4(const float* p, float* o) {
+  const float4 t = *reinterpret_cast<const float4*>(p);
+  o[0] = t.x; o[1] = t.y; o[2] = t.z; o[3] = t.w;
+}
+__device__ __forceinline__ void store4(float* p, const float* o) { *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
+
+// Chan's merge of (nb, mb, Mb) into (na, ma, Ma); an empty side changes nothing, equal counts give f = 1/2 exactly
+__device__ __forceinline__ void chan_merge(float& na, float* ma, float* Ma, float nb, const float* mb, const float* Mb) {
+  if (nb == 0.f) return;
+  if (na == 0.f) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { ma[e] = mb[e]; Ma[e] = Mb[e]; }
+    na = nb;
+    return;
+  }
+  const float n = na + nb, f = nb / n, w = na * f;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const float delta = mb[e] - ma[e];
+    ma[e] = ma[e] + delta * f;
+    Ma[e] = (Ma[e] + Mb[e]) + (delta * delta) * w;
+  }
+  na = n;
+}
+
+// rows of slice s, and of them those of row lane rl
+__device__ __forceinline__ long long slice_count(const BnGeom& g, long long s) {
+  const long long left = g.rows - s * g.slice_rows;
+  return left < g.slice_rows ? left : g.slice_rows;
+}
+
+// ---- forward, pass 1: per slice (mean, M2) of every channel -> part [slices][2][c] ---------------------------------------------------
+template <bool BF16>
+__global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(BnGeom g, const float* __restrict__ x, float* __restrict__ part) {
+  __shared__ float sh_n[kBnThreads];
+  __shared__ Stat4 sh_mean[kBnThreads], sh_m2[kBnThreads];
+  const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
+  const int cgi = blockIdx.y * g.lpr + gl;
+  const bool active = cgi < g.cg;
+  const long long r0 = (long long)blockIdx.x * g.slice_rows, cnt = slice_count(g, blockIdx.x);
+  float n = 0.f, mean[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f};
+  if (active && rl < cnt) {
+    const float* p = x + (r0 + rl) * g.c + (long long)cgi * 4;
+    const long long step = (long long)g.rpb * g.c;
+    const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
+    float k[4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+    load4(p, k);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) k[e] = bn_round<BF16>(k[e]);
+#pragma unroll 4
+    for (int i = 1; i < mine; ++i) {
+      float v[4];
+      load4(p + i * step, v);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float d = bn_round<BF16>(v[e]) - k[e];
+        s1[e] += d;
+        s2[e] += d * d;
+      }
+    }
+    n = (float)mine;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float q = s1[e] / n, v = s2[e] - s1[e] * q;
+      mean[e] = k[e] + q;
+      m2[e] = v < 0.f ? 0.f : v;          // (a NaN stays a NaN)
+    }
+  }
+  sh_n[tid] = n;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { sh_mean[tid].v[e] = mean[e]; sh_m2[tid].v[e] = m2[e]; }
+  __syncthreads();
+  for (int off = kBnThreads / 2; off >= g.lpr; off >>= 1) {
+    if (tid < off) {
+      chan_merge(n, mean, m2, sh_n[tid + off], sh_mean[tid + off].v, sh_m2[tid + off].v);
+      sh_n[tid] = n;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { sh_mean[tid].v[e] = mean[e]; sh_m2[tid].v[e] = m2[e]; }
+    }
+    __syncthreads();
+  }
+  if (rl == 0 && active) {
+    float* o = part + (long long)blockIdx.x * 2 * g.c + (long long)cgi * 4;
+    store4(o, mean);
+    store4(o + g.c, m2);
+  }
+}
+
+// ---- forward, pass 2: one workgroup per 4 channels merges the slices: thread t its slices 4t .. 4t + 3 as a tree, then the threads ----
+// writes mean and var (and the moving statistics, in place)
+__global__ __launch_bounds__(kBnThreads) void bn_stats_final_kernel(BnGeom g, const float* __restrict__ part, float* __restrict__ mean_out,
+                                                                    float* __restrict__ var_out, float* moving_mean, float* moving_var,
+                                                                    float decay) {
+  __shared__ float sh_n[kBnThreads];
+  __shared__ Stat4 sh_mean[kBnThreads], sh_m2[kBnThreads];
+  const int tid = threadIdx.x;
+  const long long ch = (long long)blockIdx.x * 4;
+  float n[4], mean[4][4], m2[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int s = tid * 4 + j;
+    n[j] = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { mean[j][e] = 0.f; m2[j][e] = 0.f; }
+    if (s < g.slices) {
+      n[j] = (float)slice_count(g, s);
+      load4(part + (long long)s * 2 * g.c + ch, mean[j]);
+      load4(part + (long long)s * 2 * g.c + g.c + ch, m2[j]);
+    }
+  }
+  chan_merge(n[0], mean[0], m2[0], n[1], mean[1], m2[1]);
+  chan_merge(n[2], mean[2], m2[2], n[3], mean[3], m2[3]);
+  chan_merge(n[0], mean[0], m2[0], n[2], mean[2], m2[2]);
+  sh_n[tid] = n[0];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { sh_mean[tid].v[e] = mean[0][e]; sh_m2[tid].v[e] = m2[0][e]; }
+  __syncthreads();
+  for (int off = kBnThreads / 2; off >= 1; off >>= 1) {
+    if (tid < off) {
+      chan_merge(n[0], mean[0], m2[0], sh_n[tid + off], sh_mean[tid + off].v, sh_m2[tid + off].v);
+      sh_n[tid] = n[0];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { sh_mean[tid].v[e] = mean[0][e]; sh_m2[tid].v[e] = m2[0][e]; }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    const float rows = (float)g.rows, bessel = g.rows > 1 ? (float)(g.rows - 1) : 1.f;
+    float var[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) var[e] = m2[0][e] / rows;
+    store4(mean_out + ch, mean[0]);
+    store4(var_out + ch, var);
+    if (moving_mean != nullptr) {
+      const float keep = decay, take = 1.f - decay;
+      float mm[4], mv[4];
+      load4(moving_mean + ch, mm);
+      load4(moving_var + ch, mv);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        mm[e] = keep * mm[e] + take * mean[0][e];
+        mv[e] = keep * mv[e] + take * (m2[0][e] / bessel);
+      }
+      store4(moving_mean + ch, mm);
+      store4(moving_var + ch, mv);
+    }
+  }
+}
+
+// ---- forward, pass 3: y = round(act(gamma (xs - mean) rstd + beta)) -------------------------------------------------------------------
+template <bool BF16, bool RELU>
+__global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, const float* __restrict__ mean,
+                                                              const float* __restrict__ var, float eps, float* __restrict__ y) {
+  const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
+  const int cgi = blockIdx.y * g.lpr + gl;
+  const long long cnt = slice_count(g, blockIdx.x);
+  if (cgi >= g.cg || rl >= cnt) return;
+  const long long ch = (long long)cgi * 4;
+  float ga[4], be[4], mu[4], rstd[4];
+  load4(gamma + ch, ga);
+  load4(beta + ch, be);
+  load4(mean + ch, mu);
+  load4(var + ch, rstd);
+#pragma unroll
+  for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(rstd[e] + eps);
+  const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+  const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
+#pragma unroll 4
+  for (int i = 0; i < mine; ++i) {
+    float v[4], o[4];
+    load4(x + base + i * step, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
+      float t = ga[e] * xhat + be[e];
+      if (RELU) t = t > 0.f ? t : (t == t ? 0.f : t);          // NaN stays NaN
+      o[e] = bn_round<BF16>(t);
+    }
+    store4(y + base + i * step, o);
+  }
+}
+
+// ---- backward, pass 1: per slice sum(dz) and sum(dz xhat) -> part [slices][2][c] -------------------------------------------------------
+template <bool BF16, bool RELU>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ y,
+                                                                 const float* __restrict__ dy, const float* __restrict__ mean,
+                                                                 const float* __restrict__ var, float eps, float* __restrict__ part) {
+  __shared__ Stat4 sh_b[kBnThreads], sh_g[kBnThreads];
+  const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
+  const int cgi = blockIdx.y * g.lpr + gl;
+  const bool active = cgi < g.cg;
+  const long long cnt = slice_count(g, blockIdx.x);
+  float sb[4] = {0.f, 0.f, 0.f, 0.f}, sg[4] = {0.f, 0.f, 0.f, 0.f};
+  if (active && rl < cnt) {
+    const long long ch = (long long)cgi * 4;
+    float mu[4], rstd[4];
+    load4(mean + ch, mu);
+    load4(var + ch, rstd);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(rstd[e] + eps);
+    const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+    const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
+#pragma unroll 4
+    for (int i = 0; i < mine; ++i) {
+      float v[4], d[4], m[4] = {1.f, 1.f, 1.f, 1.f};
+      load4(x + base + i * step, v);
+      load4(dy + base + i * step, d);
+      if (RELU) load4(y + base + i * step, m);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float dz = bn_round<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
+        const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
+        sb[e] += dz;
+        sg[e] += dz * xhat;
+      }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < 4; ++e) { sh_b[tid].v[e] = sb[e]; sh_g[tid].v[e] = sg[e]; }
+  __syncthreads();
+  for (int off = kBnThreads / 2; off >= g.lpr; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sb[e] += sh_b[tid + off].v[e];
+        sg[e] += sh_g[tid + off].v[e];
+        sh_b[tid].v[e] = sb[e];
+        sh_g[tid].v[e] = sg[e];
+      }
+    }
+    __syncthreads();
+  }
+  if (rl == 0 && active) {
+    float* o = part + (long long)blockIdx.x * 2 * g.c + (long long)cgi * 4;
+    store4(o, sb);
+    store4(o + g.c, sg);
+  }
+}
+
+// ---- backward, pass 2: the slices' sums behind the tree of bn_stats_final_kernel -> fin [2][c] (what pass 3 reads), dbeta, dgamma -----
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_final_kernel(BnGeom g, const float* __restrict__ part, float* __restrict__ fin,
+                                                                  float* dbeta, float* dgamma) {
+  __shared__ Stat4 sh_b[kBnThreads], sh_g[kBnThreads];
+  const int tid = threadIdx.x;
+  const long long ch = (long long)blockIdx.x * 4;
+  float b[4][4], q[4][4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int s = tid * 4 + j;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { b[j][e] = 0.f; q[j][e] = 0.f; }
+    if (s < g.slices) {
+      load4(part + (long long)s * 2 * g.c + ch, b[j]);
+      load4(part + (long long)s * 2 * g.c + g.c + ch, q[j]);
+    }
+  }
+  float sb[4], sg[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    sb[e] = (b[0][e] + b[1][e]) + (b[2][e] + b[3][e]);
+    sg[e] = (q[0][e] + q[1][e]) + (q[2][e] + q[3][e]);
+    sh_b[tid].v[e] = sb[e];
+    sh_g[tid].v[e] = sg[e];
+  }
+  __syncthreads();
+  for (int off = kBnThreads / 2; off >= 1; off >>= 1) {
+    if (tid < off) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        sb[e] += sh_b[tid + off].v[e];
+        sg[e] += sh_g[tid + off].v[e];
+        sh_b[tid].v[e] = sb[e];
+        sh_g[tid].v[e] = sg[e];
+      }
+    }
+    __syncthreads();
+  }
+  if (tid == 0) {
+    store4(fin + ch, sb);
+    store4(fin + g.c + ch, sg);
+    if (dbeta != nullptr) store4(dbeta + ch, sb);
+    if (dgamma != nullptr) store4(dgamma + ch, sg);
+  }
+}
+
+// ---- backward, pass 3: dx = round(gamma rstd (dz - dbeta / M - xhat dgamma / M)) -------------------------------------------------------
+template <bool BF16, bool RELU>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ y,
+                                                               const float* __restrict__ dy, const float* __restrict__ gamma,
+                                                               const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                               const float* __restrict__ fin, float* __restrict__ dx) {
+  const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
+  const int cgi = blockIdx.y * g.lpr + gl;
+  const long long cnt = slice_count(g, blockIdx.x);
+  if (cgi >= g.cg || rl >= cnt) return;
+  const long long ch = (long long)cgi * 4;
+  float scale[4], mu[4], rstd[4], mb[4], mg[4];
+  load4(gamma + ch, scale);
+  load4(mean + ch, mu);
+  load4(var + ch, rstd);
+  load4(fin + ch, mb);
+  load4(fin + g.c + ch, mg);
+  const float rows = (float)g.rows;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    rstd[e] = 1.f / sqrtf(rstd[e] + eps);
+    scale[e] = scale[e] * rstd[e];
+    mb[e] = mb[e] / rows;
+    mg[e] = mg[e] / rows;
+  }
+  const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+  const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
+#pragma unroll 4
+  for (int i = 0; i < mine; ++i) {
+    float v[4], d[4], m[4] = {1.f, 1.f, 1.f, 1.f}, o[4];
+    load4(x + base + i * step, v);
+    load4(dy + base + i * step, d);
+    if (RELU) load4(y + base + i * step, m);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const float dz = bn_round<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
+      const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
+      o[e] = bn_round<BF16>(scale[e] * ((dz - mb[e]) - xhat * mg[e]));
+    }
+    store4(dx + base + i * step, o);
+  }
+}
+
+int pow2_ceil_log2(int64_t v) {
+  int l = 0;
+  while (((int64_t)1 << l) < v) ++l;
+  return l;
+}
+
+// descriptor checks + the geometry + the workspace layout; `what` starts every message
+int plan_bn(const char* what, const ron_bn_desc* d, BnPlan* P) {
+  RON_REQUIRE(d != nullptr, "%s: NULL descriptor", what);
+  RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "%s: dtype %d: bf16 or fp16 only", what, d->dtype);
+  RON_REQUIRE(d->n >= 1 && d->h >= 1 && d->w >= 1, "%s: empty tensor (n %d, h %d, w %d)", what, d->n, d->h, d->w);
+  RON_REQUIRE(d->c >= 8 && d->c % 8 == 0, "%s: c %d must be a multiple of 8", what, d->c);
+  RON_REQUIRE(d->relu == 0 || d->relu == 1, "%s: relu %d must be 0 or 1", what, d->relu);
+  RON_REQUIRE(std::isfinite(d->eps) && d->eps >= 0.f, "%s: eps %g must be finite and >= 0", what, (double)d->eps);
+  RON_REQUIRE(d->decay >= 0.f && d->decay <= 1.f, "%s: decay %g must lie in [0, 1]", what, (double)d->decay);
+  const int64_t rows = (int64_t)d->n * d->h * d->w;
+  RON_REQUIRE(rows <= kBnMaxRows, "%s: n h w = %lld rows, at most 2^24 (the count must be exact in fp32)", what, (long long)rows);
+  P->rows = rows;
+  P->c = d->c;
+  P->cg = d->c / 4;
+  P->lpr_log2 = std::min(6, pow2_ceil_log2(P->cg));
+  P->lpr = 1 << P->lpr_log2;
+  P->rpb = kBnThreads / P->lpr;
+  P->tiles = (P->cg + P->lpr - 1) / P->lpr;
+  RON_REQUIRE(P->tiles <= 65535, "%s: c %d is beyond the grid", what, d->c);
+  const int64_t per = (rows + kBnMaxSlices - 1) / kBnMaxSlices;
+  P->slice_rows = std::max<int64_t>((int64_t)P->rpb * 4, (int64_t)1 << pow2_ceil_log2(per));
+  P->slices = (int)((rows + P->slice_rows - 1) / P->slice_rows);
+  P->off_part = 0;
+  P->off_fin = align_up((int64_t)P->slices * 2 * d->c * 4, 256);
+  P->total = P->off_fin + align_up((int64_t)2 * d->c * 4, 256);
+  return RON_OK;
+}
+
+int check_workspace(const char* what, const BnPlan& P, void* workspace, int64_t workspace_bytes) {
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (ron_batchnorm_workspace_bytes)",
+              what, (long long)workspace_bytes, (long long)P.total);
+  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
+  return RON_OK;
+}
+
+template <bool BF16, bool RELU>
+int run_forward(const ron_bn_desc* d, const BnPlan& P, const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                float* var, float* moving_mean, float* moving_var, char* ws, hipStream_t s) {
+  const BnGeom& g = P;
+  float* part = reinterpret_cast<float*>(ws + P.off_part);
+  const dim3 grid(P.slices, P.tiles);
+  RON_LAUNCH(bn_stats_kernel<BF16>, grid, dim3(kBnThreads), 0, s, g, x, part);
+  RON_LAUNCH(bn_stats_final_kernel, dim3(P.cg), dim3(kBnThreads), 0, s, g, part, mean, var, moving_mean, moving_var, d->decay);
+  RON_LAUNCH((bn_apply_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, gamma, beta, mean, var, d->eps, y);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+template <bool BF16, bool RELU>
+int run_backward(const ron_bn_desc* d, const BnPlan& P, const float* x, const float* y, const float* dy, const float* gamma,
+                 const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, char* ws, hipStream_t s) {
+  const BnGeom& g = P;
+  float* part = reinterpret_cast<float*>(ws + P.off_part);
+  float* fin = reinterpret_cast<float*>(ws + P.off_fin);
+  const dim3 grid(P.slices, P.tiles);
+  RON_LAUNCH((bn_bwd_sums_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, y, dy, mean, var, d->eps, part);
+  RON_LAUNCH(bn_bwd_final_kernel, dim3(P.cg), dim3(kBnThreads), 0, s, g, part, fin, dbeta, dgamma);
+  if (dx != nullptr) RON_LAUNCH((bn_bwd_dx_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, y, dy, gamma, mean, var, d->eps, fin, dx);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+}  // namespace
+}  // namespace ron
+
+extern "C" int64_t ron_batchnorm_workspace_bytes(const ron_bn_desc* d) {
+  ron::BnPlan P;
+  if (ron::plan_bn("batchnorm", d, &P) != RON_OK) return -1;
+  return P.total;
+}
+
+extern "C" int ron_batchnorm_train_nhwc(const ron_bn_desc* d, const float* x, const float* gamma, const float* beta, float* y, float* mean,
+                                        float* var, float* moving_mean, float* moving_var, void* workspace, int64_t workspace_bytes,
+                                        void* stream) {
+  using namespace ron;
+  const char* what = "batchnorm forward";
+  BnPlan P;
+  if (int rc = plan_bn(what, d, &P)) return rc;
+  RON_REQUIRE(x != nullptr && gamma != nullptr && beta != nullptr && y != nullptr && mean != nullptr && var != nullptr,
+              "%s: x, gamma, beta, y, mean and var must not be NULL", what);
+  RON_REQUIRE((moving_mean == nullptr) == (moving_var == nullptr), "%s: moving_mean and moving_var come together (both, or both NULL)", what);
+  RON_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)var |
+                (uintptr_t)moving_mean | (uintptr_t)moving_var) & 15) == 0,
+              "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
+  if (int rc = check_workspace(what, P, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  if (d->dtype == RON_DTYPE_BF16)
+    return d->relu ? run_forward<true, true>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s)
+                   : run_forward<true, false>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s);
+  return d->relu ? run_forward<false, true>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s)
+                 : run_forward<false, false>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s);
+}
+
+extern "C" int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x, const float* y, const float* dy, const float* gamma,
+                                           const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, void* workspace,
+                                           int64_t workspace_bytes, void* stream) {
+  using namespace ron;
+  const char* what = "batchnorm backward";
+  BnPlan P;
+  if (int rc = plan_bn(what, d, &P)) return rc;
+  RON_REQUIRE(x != nullptr && dy != nullptr && gamma != nullptr && mean != nullptr && var != nullptr,
+              "%s: x, dy, gamma, mean and var must not be NULL", what);
+  RON_REQUIRE(!d->relu || y != nullptr, "%s: relu is set and y is NULL (the mask is y > 0)", what);
+  RON_REQUIRE((((uintptr_t)x | (uintptr_t)(d->relu ? y : nullptr) | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)mean | (uintptr_t)var |
+                (uintptr_t)dx | (uintptr_t)dgamma | (uintptr_t)dbeta) & 15) == 0,
+              "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
+  if (int rc = check_workspace(what, P, workspace, workspace_bytes)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  if (d->dtype == RON_DTYPE_BF16)
+    return d->relu ? run_backward<true, true>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s)
+                   : run_backward<true, false>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s);
+  return d->relu ? run_backward<false, true>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s)
+                 : run_backward<false, false>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s);
+}

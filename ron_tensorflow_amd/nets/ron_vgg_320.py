@@ -249,7 +249,8 @@ class RONNet(object):
             scope='ron_320_vgg', end_points=('block1', 'block2', 'block3', 'block4', 'block5', 'block6', 'block7')):
         """RON network (nets/ron_vgg_320.py:136-154).  Inference only: `is_training` / `dropout_keep_prob` /
         `reuse` / `scope` are accepted for signature compatibility (the reference's dropout is commented out,
-        :480, and BatchNorm runs on its moving statistics).  Returns the reference's 6-tuple
+        :480, and BatchNorm runs on its moving statistics; the training-mode operator is ops.batchnorm_train_nhwc /
+        ops.batchnorm_backward_nhwc / ops.batchnorm_nhwc_fn, outside this graph).  Returns the reference's 6-tuple
         (predictions, logits, objness_pred, objness_logits, localisations, end_points)."""
         nchw = getattr(self, '_data_format', 'NHWC') == 'NCHW'
         if nchw:                                       # images as preprocess_for_eval(..., data_format='NCHW') hands them over

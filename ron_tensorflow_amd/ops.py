@@ -684,3 +684,111 @@ def conv2d_k2s2_nhwc_fn(x, w, bias, relu=True, transpose=False, dtype='bf16'):
     synchronises: tests and small experiments; its transposed form wants Cout a multiple of 128); the backward is ONE
     ron_conv2d_k2s2_backward_nhwc call on the current stream, computing only the gradients autograd asks for."""
     return _Conv2dK2s2NhwcFn.apply(x, w, bias, relu, transpose, dtype)
+
+
+# --------------------------------------------------------------------------- #
+# training-mode batch normalisation (ron_batchnorm_train_nhwc, ron_batchnorm_backward_nhwc): real entry points like the convolution
+# backward - they enqueue on the current stream and never synchronise
+# --------------------------------------------------------------------------- #
+def _bn_desc(n, h, w, c, relu, eps, decay, dtype):
+    return _lib.BnDesc(n, h, w, c, _lib.DTYPES[dtype], int(relu), float(eps), float(decay))
+
+
+def _bn_vectors(c, dev, **named):
+    """Per-channel arguments made contiguous and checked: float32 GPU tensors [c] (None stays None)."""
+    out = []
+    for name, t in named.items():
+        if t is not None:
+            t = t.contiguous()
+            assert t.is_cuda and t.device == dev and t.dtype == torch.float32 and tuple(t.shape) == (c,), \
+                '%s must be a float32 GPU tensor [%d]' % (name, c)
+        out.append(t)
+    return out
+
+
+def batchnorm_workspace_bytes(n, h, w, c, relu=True, eps=1e-5, decay=0.997, dtype='bf16'):
+    """Bytes of workspace batchnorm_train_nhwc and batchnorm_backward_nhwc need (host arithmetic; raises on a refused descriptor)."""
+    return _desc_workspace_bytes('batchnorm', _bn_desc(n, h, w, c, relu, eps, decay, dtype))
+
+
+def batchnorm_train_nhwc(x, gamma, beta, moving_mean=None, moving_var=None, relu=True, eps=1e-5, decay=0.997, dtype='bf16',
+                         workspace=None):
+    """Batch normalisation with batch statistics: (y, mean, var), new GPU fp32 tensors.
+
+    x [N,H,W,C] GPU fp32 (a convolution's output; it is rounded to `dtype`), gamma and beta [C].  mean and the BIASED var [C] are
+    those of the batch; y = round(act(gamma (xs - mean) / sqrt(var + eps) + beta)) comes back as storage-type values in fp32.
+    `moving_mean` / `moving_var` [C], both or neither, are updated IN PLACE: m = decay m + (1 - decay) statistic, the variance
+    Bessel-corrected (slim.batch_norm's decay; torch's momentum is 1 - decay).  `workspace`: a uint8 GPU tensor of at least
+    batchnorm_workspace_bytes(...) bytes, or None for the cached per-device, per-stream buffer."""
+    x = x.contiguous()
+    dev = x.device
+    assert x.is_cuda and x.dtype == torch.float32 and x.dim() == 4
+    n, h, w, c = x.shape
+    gamma, beta = _bn_vectors(c, dev, gamma=gamma, beta=beta)
+    for name, t in (('moving_mean', moving_mean), ('moving_var', moving_var)):        # updated in place: no copies
+        assert t is None or (t.is_cuda and t.dtype == torch.float32 and tuple(t.shape) == (c,) and t.is_contiguous()), \
+            '%s must be a contiguous float32 GPU tensor [%d]' % (name, c)
+    d = _bn_desc(n, h, w, c, relu, eps, decay, dtype)
+    ws = _sized_workspace(dev, lib().ron_batchnorm_workspace_bytes(C.byref(d))) if workspace is None else workspace
+    y = torch.empty_like(x)
+    mean = torch.empty((c,), dtype=torch.float32, device=dev)
+    var = torch.empty((c,), dtype=torch.float32, device=dev)
+    check(lib().ron_batchnorm_train_nhwc(C.byref(d), ptr(x), ptr(gamma), ptr(beta), ptr(y), ptr(mean), ptr(var), ptr(moving_mean),
+                                         ptr(moving_var), ptr(ws), int(ws.numel()), current_stream()))
+    return y, mean, var
+
+
+def batchnorm_backward_nhwc(x, y, dy, gamma, mean, var, relu=True, eps=1e-5, dtype='bf16', need=('dx', 'dgamma', 'dbeta'), workspace=None):
+    """Gradients of batchnorm_train_nhwc: (dx, dgamma, dbeta), None for those not in `need`.
+
+    x, dy (and y, the forward's output: required with `relu`, the mask is y > 0) [N,H,W,C] GPU fp32; gamma and the forward's mean
+    and var [C].  dx comes back as storage-type values in fp32 - the dy of conv2d_backward_nhwc(relu=False) for the convolution in
+    front - dgamma and dbeta [C] as unrounded fp32 sums in a fixed order."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    assert x.is_cuda and dy.is_cuda and x.dtype == torch.float32 and dy.dtype == torch.float32 and x.shape == dy.shape and x.dim() == 4
+    n, h, w, c = x.shape
+    if relu and y is None:
+        raise _lib.RonError('batchnorm_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
+    if y is not None:
+        y = y.contiguous()
+        assert y.is_cuda and y.dtype == torch.float32 and y.shape == x.shape
+    gamma, mean, var = _bn_vectors(c, dev, gamma=gamma, mean=mean, var=var)
+    unknown = set(need) - {'dx', 'dgamma', 'dbeta'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    d = _bn_desc(n, h, w, c, relu, eps, 0.0, dtype)
+    ws = _sized_workspace(dev, lib().ron_batchnorm_workspace_bytes(C.byref(d))) if workspace is None else workspace
+    names = [name for name in ('dx', 'dgamma', 'dbeta') if name in need]
+    likes = {'dx': x, 'dgamma': gamma, 'dbeta': gamma}
+    grads = _grad_outputs(None, names, tuple([likes[name]] for name in names), dev) if names else ()
+    got = {name: g[0] for name, g in zip(names, grads)}
+    dx, dgamma, dbeta = got.get('dx'), got.get('dgamma'), got.get('dbeta')
+    check(lib().ron_batchnorm_backward_nhwc(C.byref(d), ptr(x), ptr(y if relu else None), ptr(dy), ptr(gamma), ptr(mean), ptr(var),
+                                            ptr(dx), ptr(dgamma), ptr(dbeta), ptr(ws), int(ws.numel()), current_stream()))
+    return dx, dgamma, dbeta
+
+
+class _BatchNormNhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, beta, moving_mean, moving_var, relu, eps, decay, dtype):
+        y, mean, var = batchnorm_train_nhwc(x.detach(), gamma.detach(), beta.detach(), moving_mean, moving_var, relu=relu, eps=eps,
+                                            decay=decay, dtype=dtype)
+        ctx.save_for_backward(x, gamma, y, mean, var)
+        ctx.cfg = (relu, eps, dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, y, mean, var = ctx.saved_tensors
+        relu, eps, dtype = ctx.cfg
+        need = tuple({'dx': 'dx', 'dw': 'dgamma', 'db': 'dbeta'}[name] for name in _needed_grads(ctx, True))     # (x, gamma, beta)
+        dx, dgamma, dbeta = (batchnorm_backward_nhwc(x, y, dy, gamma, mean, var, relu=relu, eps=eps, dtype=dtype, need=need) if need
+                             else (None, None, None))
+        return dx, dgamma, dbeta, None, None, None, None, None, None
+
+
+def batchnorm_nhwc_fn(x, gamma, beta, moving_mean, moving_var, relu=True, eps=1e-5, decay=0.997, dtype='bf16'):
+    """batchnorm_train_nhwc as a torch.autograd.Function: x [N,H,W,C], gamma and beta [C] GPU fp32 tensors; moving_mean /
+    moving_var [C] (both, or both None) are plain buffers updated in place by the forward.  Forward and backward are ONE library
+    call each on the current stream; the backward computes only the gradients autograd asks for."""
+    return _BatchNormNhwcFn.apply(x, gamma, beta, moving_mean, moving_var, relu, eps, decay, dtype)

@@ -7,6 +7,7 @@
 // which walks launch_conv / launch_conv_group up to the launch itself (tile counts, split-K slices, tile order, entry lists, the
 // post-processing's workspace layout) and ron_clone (a second slot taking over the plans).  Index tables overrun or integer
 // overflow in any of it ends the run with a sanitizer report and a non-zero exit code.
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -235,6 +236,72 @@ static int op_backward_arguments() {
   return 0;
 }
 
+// ron_batchnorm_train_nhwc and ron_batchnorm_backward_nhwc in the dry run: the shapes of tests/bn_cases.py (M around the rows of a wave,
+// of a workgroup and of a slice for 2, 18-of-32 and 64 lanes per row), the shapes tools/batchnorm_time.py times, the last accepted
+// row count, and every refusal; pointers are used for arithmetic only.
+static int batchnorm_arguments() {
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  auto desc = [](int n, int h, int w, int c, int dtype, int relu) {
+    ron_bn_desc d;
+    memset(&d, 0, sizeof d);
+    d.n = n; d.h = h; d.w = w; d.c = c; d.dtype = dtype; d.relu = relu; d.eps = 1e-5f; d.decay = 0.997f;
+    return d;
+  };
+  struct Shape { int n, h, w, c; };
+  std::vector<Shape> shapes = {{1, 1, 1, 8}, {1, 1, 2, 8}, {2, 5, 5, 512}, {2, 40, 40, 512}, {1, 64, 64, 8}, {1, 32, 32, 8}, {1, 8, 8, 72},
+                               {2, 4, 4, 1024}, {1, 4096, 4096, 8}, {4096, 64, 64, 8}, {1, 1, 1, 262144}};
+  for (int m : {31, 32, 33, 127, 128, 129, 511, 512, 513, 1027}) shapes.push_back({1, 1, m, 8});
+  for (int m : {1, 2, 3, 7, 8, 9, 31, 32, 33, 67}) shapes.push_back({1, 1, m, 72});
+  for (int m : {1, 2, 3, 4, 5, 15, 16, 17, 35}) shapes.push_back({1, 1, m, 1024});
+  for (int s : {40, 20, 10, 5})
+    for (int c : {512, 1024}) shapes.push_back({32, s, s, c});
+  for (const Shape& p : shapes) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      for (int relu : {0, 1}) {
+        const ron_bn_desc d = desc(p.n, p.h, p.w, p.c, dtype, relu);
+        const int64_t bytes = ron_batchnorm_workspace_bytes(&d);
+        if (bytes <= 0 || bytes % 256 != 0) return 1;
+        float* const y = relu ? f : nullptr;
+        CHECK(ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, f, f, ws, bytes, nullptr));
+        CHECK(ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, nullptr, nullptr, ws, bytes, nullptr));
+        CHECK(ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, f, f, f, ws, bytes, nullptr));
+        CHECK(ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, nullptr, f, f, ws, bytes, nullptr));
+        CHECK(ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, f, nullptr, nullptr, ws, bytes, nullptr));
+        CHECK(ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, nullptr, nullptr, nullptr, ws, bytes, nullptr));
+        // the calls it refuses: a short, misaligned or missing workspace, a misaligned or missing tensor, half of the moving pair
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, f, f, static_cast<char*>(ws) + 16, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, f, f, nullptr, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f + 1, f, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f + 2, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, nullptr, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, f, nullptr, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_train_nhwc(&d, f, f, f, f, f, f, nullptr, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_backward_nhwc(&d, f, y, f + 1, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_backward_nhwc(&d, f, y, f, f, f, f, f + 1, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_batchnorm_backward_nhwc(&d, nullptr, y, f, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (relu && ron_batchnorm_backward_nhwc(&d, f, nullptr, f, f, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      }
+    }
+    // the descriptors it refuses, through all three entries
+    ron_bn_desc bad[16];
+    for (ron_bn_desc& b : bad) b = desc(p.n, p.h, p.w, p.c, RON_DTYPE_BF16, 1);
+    bad[0].dtype = RON_DTYPE_F32; bad[1].dtype = RON_DTYPE_F16X3; bad[2].c += 4; bad[3].c = 0; bad[4].n = 0; bad[5].h = -1; bad[6].w = 0;
+    bad[7].relu = 2; bad[8].relu = -1; bad[9].eps = -1e-5f; bad[10].eps = NAN; bad[11].eps = INFINITY; bad[12].decay = -0.5f;
+    bad[13].decay = 1.5f; bad[14].decay = NAN; bad[15].n = 65536; bad[15].h = 65536;
+    for (const ron_bn_desc& b : bad) {
+      if (ron_batchnorm_workspace_bytes(&b) != -1) return 1;
+      if (ron_batchnorm_train_nhwc(&b, f, f, f, f, f, f, f, f, ws, (int64_t)1 << 40, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_batchnorm_backward_nhwc(&b, f, f, f, f, f, f, f, f, f, ws, (int64_t)1 << 40, nullptr) != RON_ERR_INVALID) return 1;
+    }
+  }
+  const ron_bn_desc over = desc(4097, 64, 64, 8, RON_DTYPE_BF16, 1);          // 2^24 + 4096 rows: the count would not be exact in fp32
+  if (ron_batchnorm_workspace_bytes(&over) != -1 || ron_batchnorm_workspace_bytes(nullptr) != -1) return 1;
+  return 0;
+}
+
 // The argument envelope of ron_conv_desc (include/ron_hip.h): for every field limit - 1 and limit plan, limit + 1 is refused, through
 // ron_conv_plan and the backward's workspace query; zeros, negatives and flags other than 0 / 1 are refused before any arithmetic on
 // them (a stride of 0 used to reach a division).  The shapes are those of tests/conv_envelope_cases.py.
@@ -369,6 +436,10 @@ int main(int argc, char** argv) {
   }
   if (op_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_maxpool2x2_backward_nhwc / ron_conv2d_k2s2_backward_nhwc planning / argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (batchnorm_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_batchnorm_train_nhwc / ron_batchnorm_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
   if (conv_envelope()) {
