@@ -761,6 +761,70 @@ int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x, const floa
                                 const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, void* workspace,
                                 int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * The training update: what ron_net.py:354-381 does with the gradients.  ron_optimizer_step applies ONE rule to a whole list
+ * of variables - TensorFlow 1.x's dense apply kernels, the ones tf_utils.configure_optimizer instantiates (tf_utils.py:126-171;
+ * the drivers' default is momentum, 0.9) - with the gradient of slim's l2_regularizer(weight_decay) folded into the gradient,
+ * as optimizer.apply_gradients on tf.losses.get_total_loss() does (ron_arg_scope puts that regulariser on every conv /
+ * conv_transpose `weights`, nets/ron_vgg_320.py:604-612).  A real entry point like the convolution backward and the batch
+ * normalisation: it enqueues on `stream`, allocates nothing, never synchronises, honours the dry-run mode, assumes nothing
+ * about the workspace's contents and uses no atomics; the same inputs give the same bytes.
+ *
+ * `t` is a HOST array of n entries whose pointers are DEVICE fp32 (var, grad, slot0, slot1: `count` elements each); the
+ * pointers may differ from call to call (gradient buffers are the caller's).  The table reaches the kernel by value in the
+ * kernel arguments (under 4 KiB per launch): no device-side table, no upload.  A list longer than one table is cut into
+ * consecutive launches of the same kernel; the number of launches and the cut are a function of the counts alone.
+ *
+ * Everything is fp32, ONE rounded operation per arithmetic sign, in exactly the order written; 1 - decay, 1 - beta1 and
+ * 1 - beta2 are formed once on the host in fp32; division and square root are the correctly rounded ones:
+ *   g' = g + weight_decay * w    when the tensor's weight_decay != 0, else g' = g (the bits of g: nothing is multiplied by 0)
+ *   RON_OPT_SGD       w = w - lr * g'
+ *   RON_OPT_MOMENTUM  m = momentum * m + g';  w = w - lr * m                                  (slot0 = m; use_nesterov=False)
+ *   RON_OPT_RMSPROP   ms = ms + (1 - decay) * (g' * g' - ms);  mom = momentum * mom + (lr * g') / sqrt(ms + epsilon);
+ *                     w = w - mom                                                             (slot0 = ms, slot1 = mom)
+ *   RON_OPT_ADAM      m = m + (1 - beta1) * (g' - m);  v = v + (1 - beta2) * (g' * g' - v);
+ *                     w = w - (lr_t * m) / (sqrt(v) + epsilon)                                (slot0 = m, slot1 = v)
+ *                     lr_t = lr * sqrt(1 - beta2^step) / (1 - beta1^step) in double on the host, rounded to fp32 once
+ * weight_decay * w is the gradient of l2_regularizer(weight_decay)(w) = weight_decay * sum(w^2) / 2; a caller passes 0 for
+ * biases, gamma and beta, as slim does.  The slots are the caller's, initial values included (TensorFlow: zeros; RMSProp's ms
+ * ones): the call never initialises them.  Slots the rule does not need are ignored.
+ *
+ * reg_loss (DEVICE, one float; may be NULL) receives sum over tensors of (0.5f * weight_decay) * sum(w^2) of the weights
+ * BEFORE the update - the regularisation part of the reference's total_loss - as an fp32 sum in a fixed order that depends on
+ * the counts alone; tensors with weight_decay == 0 contribute nothing and are not read for it.  With reg_loss == NULL the
+ * workspace is not touched and no reduction is launched.
+ *
+ * Accepted: n from 1 to 4096; count >= 1 (at most 2^40, and 2^22 work units per list); every tensor pointer the rule uses
+ * non-NULL and 16-byte aligned (the counts are arbitrary: no access touches a byte outside [ptr, ptr + count), so packed
+ * tensors may start 16 bytes behind a neighbour's last whole vector); weight_decay >= 0 and finite; learning_rate finite;
+ * momentum, decay, beta1, beta2 in [0, 1], beta1 and beta2 below 1 for Adam; epsilon >= 0 and finite; step >= 1 for Adam
+ * (ignored otherwise); with reg_loss the workspace 256-byte aligned and at least ron_optimizer_workspace_bytes(t, n) bytes
+ * (host arithmetic on the counts; -1 + ron_last_error() when refused).  Refused as well: a var that appears twice in the list,
+ * a var that equals its own grad or slot, an unknown rule.  Every refusal is RON_ERR_INVALID with a message of its own, before
+ * any HIP call.  ron_optimizer_plan reports, for a list's counts, out[0] the launches of the update kernel, out[1] the work
+ * units, out[2] the table entries per launch and out[3] the elements per work unit.
+ * ---------------------------------------------------------------------------------------- */
+typedef enum { RON_OPT_SGD = 0, RON_OPT_MOMENTUM = 1, RON_OPT_RMSPROP = 2, RON_OPT_ADAM = 3 } ron_opt_rule;
+typedef struct {
+  int32_t rule;      /* ron_opt_rule */
+  float momentum;    /* momentum and rmsprop */
+  float decay;       /* rmsprop */
+  float beta1, beta2;
+  float epsilon;     /* rmsprop and adam */
+} ron_opt_cfg;
+typedef struct {
+  float* var;
+  const float* grad;
+  float* slot0;
+  float* slot1;
+  int64_t count;
+  float weight_decay;
+} ron_opt_tensor;
+int ron_optimizer_plan(const ron_opt_tensor* t, int n, int64_t out[4]);
+int64_t ron_optimizer_workspace_bytes(const ron_opt_tensor* t, int n);
+int ron_optimizer_step(const ron_opt_cfg* cfg, const ron_opt_tensor* t, int n, float learning_rate, int64_t step, float* reg_loss,
+                       void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -114,6 +114,19 @@ class BnDesc(C.Structure):
                 ('eps', C.c_float), ('decay', C.c_float)]
 
 
+OPT_RULES = {'sgd': 0, 'momentum': 1, 'rmsprop': 2, 'adam': 3}
+
+
+class OptCfg(C.Structure):
+    _fields_ = [('rule', C.c_int32), ('momentum', C.c_float), ('decay', C.c_float), ('beta1', C.c_float), ('beta2', C.c_float),
+                ('epsilon', C.c_float)]
+
+
+class OptTensor(C.Structure):
+    _fields_ = [('var', C.c_void_p), ('grad', C.c_void_p), ('slot0', C.c_void_p), ('slot1', C.c_void_p), ('count', C.c_int64),
+                ('weight_decay', C.c_float)]
+
+
 # every symbol include/ron_hip.h declares: (restype, argtypes)
 _P = C.c_void_p
 SIGNATURES = {
@@ -197,6 +210,9 @@ SIGNATURES = {
     'ron_batchnorm_workspace_bytes': (C.c_int64, [C.POINTER(BnDesc)]),
     'ron_batchnorm_train_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_batchnorm_backward_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_optimizer_plan': (C.c_int, [C.POINTER(OptTensor), C.c_int, C.POINTER(C.c_int64)]),
+    'ron_optimizer_workspace_bytes': (C.c_int64, [C.POINTER(OptTensor), C.c_int]),
+    'ron_optimizer_step': (C.c_int, [C.POINTER(OptCfg), C.POINTER(OptTensor), C.c_int, C.c_float, C.c_int64, _P, _P, C.c_int64, _P]),
 }
 
 _lib = None

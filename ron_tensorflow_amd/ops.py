@@ -792,3 +792,69 @@ def batchnorm_nhwc_fn(x, gamma, beta, moving_mean, moving_var, relu=True, eps=1e
     moving_var [C] (both, or both None) are plain buffers updated in place by the forward.  Forward and backward are ONE library
     call each on the current stream; the backward computes only the gradients autograd asks for."""
     return _BatchNormNhwcFn.apply(x, gamma, beta, moving_mean, moving_var, relu, eps, decay, dtype)
+
+
+# --------------------------------------------------------------------------- #
+# the training update (ron_optimizer_step): one rule applied to a whole list of variables, a real entry point like the batch
+# normalisation - it enqueues on the current stream and never synchronises
+# --------------------------------------------------------------------------- #
+def _opt_table(tensors, slots=2):
+    """The host table of ron_optimizer_step: `tensors` is a list of (var, grad, slot0, slot1, weight_decay), the first four float32
+    GPU tensors of one size (slots the rule does not use may be None).  Returns (table, n, device)."""
+    n = len(tensors)
+    table = (_lib.OptTensor * max(n, 1))()
+    dev = None
+    for i, (var, grad, slot0, slot1, wd) in enumerate(tensors):
+        used = (var, grad) + (slot0, slot1)[:slots]
+        for t in used:
+            assert t is not None and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == var.numel(), \
+                'tensor %d: var, grad and the slots the rule uses must be contiguous float32 GPU tensors of one size' % i
+            assert dev is None or t.device == dev, 'tensor %d lives on another device' % i
+            dev = t.device
+        p = [C.c_void_p(t.data_ptr()) if t is not None else None for t in (var, grad, slot0, slot1)]
+        table[i] = _lib.OptTensor(p[0], p[1], p[2] if slots >= 1 else None, p[3] if slots >= 2 else None, var.numel(), float(wd))
+    return table, n, dev
+
+
+def optimizer_plan(counts):
+    """(launches, work units, table entries per launch, elements per work unit) of ron_optimizer_step for a list of element counts."""
+    table = (_lib.OptTensor * max(len(counts), 1))()
+    for i, c in enumerate(counts):
+        table[i].count = int(c)
+    out = (C.c_int64 * 4)()
+    check(lib().ron_optimizer_plan(table, len(counts), out))
+    return tuple(int(v) for v in out)
+
+
+def optimizer_workspace_bytes(counts):
+    """Bytes of workspace optimizer_step needs for reg_loss (host arithmetic on the counts; raises on a refused list)."""
+    table = (_lib.OptTensor * max(len(counts), 1))()
+    for i, c in enumerate(counts):
+        table[i].count = int(c)
+    nbytes = lib().ron_optimizer_workspace_bytes(table, len(counts))
+    if nbytes < 0:
+        check(-1)
+    return int(nbytes)
+
+
+def optimizer_step(rule, tensors, learning_rate, step=1, momentum=0.9, decay=0.9, beta1=0.9, beta2=0.999, epsilon=0.0,
+                   want_reg_loss=False, workspace=None):
+    """ONE ron_optimizer_step on the current stream: `rule` ('sgd' | 'momentum' | 'rmsprop' | 'adam') applied IN PLACE to every entry
+    of `tensors`, a list of (var, grad, slot0, slot1, weight_decay) - float32 GPU tensors of one size each; slots the rule does not
+    use may be None (momentum: slot0 = m; rmsprop: slot0 = ms, slot1 = mom; adam: slot0 = m, slot1 = v).  g' = g + weight_decay w where
+    weight_decay != 0; TensorFlow 1.x's dense apply kernels in fp32, one rounding per operation (include/ron_hip.h).  `step` (>= 1)
+    is Adam's.  Returns the regularisation loss sum (weight_decay / 2) sum(w^2) of the weights before the update as a GPU scalar when
+    `want_reg_loss`, else None.  `workspace`: a uint8 GPU tensor of optimizer_workspace_bytes(...) bytes, or None for the cached
+    per-device, per-stream buffer (only touched with want_reg_loss)."""
+    if rule not in _lib.OPT_RULES:
+        raise _lib.RonError('optimizer_step: unknown rule %r (sgd, momentum, rmsprop, adam)' % (rule,))
+    code = _lib.OPT_RULES[rule]
+    table, n, dev = _opt_table(tensors, (0, 1, 2, 2)[code])
+    cfg = _lib.OptCfg(code, float(momentum), float(decay), float(beta1), float(beta2), float(epsilon))
+    reg, ws, nbytes = None, None, 0
+    if want_reg_loss and n:
+        ws = _sized_workspace(dev, lib().ron_optimizer_workspace_bytes(table, n)) if workspace is None else workspace
+        nbytes = int(ws.numel())
+        reg = torch.empty((), dtype=torch.float32, device=dev)
+    check(lib().ron_optimizer_step(C.byref(cfg), table, n, float(learning_rate), int(step), ptr(reg), ptr(ws), nbytes, current_stream()))
+    return reg

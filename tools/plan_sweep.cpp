@@ -302,6 +302,129 @@ static int batchnorm_arguments() {
   return 0;
 }
 
+// ron_optimizer_step in the dry run: the lists of tests/optim_cases.py (single tensors around the work unit, lists around the launch
+// table), the lists tools/optimizer_time.py times (the trainable variables of both RON-320 variants, from ron_variable_info), the
+// largest accepted list and every refusal; pointers are used for arithmetic only.
+static int optimizer_arguments() {
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  float* const reg = reinterpret_cast<float*>(uintptr_t(1) << 41);
+  auto table = [](const std::vector<int64_t>& counts) {
+    std::vector<ron_opt_tensor> t(counts.size());
+    for (size_t i = 0; i < counts.size(); ++i) {
+      float* const base = reinterpret_cast<float*>((uintptr_t(i) + 1) << 42);          // fake device addresses, 16-byte aligned, all distinct
+      t[i].var = base; t[i].grad = base + 4; t[i].slot0 = base + 8; t[i].slot1 = base + 12;
+      t[i].count = counts[i];
+      t[i].weight_decay = i % 2 == 0 ? 0.0005f : 0.f;
+    }
+    return t;
+  };
+  auto cfg_of = [](int rule) {
+    ron_opt_cfg c;
+    memset(&c, 0, sizeof c);
+    c.rule = rule; c.momentum = 0.9f; c.decay = 0.9f; c.beta1 = 0.9f; c.beta2 = 0.999f; c.epsilon = 1.f;
+    return c;
+  };
+  int64_t plan[4] = {0, 0, 0, 0};
+  {
+    ron_opt_tensor one;
+    memset(&one, 0, sizeof one);
+    one.count = 1;
+    CHECK(ron_optimizer_plan(&one, 1, plan));
+  }
+  const int64_t E = plan[2], U = plan[3];
+  if (E < 1 || U < 4 || U % 4 != 0 || E * 48 + 64 > 4096) return 1;
+  std::vector<std::vector<int64_t>> lists;
+  for (int64_t c : {(int64_t)1, (int64_t)3, (int64_t)4, (int64_t)5, U - 1, U, U + 1, 2 * U + 7, (int64_t)1 << 34}) lists.push_back({c});
+  for (int64_t n : {(int64_t)1, E - 1, E, E + 1, 2 * E + 1, (int64_t)4096}) {
+    std::vector<int64_t> l;
+    for (int64_t i = 0; i < n; ++i) l.push_back(1 + (5 * i + 3) % 9);
+    lists.push_back(l);
+  }
+  for (int variant : {(int)RON_VARIANT_REDUCEDFC, (int)RON_VARIANT_FULL}) {
+    ron_config cfg;
+    memset(&cfg, 0, sizeof(cfg));
+    cfg.variant = variant; cfg.dtype = RON_DTYPE_BF16; cfg.img_h = cfg.img_w = 320; cfg.num_classes = 21; cfg.max_batch = 1;
+    ron_ctx* c = nullptr;
+    CHECK(ron_create(&c, &cfg));
+    std::vector<int64_t> l;
+    for (int i = 0; i < ron_num_variables(c); ++i) {
+      const char* name = nullptr;
+      int64_t shape[4] = {0, 0, 0, 0};
+      int nd = 0;
+      CHECK(ron_variable_info(c, i, &name, shape, &nd));
+      if (strstr(name, "/moving_") != nullptr) continue;
+      int64_t n = 1;
+      for (int k = 0; k < nd; ++k) n *= shape[k];
+      l.push_back(n);
+    }
+    CHECK(ron_destroy(c));
+    if (l.size() < 100) return 1;
+    lists.push_back(l);
+  }
+  for (const std::vector<int64_t>& counts : lists) {
+    std::vector<ron_opt_tensor> t = table(counts);
+    const int n = (int)t.size();
+    CHECK(ron_optimizer_plan(t.data(), n, plan));
+    int64_t units = 0;
+    for (int64_t c : counts) units += (c + U - 1) / U;
+    if (plan[0] != (n + E - 1) / E || plan[1] != units) return 1;
+    const int64_t bytes = ron_optimizer_workspace_bytes(t.data(), n);
+    if (bytes < units * 4 || bytes % 256 != 0) return 1;
+    for (int rule : {(int)RON_OPT_SGD, (int)RON_OPT_MOMENTUM, (int)RON_OPT_RMSPROP, (int)RON_OPT_ADAM}) {
+      const ron_opt_cfg c = cfg_of(rule);
+      CHECK(ron_optimizer_step(&c, t.data(), n, 0.001f, 1, reg, ws, bytes, nullptr));
+      CHECK(ron_optimizer_step(&c, t.data(), n, 0.001f, 90001, nullptr, nullptr, 0, nullptr));
+      // the calls it refuses: a short, misaligned or missing workspace with reg_loss, a missing, misaligned or aliased tensor
+      if (ron_optimizer_step(&c, t.data(), n, 0.001f, 1, reg, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_optimizer_step(&c, t.data(), n, 0.001f, 1, reg, static_cast<char*>(ws) + 16, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_optimizer_step(&c, t.data(), n, 0.001f, 1, reg, nullptr, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_optimizer_step(&c, t.data(), n, NAN, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_optimizer_step(&c, t.data(), n, INFINITY, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+      if (rule == RON_OPT_ADAM && ron_optimizer_step(&c, t.data(), n, 0.001f, 0, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+      const int last = n - 1;
+      std::vector<ron_opt_tensor> bad[10];
+      for (std::vector<ron_opt_tensor>& b : bad) b = t;
+      bad[0][last].var = nullptr; bad[1][last].grad = nullptr; bad[2][last].var += 1; bad[3][last].grad += 2;
+      bad[4][last].grad = bad[4][last].var; bad[5][last].weight_decay = -1.f; bad[6][last].weight_decay = NAN; bad[7][last].weight_decay = INFINITY;
+      bad[8][last].count = 0; bad[9][last].var = bad[9][0].var;          // (a list of one tensor: the entry itself, accepted)
+      for (int i = 0; i < 10; ++i) {
+        if (i == 9 && n == 1) continue;
+        if (ron_optimizer_step(&c, bad[i].data(), n, 0.001f, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) {
+          fprintf(stderr, "optimizer: rule %d, %d tensors: bad table %d accepted\n", rule, n, i);
+          return 1;
+        }
+      }
+      std::vector<ron_opt_tensor> slots[4];
+      for (std::vector<ron_opt_tensor>& b : slots) b = t;
+      slots[0][last].slot0 = nullptr; slots[1][last].slot1 = nullptr; slots[2][last].slot0 = slots[2][last].var; slots[3][last].slot1 += 1;
+      const bool uses[4] = {rule != RON_OPT_SGD, rule >= RON_OPT_RMSPROP, rule != RON_OPT_SGD, rule >= RON_OPT_RMSPROP};
+      for (int i = 0; i < 4; ++i)          // a slot the rule does not use is ignored
+        if (ron_optimizer_step(&c, slots[i].data(), n, 0.001f, 1, nullptr, nullptr, 0, nullptr) != (uses[i] ? RON_ERR_INVALID : RON_OK)) return 1;
+    }
+    // the configurations it refuses
+    ron_opt_cfg bad[14];
+    for (ron_opt_cfg& b : bad) b = cfg_of(RON_OPT_ADAM);
+    bad[0].rule = -1; bad[1].rule = 4; bad[2].momentum = -0.1f; bad[3].momentum = 1.5f; bad[4].decay = NAN; bad[5].decay = 2.f; bad[6].beta1 = 1.f;
+    bad[7].beta2 = 1.f; bad[8].beta1 = -0.5f; bad[9].beta2 = NAN; bad[10].epsilon = -1.f; bad[11].epsilon = NAN; bad[12].epsilon = INFINITY;
+    bad[13].rule = INT32_MAX;
+    for (const ron_opt_cfg& b : bad)
+      if (ron_optimizer_step(&b, t.data(), n, 0.001f, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+    if (ron_optimizer_step(nullptr, t.data(), n, 0.001f, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+  }
+  // the lists it refuses, through all three entries
+  const ron_opt_cfg c = cfg_of(RON_OPT_MOMENTUM);
+  std::vector<ron_opt_tensor> big = table(std::vector<int64_t>(4097, 1));
+  std::vector<ron_opt_tensor> wide = table({(int64_t)1 << 34, 1}), huge = table({((int64_t)1 << 40) + 1}), neg = table({-5});
+  struct Refused { const ron_opt_tensor* t; int n; };
+  const Refused refused[] = {{big.data(), 4097}, {big.data(), 0}, {big.data(), -1}, {nullptr, 1}, {wide.data(), 2}, {huge.data(), 1}, {neg.data(), 1}};
+  for (const Refused& r : refused) {
+    if (ron_optimizer_plan(r.t, r.n, plan) != RON_ERR_INVALID || ron_optimizer_workspace_bytes(r.t, r.n) != -1) return 1;
+    if (ron_optimizer_step(&c, r.t, r.n, 0.001f, 1, nullptr, nullptr, 0, nullptr) != RON_ERR_INVALID) return 1;
+  }
+  if (ron_optimizer_plan(big.data(), 1, nullptr) != RON_ERR_INVALID) return 1;
+  return 0;
+}
+
 // The argument envelope of ron_conv_desc (include/ron_hip.h): for every field limit - 1 and limit plan, limit + 1 is refused, through
 // ron_conv_plan and the backward's workspace query; zeros, negatives and flags other than 0 / 1 are refused before any arithmetic on
 // them (a stride of 0 used to reach a division).  The shapes are those of tests/conv_envelope_cases.py.
@@ -440,6 +563,10 @@ int main(int argc, char** argv) {
   }
   if (batchnorm_arguments()) {
     fprintf(stderr, "plan_sweep: ron_batchnorm_train_nhwc / ron_batchnorm_backward_nhwc planning / argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (optimizer_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_optimizer_step planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
   if (conv_envelope()) {
