@@ -664,7 +664,7 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
  * factor of the weight gradient: -1 = by shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the
  * fp32 partial sums of the slices would reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned pointer and a
  * workspace that is too small included - is RON_ERR_INVALID with a message, before any HIP call.
- * Out of scope: the 3-channel stem, strided and transposed convolutions, pools (the 2x2 stride-2 ones have entry points of
+ * Out of scope: the 3-channel stem (ron_conv2d_stem_backward_nhwc below), strided and transposed convolutions, pools (the 2x2 stride-2 ones have entry points of
  * their own below), fp32 and f16x3 arithmetic.
  * ron_conv2d_backward_workspace_bytes is host arithmetic only (it depends on d->splitk too); -1 + ron_last_error() on a
  * descriptor the call would refuse.
@@ -672,6 +672,40 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
 int64_t ron_conv2d_backward_workspace_bytes(const ron_conv_desc* d);
 int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
                              float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Backward of the 3-channel stem convolution conv1_1 (3 -> 64 channels, 3x3, stride 1, SAME): its weight and bias
+ * gradients, the two variables ron_conv2d_backward_nhwc cannot reach.  There is no gradient with respect to the image
+ * (nothing takes one), hence no w and no dx.  A real entry point like the convolution backward: it enqueues on `stream`,
+ * allocates nothing, never synchronises, honours the dry-run mode and assumes nothing about the workspace's contents.
+ *
+ * The semantics are those of ron_conv2d_backward_nhwc, restricted to dw and dbias:
+ *   xs    = round(x) to d->dtype (what the forward's stem kernel multiplies)
+ *   dz    = round(dy * (y > 0)) when d->relu (TF's ReluGrad: nothing where y == 0), else round(dy)
+ *   dw[ky,kx,c,co] = sum over n, i, j of xs[n, i+ky-1, j+kx-1, c] * dz[n,i,j,co]: an fp32 sum, not rounded further; terms
+ *           outside the map are zero; HWIO [3,3,3,64]
+ *   dbias[co] = sum of dz[..., co]: the rounded dz, in fp32
+ * The sums run in a fixed order (no float atomics): the same inputs give the same bytes on every call, for every split.
+ *
+ * All pointers are DEVICE fp32: x [n,h,w,3], y and dy [n,h,w,64], dw [3,3,3,64], dbias [64].  y and dy must be 16-byte
+ * aligned (they are read 16 bytes at a time); x needs its natural 4-byte alignment only (a pixel is 12 bytes); the
+ * workspace is 256-byte aligned.  y is read only when d->relu.  dw and dbias may each be NULL (not computed); every element
+ * of a non-NULL output is written; with both NULL the call is accepted and enqueues nothing.  x may be NULL when dw is.
+ *
+ * Accepted descriptors: cin 3, cout 64, kh = kw = 3, stride 1, dilation 1 (the convolution the forward runs on its 3-channel
+ * path); dtype bf16 / fp16; relu 0 or 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1;
+ * n, h, w >= 1 with n * h * w <= RON_STEM_BACKWARD_MAX_PIXELS: the kernel counts pixels, rounded up to its step of 32, in
+ * 32-bit signed integers, and a larger tensor is refused, never wrapped.  d->splitk is the number of pixel slices: -1 = by
+ * shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the fp32 partial sums of the slices would
+ * reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned y or dy and a workspace that is too small included -
+ * is RON_ERR_INVALID with a message, before any HIP call.
+ * ron_conv2d_stem_backward_workspace_bytes is host arithmetic only (it depends on d->splitk); -1 + ron_last_error() on a
+ * descriptor the call would refuse.
+ * ---------------------------------------------------------------------------------------- */
+#define RON_STEM_BACKWARD_MAX_PIXELS 2147483616 /* 2^31 - 32 */
+int64_t ron_conv2d_stem_backward_workspace_bytes(const ron_conv_desc* d);
+int ron_conv2d_stem_backward_nhwc(const ron_conv_desc* d, const float* x, const float* y, const float* dy, float* dw,
+                                  float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of the 2x2 stride-2 SAME max-pool (slim.max_pool2d [2, 2], pool1 .. pool5: nets/ron_vgg_320.py:456..475,

@@ -33,6 +33,7 @@
 #include <algorithm>
 
 #include "conv_mfma.h"
+#include "wgrad_device.h"
 
 namespace ron {
 namespace {
@@ -42,27 +43,7 @@ constexpr int kWgStep = 32;         // pixels per K step
 constexpr int kWgImage = kWgStep * kWgTile * 2;     // bytes of one staged operand image
 constexpr int kWgLds = 4 * kWgImage;                // two operands, double buffered: 32 KB, inside the default limit
 
-typedef short v4i16 __attribute__((ext_vector_type(4)));
-typedef short v8i16 __attribute__((ext_vector_type(8)));
-typedef __bf16 v8bf16 __attribute__((ext_vector_type(8)));
-typedef _Float16 v8f16 __attribute__((ext_vector_type(8)));
-typedef float v4f32 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) v4i16 lds_v4i16;
-
-__device__ __forceinline__ unsigned short round_bf16_bits(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (unsigned short)((u >> 16) | 0x0040u);      // keep NaN a NaN
-  return (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
-__device__ __forceinline__ unsigned short round_f16_bits(float f) {
-  const _Float16 h = (_Float16)f;
-  return __builtin_bit_cast(unsigned short, h);
-}
-template <bool BF16> __device__ __forceinline__ unsigned short round_bits(float f) { return BF16 ? round_bf16_bits(f) : round_f16_bits(f); }
-template <bool BF16> __device__ __forceinline__ float bits_to_f(unsigned short b) {
-  if (BF16) return __uint_as_float((unsigned)b << 16);
-  return (float)__builtin_bit_cast(_Float16, b);
-}
+using namespace wgrad;      // wgrad_device.h: the roundings, the MFMA and its transposed operand read (shared with stem_wgrad.hip)
 
 // byte offset of 16-byte chunk `ch` (0..15) of pixel row `row` (0..31) in a staged image
 __device__ __forceinline__ int image_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }
@@ -212,19 +193,6 @@ struct WgradArgs {
   int tiles_m, tiles_n;
   int steps, steps_per;     // K steps in all / per slice (no empty slice)
 };
-
-template <bool BF16>
-__device__ __forceinline__ v4f32 wgrad_mfma(v8i16 a, v8i16 b, v4f32 c) {
-  if (BF16) return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf16, a), __builtin_bit_cast(v8bf16, b), c, 0, 0, 0);
-  return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(v8f16, a), __builtin_bit_cast(v8f16, b), c, 0, 0, 0);
-}
-
-// the 8 K values (pixel rows 8g .. 8g+7) x 16 channels operand of one lane group, from the image at `img`: two transposed reads
-__device__ __forceinline__ v8i16 wgrad_operand(const char* img, int off_lo, int off_hi) {
-  const v4i16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(img + off_lo));
-  const v4i16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4i16*)(img + off_hi));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
 
 // WBM, WBN: 16-channel MFMA blocks per wave along cin / cout (4 or 2): the workgroup's tile is 32 WBM x 32 WBN channels.  The 64-wide
 // forms are for tensors of 64 channels (conv1_2; heads of <= 64 outputs), where a 128-wide tile would multiply zeros half the time.

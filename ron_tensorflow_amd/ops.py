@@ -572,6 +572,46 @@ def conv2d_backward_nhwc(x, w, dy, y=None, relu=True, dilation=1, dtype='bf16', 
     return _conv_backward_call('conv2d_backward', describe, x, w, dy, y, relu, need, workspace)
 
 
+def _stem_desc(n, h, w, relu, dtype, splitk):
+    return _backward_desc(n, h, w, 3, 64, 3, 1, relu, dtype, splitk)
+
+
+def conv2d_stem_backward_workspace_bytes(n, h, w, relu=True, dtype='bf16', splitk=-1):
+    """Bytes of workspace conv2d_stem_backward_nhwc needs (host arithmetic; raises on a descriptor the library refuses)."""
+    return _desc_workspace_bytes('conv2d_stem_backward', _stem_desc(n, h, w, relu, dtype, splitk))
+
+
+def conv2d_stem_backward_nhwc(x, dy, y=None, relu=True, dtype='bf16', splitk=-1, need=('dw', 'db'), workspace=None):
+    """Weight and bias gradients of the 3-channel stem y = act(conv_SAME(x, w) + bias), 3x3, 3 -> 64 channels (conv1_1): (dw, db),
+    None for those not in `need`.  There is no gradient with respect to the image, hence no w.
+
+    x [N,H,W,3], dy and y [N,H,W,64] GPU fp32.  Everything else as conv2d_backward_nhwc: the mask is y > 0 with `relu`, operands are
+    rounded to `dtype` (bf16 / fp16), dw [3,3,3,64] and db [64] are unrounded fp32 sums in a fixed order; `splitk`: pixel slices (-1 by
+    shape, 1 off, S forced); `workspace`: a uint8 GPU tensor of at least conv2d_stem_backward_workspace_bytes(...) bytes, or None
+    for the cached per-device, per-stream buffer."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and x.is_cuda and dy.is_cuda
+    n, h, wd, cin = x.shape
+    if cin != 3 or tuple(dy.shape) != (n, h, wd, 64):
+        raise _lib.RonError('conv2d_stem_backward_nhwc: x %s, dy %s: the 3 -> 64 channel stem only' % (tuple(x.shape), tuple(dy.shape)))
+    if relu and y is None:
+        raise _lib.RonError('conv2d_stem_backward_nhwc: relu=True needs the forward output y (the mask is y > 0)')
+    if y is not None:
+        y = y.contiguous()
+        assert y.dtype == torch.float32 and tuple(y.shape) == tuple(dy.shape)
+    unknown = set(need) - {'dw', 'db'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    d = _stem_desc(n, h, wd, relu, dtype, splitk)
+    nbytes = _desc_workspace_bytes('conv2d_stem_backward', d)
+    ws = _workspace(dev, nbytes) if workspace is None else workspace
+    dw = torch.empty((3, 3, 3, 64), dtype=torch.float32, device=dev) if 'dw' in need else None
+    db = torch.empty((64,), dtype=torch.float32, device=dev) if 'db' in need else None
+    check(lib().ron_conv2d_stem_backward_nhwc(C.byref(d), ptr(x), ptr(y if relu else None), ptr(dy), ptr(dw), ptr(db), ptr(ws),
+                                              int(ws.numel()), current_stream()))
+    return dw, db
+
+
 class _Conv2dNhwcFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, relu, dilation, dtype):
@@ -587,6 +627,14 @@ class _Conv2dNhwcFn(torch.autograd.Function):
         x, w, y = ctx.saved_tensors
         relu, dilation, dtype, has_bias = ctx.cfg
         need = _needed_grads(ctx, has_bias)
+        if x.shape[3] == 3:          # the stem: an entry point of its own, which has no gradient with respect to the image
+            if 'dx' in need:
+                raise _lib.RonError('conv2d_nhwc_fn: no gradient with respect to the input of the 3-channel stem (the image)')
+            if tuple(w.shape) != (3, 3, 3, 64) or dilation != 1:
+                raise _lib.RonError('conv2d_nhwc_fn: w %s, dilation %d: the backward of a 3-channel input exists for the 3x3, 3 -> 64 '
+                                    'stem only' % (tuple(w.shape), dilation))
+            dw, db = conv2d_stem_backward_nhwc(x, dy, y, relu=relu, dtype=dtype, need=need) if need else (None, None)
+            return None, dw, db, None, None, None
         dx, dw, db = conv2d_backward_nhwc(x, w, dy, y, relu=relu, dilation=dilation, dtype=dtype, need=need) if need else (None, None, None)
         return dx, dw, db, None, None, None
 
@@ -596,7 +644,8 @@ def conv2d_nhwc_fn(x, w, bias, relu=True, dilation=1, dtype='bf16'):
 
     The forward is ron_conv2d_nhwc, which packs the weights on the HOST (a device-to-host copy of w) and synchronises: a
     convenience for tests and small experiments, not the training path.  The backward is ONE ron_conv2d_backward_nhwc call on the
-    current stream, computing only the gradients autograd asks for; tensors that do not require grad get None."""
+    current stream, computing only the gradients autograd asks for; tensors that do not require grad get None.  A 3-channel x (the
+    image in front of conv1_1) has ONE ron_conv2d_stem_backward_nhwc call instead, for dw and db; asking for its dx raises RonError."""
     return _Conv2dNhwcFn.apply(x, w, bias, relu, dilation, dtype)
 
 

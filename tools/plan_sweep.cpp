@@ -170,6 +170,64 @@ static int conv_backward_arguments() {
   return 0;
 }
 
+// ron_conv2d_stem_backward_nhwc in the dry run: the descriptor checks, the pixel slices and the workspace, over the case table of
+// tests/stem_grad_cases.py plus the layer itself (tools/stem_backward_time.py) and the last accepted pixel count, every dtype and pixel
+// split, and the refusals; pointers are used for arithmetic only.
+static int stem_backward_arguments() {
+  struct Case { int n, h, w; };
+  const Case cases[] = {{1, 1, 1}, {2, 5, 7}, {3, 3, 3}, {1, 1, 33}, {1, 33, 1}, {1, 8, 32}, {2, 40, 40}, {1, 320, 320}, {32, 320, 320},
+                        {64, 512, 512}, {1, 1, (int)RON_STEM_BACKWARD_MAX_PIXELS}, {32768, 1, 65535}};
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (const Case& c : cases) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      for (int splitk : {-1, 1, 2, 7, 1000000, 0x7FFFFFFF}) {
+        for (int relu : {0, 1}) {
+          ron_conv_desc d;
+          memset(&d, 0, sizeof d);
+          d.n = c.n; d.h = c.h; d.w = c.w; d.cin = 3; d.cout = 64; d.kh = d.kw = 3; d.stride = 1; d.dilation = 1;
+          d.relu = relu; d.dtype = dtype; d.tile_cfg = -1; d.splitk = splitk;
+          const int64_t bytes = ron_conv2d_stem_backward_workspace_bytes(&d);
+          if (bytes <= 0 || bytes % 256 != 0 || bytes >= ((int64_t)1 << 32)) return 1;
+          float* const y = relu ? f : nullptr;
+          CHECK(ron_conv2d_stem_backward_nhwc(&d, f, y, f, f, f, ws, bytes, nullptr));
+          CHECK(ron_conv2d_stem_backward_nhwc(&d, nullptr, y, f, nullptr, f, ws, bytes, nullptr));
+          CHECK(ron_conv2d_stem_backward_nhwc(&d, f + 1, y, f, f, nullptr, ws, bytes, nullptr));      // an x that is only 4-byte aligned
+          CHECK(ron_conv2d_stem_backward_nhwc(&d, nullptr, y, f, nullptr, nullptr, ws, bytes, nullptr));
+          if (ron_conv2d_stem_backward_nhwc(&d, f, y, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+          if (relu && ron_conv2d_stem_backward_nhwc(&d, f, nullptr, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          if (ron_conv2d_stem_backward_nhwc(&d, f, y, f + 1, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          if (ron_conv2d_stem_backward_nhwc(&d, nullptr, y, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+          ron_conv_desc bad = d;
+          bad.cin = 64;
+          if (ron_conv2d_stem_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.cout = 24;
+          if (ron_conv2d_stem_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.kh = bad.kw = 5;
+          if (ron_conv2d_stem_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.dilation = 2;
+          if (ron_conv2d_stem_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.splitk = 0;
+          if (ron_conv2d_stem_backward_workspace_bytes(&bad) != -1) return 1;
+          bad = d; bad.dtype = RON_DTYPE_F16X3;
+          if (ron_conv2d_stem_backward_nhwc(&bad, f, f, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        }
+      }
+    }
+  }
+  // one pixel more than the kernel's 32-bit pixel arithmetic holds, and products that leave 32 and 64 bits
+  const Case big[] = {{1, 1, (int)RON_STEM_BACKWARD_MAX_PIXELS + 1}, {32768, 256, 256}, {0x7FFFFFFF, 0x7FFFFFFF, 0x7FFFFFFF}, {65536, 65536, 1}};
+  for (const Case& c : big) {
+    ron_conv_desc d;
+    memset(&d, 0, sizeof d);
+    d.n = c.n; d.h = c.h; d.w = c.w; d.cin = 3; d.cout = 64; d.kh = d.kw = 3; d.stride = 1; d.dilation = 1;
+    d.relu = 1; d.dtype = RON_DTYPE_BF16; d.tile_cfg = -1; d.splitk = -1;
+    if (ron_conv2d_stem_backward_workspace_bytes(&d) != -1) return 1;
+    if (ron_conv2d_stem_backward_nhwc(&d, f, f, f, f, f, ws, (int64_t)1 << 40, nullptr) != RON_ERR_INVALID) return 1;
+  }
+  return 0;
+}
+
 // ron_maxpool2x2_backward_nhwc and ron_conv2d_k2s2_backward_nhwc in the dry run: the case tables of tests/op_grad_cases.py plus the
 // shapes of tools/op_backward_time.py, every dtype and pixel split, and the refusals; pointers are used for arithmetic only.
 static int op_backward_arguments() {
@@ -555,6 +613,10 @@ int main(int argc, char** argv) {
   }
   if (conv_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_conv2d_backward_nhwc planning / argument handling: %s\n", ron_last_error());
+    return 1;
+  }
+  if (stem_backward_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_conv2d_stem_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
   if (op_backward_arguments()) {
