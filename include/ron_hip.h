@@ -751,6 +751,83 @@ int ron_conv2d_k2s2_backward_nhwc(const ron_conv_desc* d, const float* x, const 
                                   float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The SSD-only operators between pool1 and the SSD heads: pool5 (3x3 stride-1 max-pool), the block4 L2 normalisation and
+ * the padded 3x3 convolutions of the extra blocks.  Each has a forward test operator where the library had none (they
+ * allocate and synchronise, like ron_maxpool2x2_nhwc) and a backward that is a real entry point like the convolution
+ * backward: it enqueues on `stream`, allocates nothing, never synchronises, honours the dry-run mode, assumes nothing about
+ * the workspace's contents, writes every element of every non-NULL output by a plain store and uses no float atomics: the
+ * same inputs give the same bytes.
+ *
+ * --- pool5: slim.max_pool2d [3, 3] stride 1 SAME (nets/ssd_vgg_300.py:472, nets/ssd_vgg_512.py:399) ---
+ * ron_maxpool3x3s1_nhwc (test operator) runs the graph's own kernel on x [n,h,w,c] -> y [n,h,w,c], device fp32.  ONE
+ * restriction: that kernel starts its maximum at 0 (its zero halo takes part), so it equals TensorFlow's pool for
+ * NON-NEGATIVE inputs only - what pool5 sees behind conv5_3's ReLU.  c a multiple of 8 (bf16 / fp16).
+ *
+ * ron_maxpool3x3s1_backward_nhwc: x (the pool's input), dy and dx are [n,h,w,c] device fp32, 16-byte aligned; no workspace.
+ *   xs = round(x) to `dtype`.  The window of output (oy, ox) holds the IN-BOUNDS positions of rows oy-1 .. oy+1 and columns
+ *   ox-1 .. ox+1: padding does not take part - it is excluded, not a zero (so the backward is right for negative inputs
+ *   too).  A window's gradient goes to the FIRST of its positions, in row-major order, whose xs equals the window's
+ *   maximum: the running maximum starts at the window's first in-bounds position and a later position takes over only
+ *   when it is greater (>), compared on the rounded values; ties after rounding are ties, and so are -0.0 and +0.0.
+ *   dx[n,i,j,ch] = the fp32 sum of round(dy[n,oy,ox,ch]) over the up to nine windows that contain (i, j) and select it,
+ *   added in row-major order of (oy, ox) starting from 0.f, rounded ONCE to the storage type and delivered as a
+ *   storage-type value in fp32; a position no window selects gets 0.  A window that holds a NaN is outside the contract.
+ *   This is torch-CPU's max_pool2d(3, 1, 1) backward in both memory formats and TensorFlow's MaxPoolGrad by the argument
+ *   of the 2x2 pool above (parity with TensorFlow unpinned, as there).  The rule holds no multiplication: the result is
+ *   reproducible bit for bit in numpy float32.
+ *   Accepted: dtype bf16 / fp16, c a multiple of 8, n, h, w >= 1 with n h w c elements inside 64-bit indexing, 16-byte
+ *   aligned non-NULL pointers; anything else is RON_ERR_INVALID with a message, before any HIP call.
+ *
+ * --- block4: custom_layers.l2_normalization(scaling=True) (nets/custom_layers.py:66-135, nets/ssd_vgg_300.py:413) ---
+ * gamma is the variable .../L2Normalization/gamma: a DEVICE fp32 vector [c], never rounded.  Per pixel p, over channels:
+ *   xs = round(x);  ss = sum_c xs^2 (fp32);  inv = 1 / sqrt(max(ss, 1e-12f));  y = round(xs * inv * gamma[c])
+ * ron_l2norm_nhwc (test operator) runs the graph's kernel on x [n,h,w,c] -> y [n,h,w,c], device fp32.
+ *
+ * ron_l2norm_backward_nhwc: x, dy, dx [n,h,w,c]; gamma, dgamma [c]; all device fp32.  dx and dgamma may each be NULL.
+ *   dz = round(dy) (there is no activation behind the normalisation);  u = xs * inv;  g = dz * gamma;  t = sum_c g u
+ *   ss >= 1e-12f:  dx = round(inv * (g - u t))
+ *   otherwise:     dx = round(inv * g)      the clamped branch: TF's maximum hands no gradient to ss there, so an all-zero
+ *                                           post-ReLU pixel gets dy * gamma * 1e6
+ *   dgamma[c] = sum_p dz[p,c] u[p,c]: an fp32 sum, not rounded further
+ *   ss and t are fp32 sums in an order that is a function of the shape alone (a lane's channels in order, then a butterfly
+ *   over the 64 lanes); so is dgamma: wave v of W = min(n h w, 2048) adds its pixels v, v + W, ... in that order into row
+ *   v of a [W][c] table in the workspace, a second kernel adds eight contiguous runs of rows, each in row order, and then
+ *   the runs in run order.  W does not depend on the device.
+ *   Accepted: dtype bf16 / fp16, c a multiple of 8 and at most 2048 (a wave keeps its pixel in registers), n, h, w >= 1 with
+ *   n h w c inside 64-bit indexing (the table has at most 2048 rows whatever the shape: it imposes no further limit),
+ *   16-byte aligned tensors, x, gamma and dy non-NULL, a 256-byte aligned workspace of at least
+ *   ron_l2norm_backward_workspace_bytes(...) bytes (host arithmetic only; -1 + ron_last_error() on a refused shape).
+ *   Anything else is RON_ERR_INVALID with a message, before any HIP call.
+ *
+ * --- the 3x3 convolutions of the extra blocks ---
+ * ron_conv2d_padded_backward_nhwc: `d` is read as everywhere - n, h, w are the dimensions of the input x - with
+ * kh = kw = 3 and dilation = 1, and (d->stride, cpad) one of
+ *   (2, 1)  custom_layers.pad2d(pad=(1, 1)) + 3x3 stride-2 VALID: block8 / block9 of SSD-300 (nets/ssd_vgg_300.py:488-495),
+ *           block8 .. block11 of SSD-512 (nets/ssd_vgg_512.py:413-432)
+ *   (1, 0)  plain 3x3 VALID, h, w >= 3: block10 / block11 of SSD-300 (nets/ssd_vgg_300.py:500, 505)
+ * With ho = (h + 2 cpad - 3) / stride + 1 (wo likewise), y and dy are [n,ho,wo,cout]; x and dx [n,h,w,cin]; w and dw HWIO
+ * [3,3,cin,cout]; dbias [cout].  Both forms are the stride-1 SAME convolution sampled at (o + stride oy, o + stride ox),
+ * o = 1 - cpad, so their gradients are those of ron_conv2d_backward_nhwc for dz = round(dy * (y > 0)) (round(dy) without
+ * relu; y is this operator's own [n,ho,wo,cout] output) scattered to those positions of a zero [n,h,w,cout] map: the same
+ * sums with zero terms added.  Everything else - masks, roundings, NULL outputs, splitk, alignment, the 2 GiB caps of the
+ * packed FULL-RESOLUTION tensors, the refusals - is the contract of ron_conv2d_backward_nhwc word for word.  At stride 2
+ * this spends four times the MFMA work of a strided gather (on maps of 32 x 32 and smaller).
+ * Block12 of SSD-512 (pad2d(1) + 4x4 VALID on a 2x2 map, nets/ssd_vgg_512.py:437-438) needs no entry point: only the
+ * filter's inner 2x2 taps meet data, so it is ron_conv2d_k2s2_backward_nhwc with w[1:3, 1:3], and dw is zero in the twelve
+ * outer taps.
+ * ron_conv2d_padded_backward_workspace_bytes is host arithmetic only; -1 + ron_last_error() on what the call would refuse.
+ * ---------------------------------------------------------------------------------------- */
+int ron_maxpool3x3s1_nhwc(const float* x, int n, int h, int w, int c, int dtype, float* y, void* stream);
+int ron_maxpool3x3s1_backward_nhwc(const float* x, const float* dy, int n, int h, int w, int c, int dtype, float* dx, void* stream);
+int ron_l2norm_nhwc(const float* x, const float* gamma, int n, int h, int w, int c, int dtype, float* y, void* stream);
+int64_t ron_l2norm_backward_workspace_bytes(int n, int h, int w, int c, int dtype);
+int ron_l2norm_backward_nhwc(const float* x, const float* gamma, const float* dy, int n, int h, int w, int c, int dtype, float* dx,
+                             float* dgamma, void* workspace, int64_t workspace_bytes, void* stream);
+int64_t ron_conv2d_padded_backward_workspace_bytes(const ron_conv_desc* d, int cpad);
+int ron_conv2d_padded_backward_nhwc(const ron_conv_desc* d, int cpad, const float* x, const float* w, const float* y, const float* dy,
+                                    float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Training-mode batch normalisation (slim.batch_norm under ron_arg_scope(is_training=True), nets/ron_vgg_320.py:616-624:
  * fused=True, decay=0.997, epsilon=1e-5, scale=True; every _conv_left and _objectness, reg_bbox/Conv2d_0_3x3 and the two
  * inception concatenations of pred_cls_module), forward and backward.  Real entry points like the convolution backward: they

@@ -209,6 +209,13 @@ SIGNATURES = {
     'ron_maxpool2x2_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     'ron_conv2d_k2s2_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_k2s2_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_maxpool3x3s1_nhwc': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    'ron_maxpool3x3s1_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    'ron_l2norm_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    'ron_l2norm_backward_workspace_bytes': (C.c_int64, [C.c_int] * 5),
+    'ron_l2norm_backward_nhwc': (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_int64, _P]),
+    'ron_conv2d_padded_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc), C.c_int]),
+    'ron_conv2d_padded_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_batchnorm_workspace_bytes': (C.c_int64, [C.POINTER(BnDesc)]),
     'ron_batchnorm_train_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_batchnorm_backward_nhwc': (C.c_int, [C.POINTER(BnDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),

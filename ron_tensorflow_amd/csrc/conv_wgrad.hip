@@ -1,5 +1,6 @@
-// Backward of the stride-1 SAME convolution (ron_conv2d_backward_nhwc): data, weight and bias gradients.  The 2x2 stride-2 convolution and
-// transposed convolution (ron_conv2d_k2s2_backward_nhwc) reuse its kernels on space-to-depth views: the last section of this file.
+// Backward of the stride-1 SAME convolution (ron_conv2d_backward_nhwc): data, weight and bias gradients.  The padded 3x3 convolutions
+// of the SSD extra blocks (ron_conv2d_padded_backward_nhwc) reuse it behind a scattering pack of dz, the 2x2 stride-2 convolution and
+// transposed convolution (ron_conv2d_k2s2_backward_nhwc) reuse its kernels on space-to-depth views: the last two sections of this file.
 //
 //   dz    = round(dy * (y > 0))                              pack_halo_kernel (ReLU mask fused), a halo tensor of the storage type
 //   dx    = round(conv_SAME(dz, flipped / swapped weights))  launch_conv on dz (the forward's kernels), weights packed ON THE DEVICE
@@ -57,9 +58,12 @@ struct PackArgs {
   unsigned short* out;
   long long rows, guard;
   int N, H, W, pad, Csrc, Cdst;
+  // SCATTER only (ron_conv2d_padded_backward_nhwc): src and mask are [N,Hs,Ws,Csrc] and source pixel (sy, sx) lands on pixel
+  // (soff + sstep * sy, soff + sstep * sx) of the H x W map; every other pixel of the map is zero
+  int Hs, Ws, sstep, soff;
 };
 
-template <bool BF16>
+template <bool BF16, bool SCATTER = false>
 __global__ void conv_bwd_pack_halo_kernel(PackArgs a) {
   // (every buffer of the entry point is below 2 GiB, plan_backward: the 16-byte pieces and the pixels fit 32-bit arithmetic)
   const unsigned vecs = a.Cdst / 8;
@@ -76,8 +80,16 @@ __global__ void conv_bwd_pack_halo_kernel(PackArgs a) {
       const int col = (int)(q - r * Wp);
       const unsigned img = r / Hp;
       const int row = (int)(r - img * Hp);
-      if (col >= a.pad && row >= a.pad && img < (unsigned)a.N) {
-        const long long s0 = (((long long)img * a.H + (row - a.pad)) * a.W + (col - a.pad)) * a.Csrc + v * 8;
+      bool inside = col >= a.pad && row >= a.pad && img < (unsigned)a.N;
+      int sy = row - a.pad, sx = col - a.pad, sh = a.H, sw = a.W;
+      if (SCATTER && inside) {
+        sy -= a.soff; sx -= a.soff;
+        inside = sy >= 0 && sx >= 0 && sy % a.sstep == 0 && sx % a.sstep == 0;
+        sy /= a.sstep; sx /= a.sstep; sh = a.Hs; sw = a.Ws;
+        inside = inside && sy < sh && sx < sw;
+      }
+      if (inside) {
+        const long long s0 = (((long long)img * sh + sy) * sw + sx) * a.Csrc + v * 8;
         if (vec_ok && v * 8 + 8 <= a.Csrc) {
           const float4 lo = *reinterpret_cast<const float4*>(a.src + s0), hi = *reinterpret_cast<const float4*>(a.src + s0 + 4);
           f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
@@ -469,7 +481,23 @@ int launch_pack_halo(const float* src, const float* mask, void* out, int64_t row
   a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
   a.rows = rows + 2 * guard; a.guard = guard;
   a.N = n; a.H = h; a.W = w; a.pad = pad; a.Csrc = csrc; a.Cdst = cdst;
+  a.Hs = h; a.Ws = w; a.sstep = 1; a.soff = 0;
   RON_LAUNCH(conv_bwd_pack_halo_kernel<BF16>, dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
+// the same buffer from a COARSER source: dense fp32 [n,hs,ws,csrc] scattered to pixels (soff + sstep * sy, soff + sstep * sx) of the
+// h x w map (the caller guarantees that they all exist), zero at every other pixel
+template <bool BF16>
+int launch_pack_halo_scatter(const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc,
+                             int cdst, int hs, int ws, int sstep, int soff, hipStream_t s) {
+  PackArgs a;
+  a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
+  a.rows = rows; a.guard = 0;
+  a.N = n; a.H = h; a.W = w; a.pad = pad; a.Csrc = csrc; a.Cdst = cdst;
+  a.Hs = hs; a.Ws = ws; a.sstep = sstep; a.soff = soff;
+  RON_LAUNCH((conv_bwd_pack_halo_kernel<BF16, true>), dim3(grid_for(a.rows * (cdst / 8))), dim3(256), 0, s, a);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
 }
@@ -561,12 +589,16 @@ int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
   return finish_plan(P);
 }
 
+// sstep = 0: y and dy are [n,h,w,cout] (ron_conv2d_backward_nhwc); else they are [n,hs,ws,cout] and dz is their scatter to pixels
+// (soff + sstep * oy, soff + sstep * ox) of a zero h x w map (ron_conv2d_padded_backward_nhwc) - everything behind the pack is the same
 template <bool BF16>
 int run_backward(const ron_conv_desc* d, const BackwardPlan& P, const float* x, const float* w, const float* y, const float* dy,
-                 float* dx, float* dw, float* dbias, char* ws, hipStream_t s) {
+                 float* dx, float* dw, float* dbias, char* ws, hipStream_t s, int hs = 0, int wsrc = 0, int sstep = 0, int soff = 0) {
   int rc;
   void* dzbuf = ws + P.off_dz;
-  if ((rc = launch_pack_halo<BF16>(dy, d->relu ? y : nullptr, dzbuf, P.rows, d->n, d->h, d->w, P.pad, d->cout, P.cop, 0, s))) return rc;
+  if (sstep == 0) rc = launch_pack_halo<BF16>(dy, d->relu ? y : nullptr, dzbuf, P.rows, d->n, d->h, d->w, P.pad, d->cout, P.cop, 0, s);
+  else rc = launch_pack_halo_scatter<BF16>(dy, d->relu ? y : nullptr, dzbuf, P.rows, d->n, d->h, d->w, P.pad, d->cout, P.cop, hs, wsrc, sstep, soff, s);
+  if (rc) return rc;
   if (dx != nullptr) {
     WpackArgs wa;
     wa.w = w; wa.out = reinterpret_cast<unsigned short*>(ws + P.off_w);
@@ -612,6 +644,59 @@ extern "C" int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, 
   char* ws = static_cast<char*>(workspace);
   return d->dtype == RON_DTYPE_BF16 ? run_backward<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s)
                                     : run_backward<false>(d, P, x, w, y, dy, dx, dw, dbias, ws, s);
+}
+
+// ---- ron_conv2d_padded_backward_nhwc: the 3x3 convolutions of the SSD extra blocks ----------------------------------------------------
+// pad2d(cpad) + 3x3 VALID at stride s is the stride-1 SAME convolution sampled at (o + s oy, o + s ox), o = 1 - cpad.  So its
+// backward is the stride-1 SAME backward of dz scattered to those pixels of a zero map of the input's size: dx, dw and dbias are the
+// same sums with zero terms added.  The only new device code is the scatter in the pack (conv_bwd_pack_halo_kernel<.., true>); the
+// plan, the data gradient, the weight gradient and the column sums run unchanged on the full-resolution geometry.  At stride 2 that
+// is four times the MFMA work of a strided gather, on maps of 32 x 32 and smaller.
+namespace ron {
+namespace {
+
+struct PaddedPlan : BackwardPlan {
+  int ho = 0, wo = 0, soff = 0;
+};
+
+int plan_padded(const ron_conv_desc* d, int cpad, PaddedPlan* P) {
+  RON_REQUIRE(d != nullptr, "conv padded backward: NULL descriptor");
+  if (int rc0 = check_conv_desc(d)) return rc0;
+  RON_REQUIRE(d->kh == 3 && d->kw == 3 && d->dilation == 1, "conv padded backward: filter %d x %d, dilation %d: 3 x 3, dilation 1 only (the 4 x 4 of block12 is ron_conv2d_k2s2_backward_nhwc on its inner taps)",
+              d->kh, d->kw, d->dilation);
+  RON_REQUIRE((d->stride == 2 && cpad == 1) || (d->stride == 1 && cpad == 0),
+              "conv padded backward: stride %d with padding %d: (2, 1) = pad2d(1) + stride-2 VALID or (1, 0) = plain VALID only", d->stride, cpad);
+  RON_REQUIRE(cpad == 1 || (d->h >= 3 && d->w >= 3), "conv padded backward: map %d x %d: a VALID 3 x 3 convolution needs h, w >= 3", d->h, d->w);
+  ron_conv_desc full = *d;          // the stride-1 SAME convolution on the same map
+  full.stride = 1;
+  if (int rc = plan_backward(&full, P)) return rc;
+  P->ho = (d->h + 2 * cpad - 3) / d->stride + 1;
+  P->wo = (d->w + 2 * cpad - 3) / d->stride + 1;
+  P->soff = 1 - cpad;
+  return RON_OK;
+}
+
+}  // namespace
+}  // namespace ron
+
+extern "C" int64_t ron_conv2d_padded_backward_workspace_bytes(const ron_conv_desc* d, int cpad) {
+  ron::PaddedPlan P;
+  if (ron::plan_padded(d, cpad, &P) != RON_OK) return -1;
+  return P.total;
+}
+
+extern "C" int ron_conv2d_padded_backward_nhwc(const ron_conv_desc* d, int cpad, const float* x, const float* w, const float* y, const float* dy,
+                                               float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream) {
+  using namespace ron;
+  PaddedPlan P;
+  if (int rc = plan_padded(d, cpad, &P)) return rc;
+  if (int rc = check_backward_call("conv padded backward", "ron_conv2d_padded_backward_workspace_bytes", d, P, x, w, y, dy, dx, dw, workspace,
+                                   workspace_bytes))
+    return rc;
+  hipStream_t s = (hipStream_t)stream;
+  char* ws = static_cast<char*>(workspace);
+  return d->dtype == RON_DTYPE_BF16 ? run_backward<true>(d, P, x, w, y, dy, dx, dw, dbias, ws, s, P.ho, P.wo, d->stride, P.soff)
+                                    : run_backward<false>(d, P, x, w, y, dy, dx, dw, dbias, ws, s, P.ho, P.wo, d->stride, P.soff);
 }
 
 // ---- ron_conv2d_k2s2_backward_nhwc: the 2x2 stride-2 convolution and the 2x2 stride-2 transposed convolution ----------------------------

@@ -335,4 +335,47 @@ extern "C" int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, i
   return RON_OK;
 }
 
+// pool5 of SSD: the graph's launch_maxpool3x3s1 on packed tensors.  The kernel starts its maximum at 0 (the zero halo takes part), so
+// it is slim.max_pool2d [3,3] stride 1 SAME for NON-NEGATIVE inputs only: what pool5 sees behind conv5_3's ReLU.
+extern "C" int ron_maxpool3x3s1_nhwc(const float* x, int n, int h, int w, int c, int dtype, float* y, void* stream) {
+  using namespace ron;
+  RON_REQUIRE(x && y && n > 0 && h > 0 && w > 0 && c > 0, "bad argument");
+  RON_REQUIRE(dtype >= 0 && dtype <= RON_DTYPE_F16X3, "bad dtype");
+  hipStream_t s = (hipStream_t)stream;
+  const int esz = (int)dtype_size(dtype);
+  TensorView vin = make_view(nullptr, n, h, w, c, 1, esz);
+  TensorView vout = make_view(nullptr, n, h, w, c, 1, esz);
+  DevBuf d_in, d_out;
+  int rc;
+  if ((rc = alloc(&d_in, vin.bytes, true))) return rc;
+  if ((rc = alloc(&d_out, vout.bytes, true))) return rc;
+  vin.base = d_in.p; vout.base = d_out.p;
+  if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
+  if ((rc = launch_maxpool3x3s1(vin, vout, dtype, s))) return rc;
+  if ((rc = launch_unpack(vout, dtype, 0, y, s))) return rc;
+  RON_HIP_CHECK(hipStreamSynchronize(s));
+  return RON_OK;
+}
+
+// block4 of SSD: the graph's launch_l2norm on packed tensors; gamma is a DEVICE fp32 vector [c], read as it stands
+extern "C" int ron_l2norm_nhwc(const float* x, const float* gamma, int n, int h, int w, int c, int dtype, float* y, void* stream) {
+  using namespace ron;
+  RON_REQUIRE(x && gamma && y && n > 0 && h > 0 && w > 0 && c > 0, "bad argument");
+  RON_REQUIRE(dtype >= 0 && dtype <= RON_DTYPE_F16X3, "bad dtype");
+  hipStream_t s = (hipStream_t)stream;
+  const int esz = (int)dtype_size(dtype);
+  TensorView vin = make_view(nullptr, n, h, w, c, 1, esz);
+  TensorView vout = make_view(nullptr, n, h, w, c, 1, esz);
+  DevBuf d_in, d_out;
+  int rc;
+  if ((rc = alloc(&d_in, vin.bytes, true))) return rc;
+  if ((rc = alloc(&d_out, vout.bytes, true))) return rc;
+  vin.base = d_in.p; vout.base = d_out.p;
+  if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
+  if ((rc = launch_l2norm(vin, vout, gamma, dtype, s))) return rc;
+  if ((rc = launch_unpack(vout, dtype, 0, y, s))) return rc;
+  RON_HIP_CHECK(hipStreamSynchronize(s));
+  return RON_OK;
+}
+
 extern "C" int ron_conv_num_tile_cfgs(void) { return ron::conv_num_cfgs(); }

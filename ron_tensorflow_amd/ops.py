@@ -508,16 +508,17 @@ def _backward_desc(n, h, w, cin, cout, k, dilation, relu, dtype, splitk):
     return _lib.ConvDesc(n, h, w, cin, cout, k, k, 1, dilation, int(relu), 0, _lib.DTYPES[dtype], -1, 0, 0, 0, splitk, 0)
 
 
-def _desc_workspace_bytes(op, d):
-    """ron_<op>_workspace_bytes of a descriptor; raises on one the library refuses."""
-    nbytes = getattr(lib(), 'ron_%s_workspace_bytes' % op)(C.byref(d))
+def _desc_workspace_bytes(op, d, *extra):
+    """ron_<op>_workspace_bytes of a descriptor (and the operator's arguments behind it); raises on one the library refuses."""
+    nbytes = getattr(lib(), 'ron_%s_workspace_bytes' % op)(C.byref(d), *extra)
     if nbytes < 0:
         raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
     return int(nbytes)
 
 
-def _conv_backward_call(op, describe, x, w, dy, y, relu, need, workspace):
-    """What conv2d_backward_nhwc and conv2d_k2s2_backward_nhwc (`op`: the name without _nhwc) share: the arguments made contiguous
+def _conv_backward_call(op, describe, x, w, dy, y, relu, need, workspace, extra=()):
+    """What conv2d_backward_nhwc, conv2d_k2s2_backward_nhwc and conv2d_padded_backward_nhwc (`op`: the name without _nhwc; `extra`:
+    the operator's arguments between the descriptor and x) share: the arguments made contiguous
     GPU tensors, `describe(x, w, dy)` (the operator's shape assertions; returns cout and a function that builds the descriptor),
     the checks of y and need, the workspace, the outputs and the call of ron_<op>_nhwc."""
     x, dy = x.contiguous(), dy.contiguous()
@@ -535,12 +536,12 @@ def _conv_backward_call(op, describe, x, w, dy, y, relu, need, workspace):
     unknown = set(need) - {'dx', 'dw', 'db'}
     assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
     d = desc()
-    nbytes = _desc_workspace_bytes(op, d)
+    nbytes = _desc_workspace_bytes(op, d, *extra)
     ws = _workspace(dev, nbytes) if workspace is None else workspace
     dx = torch.empty_like(x) if 'dx' in need else None
     dw = torch.empty_like(w) if 'dw' in need else None
     db = torch.empty((cout,), dtype=torch.float32, device=dev) if 'db' in need else None
-    check(getattr(lib(), 'ron_%s_nhwc' % op)(C.byref(d), ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
+    check(getattr(lib(), 'ron_%s_nhwc' % op)(C.byref(d), *extra, ptr(x), ptr(w), ptr(y if relu else None), ptr(dy), ptr(dx), ptr(dw), ptr(db),
                                               ptr(ws), int(ws.numel()), current_stream()))
     return dx, dw, db
 
@@ -841,6 +842,213 @@ def batchnorm_nhwc_fn(x, gamma, beta, moving_mean, moving_var, relu=True, eps=1e
     moving_var [C] (both, or both None) are plain buffers updated in place by the forward.  Forward and backward are ONE library
     call each on the current stream; the backward computes only the gradients autograd asks for."""
     return _BatchNormNhwcFn.apply(x, gamma, beta, moving_mean, moving_var, relu, eps, decay, dtype)
+
+
+# --------------------------------------------------------------------------- #
+# the SSD-only operators (ron_maxpool3x3s1_*, ron_l2norm_*, ron_conv2d_padded_backward_nhwc): the forwards are test operators (they
+# synchronise), the backwards real entry points like the convolution backward - they enqueue on the current stream and never synchronise
+# --------------------------------------------------------------------------- #
+def maxpool3x3s1_nhwc(x, dtype='bf16'):
+    """slim.max_pool2d [3, 3] stride 1 SAME (pool5 of SSD) through the graph's kernel: [N,H,W,C] -> [N,H,W,C].  That kernel starts
+    its maximum at 0, so this is TensorFlow's pool for NON-NEGATIVE x only (what pool5 sees behind a ReLU)."""
+    x = x.contiguous()
+    assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 4
+    n, h, w, c = x.shape
+    y = torch.empty_like(x)
+    check(lib().ron_maxpool3x3s1_nhwc(ptr(x), n, h, w, c, _lib.DTYPES[dtype], ptr(y), current_stream()))
+    return y
+
+
+def maxpool3x3s1_backward_nhwc(x, dy, dtype='bf16'):
+    """Gradient of the 3x3 stride-1 SAME max-pool at its input: x, dy [N,H,W,C] GPU fp32 -> dx [N,H,W,C].  Each window hands
+    round(dy) to the first of its in-bounds positions (row-major) whose rounded input equals the window's maximum; a position
+    adds what up to nine windows hand it in fp32 and rounds once (include/ron_hip.h); every element of dx is written."""
+    x, dy = x.contiguous(), dy.contiguous()
+    assert x.dtype == torch.float32 and dy.dtype == torch.float32 and x.is_cuda and dy.is_cuda and x.dim() == 4
+    assert dy.shape == x.shape, 'dy %s does not belong to x %s' % (tuple(dy.shape), tuple(x.shape))
+    n, h, w, c = x.shape
+    dx = torch.empty_like(x)
+    check(lib().ron_maxpool3x3s1_backward_nhwc(ptr(x), ptr(dy), n, h, w, c, _lib.DTYPES[dtype], ptr(dx), current_stream()))
+    return dx
+
+
+class _MaxPool3x3s1NhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, dtype):
+        ctx.save_for_backward(x)
+        ctx.dtype = dtype
+        return maxpool3x3s1_nhwc(x.detach(), dtype=dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return (maxpool3x3s1_backward_nhwc(x, dy, ctx.dtype) if ctx.needs_input_grad[0] else None), None
+
+
+def maxpool3x3s1_nhwc_fn(x, dtype='bf16'):
+    """maxpool3x3s1_nhwc as a torch.autograd.Function: the forward is the test operator ron_maxpool3x3s1_nhwc (non-negative x; it
+    synchronises), the backward ONE ron_maxpool3x3s1_backward_nhwc call on the current stream (none when x does not require grad)."""
+    return _MaxPool3x3s1NhwcFn.apply(x, dtype)
+
+
+def _l2_gamma(gamma, c, dev):
+    if not hasattr(gamma, 'data_ptr'):
+        gamma = torch.from_numpy(np.ascontiguousarray(gamma, dtype=np.float32)).to(dev)
+    return _bn_vectors(c, dev, gamma=gamma)[0]
+
+
+def l2norm_nhwc(x, gamma, dtype='bf16'):
+    """custom_layers.l2_normalization(scaling=True) over the channels (block4 of SSD) through the graph's kernel: x [N,H,W,C] GPU
+    fp32, gamma [C] (a GPU fp32 tensor; a numpy array is uploaded) -> y = round(xs / sqrt(max(sum xs^2, 1e-12)) * gamma)."""
+    x = x.contiguous()
+    assert x.dtype == torch.float32 and x.is_cuda and x.dim() == 4
+    n, h, w, c = x.shape
+    gamma = _l2_gamma(gamma, c, x.device)
+    y = torch.empty_like(x)
+    check(lib().ron_l2norm_nhwc(ptr(x), ptr(gamma), n, h, w, c, _lib.DTYPES[dtype], ptr(y), current_stream()))
+    return y
+
+
+def l2norm_backward_workspace_bytes(n, h, w, c, dtype='bf16'):
+    """Bytes of workspace l2norm_backward_nhwc needs (host arithmetic; raises on a shape the library refuses)."""
+    nbytes = lib().ron_l2norm_backward_workspace_bytes(n, h, w, c, _lib.DTYPES[dtype])
+    if nbytes < 0:
+        raise _lib.RonError('libron_hip: %s' % lib().ron_last_error().decode())
+    return int(nbytes)
+
+
+def l2norm_backward_nhwc(x, gamma, dy, dtype='bf16', need=('dx', 'dgamma'), workspace=None):
+    """Gradients of l2norm_nhwc: (dx, dgamma), None for those not in `need`.  x, dy [N,H,W,C], gamma [C] GPU fp32.  dx comes back
+    as storage-type values in fp32, dgamma [C] as an unrounded fp32 sum in a fixed order; a pixel whose sum of squares is below
+    1e-12 takes the clamped branch (include/ron_hip.h).  `workspace`: a uint8 GPU tensor of at least
+    l2norm_backward_workspace_bytes(...) bytes, or None for the cached per-device, per-stream buffer."""
+    x, dy = x.contiguous(), dy.contiguous()
+    dev = x.device
+    assert x.is_cuda and dy.is_cuda and x.dtype == torch.float32 and dy.dtype == torch.float32 and x.shape == dy.shape and x.dim() == 4
+    n, h, w, c = x.shape
+    gamma = _l2_gamma(gamma, c, dev)
+    unknown = set(need) - {'dx', 'dgamma'}
+    assert not unknown, 'need: unknown output(s) %s' % sorted(unknown)
+    ws = _workspace(dev, l2norm_backward_workspace_bytes(n, h, w, c, dtype)) if workspace is None else workspace
+    dx = torch.empty_like(x) if 'dx' in need else None
+    dgamma = torch.empty_like(gamma) if 'dgamma' in need else None
+    check(lib().ron_l2norm_backward_nhwc(ptr(x), ptr(gamma), ptr(dy), n, h, w, c, _lib.DTYPES[dtype], ptr(dx), ptr(dgamma), ptr(ws),
+                                         int(ws.numel()), current_stream()))
+    return dx, dgamma
+
+
+class _L2NormNhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, gamma, dtype):
+        ctx.save_for_backward(x, gamma)
+        ctx.dtype = dtype
+        return l2norm_nhwc(x.detach(), gamma.detach(), dtype=dtype)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma = ctx.saved_tensors
+        need = tuple(name for name, on in zip(('dx', 'dgamma'), ctx.needs_input_grad[:2]) if on)
+        dx, dgamma = l2norm_backward_nhwc(x, gamma, dy, dtype=ctx.dtype, need=need) if need else (None, None)
+        return dx, dgamma, None
+
+
+def l2norm_nhwc_fn(x, gamma, dtype='bf16'):
+    """l2norm_nhwc as a torch.autograd.Function: x [N,H,W,C], gamma [C] GPU fp32 tensors.  The forward is the test operator
+    ron_l2norm_nhwc (it synchronises), the backward ONE ron_l2norm_backward_nhwc call on the current stream, computing only the
+    gradients autograd asks for."""
+    return _L2NormNhwcFn.apply(x, gamma, dtype)
+
+
+def _padded_desc(n, h, w, cin, cout, stride, relu, dtype, splitk):
+    return _lib.ConvDesc(n, h, w, cin, cout, 3, 3, stride, 1, int(relu), 0, _lib.DTYPES[dtype], -1, 0, 0, 0, splitk, 0)
+
+
+def _padded_out_hw(h, w, k, stride, cpad):
+    return (h + 2 * cpad - k) // stride + 1, (w + 2 * cpad - k) // stride + 1
+
+
+def _is_block12(k, stride, cpad, h, w):
+    """pad2d(1) + 4x4 VALID on a 2x2 map (block12 of SSD-512): only the filter's inner 2x2 taps meet data."""
+    return k == 4 and stride == 1 and cpad == 1 and h == 2 and w == 2
+
+
+def conv2d_padded_backward_workspace_bytes(n, h, w, cin, cout, stride=2, cpad=1, relu=True, dtype='bf16', splitk=-1):
+    """Bytes of workspace conv2d_padded_backward_nhwc needs for a 3x3 convolution (n, h, w: the input x; host arithmetic; raises on
+    what the library refuses)."""
+    return _desc_workspace_bytes('conv2d_padded_backward', _padded_desc(n, h, w, cin, cout, stride, relu, dtype, splitk), int(cpad))
+
+
+def conv2d_padded_backward_nhwc(x, w, dy, y=None, stride=2, cpad=1, relu=True, dtype='bf16', splitk=-1, need=('dx', 'dw', 'db'),
+                                workspace=None):
+    """Gradients of the padded convolutions of the SSD extra blocks, y = act(conv_VALID(pad2d(x, cpad), w, stride) + bias):
+    (dx, dw, db), None for those not in `need`.  3x3 filters with (stride, cpad) = (2, 1) or (1, 0): ONE
+    ron_conv2d_padded_backward_nhwc call; x [N,H,W,Cin], w HWIO [3,3,Cin,Cout], y and dy [N,Ho,Wo,Cout] with
+    Ho = (H + 2 cpad - 3) // stride + 1.  A 4x4 filter with cpad 1 on a 2x2 map (block12 of SSD-512) meets data in its inner 2x2
+    taps only: ONE ron_conv2d_k2s2_backward_nhwc call on w[1:3, 1:3], sliced and re-embedded on the device, dw zero in the twelve
+    outer taps.  Anything else raises RonError.  Everything else as conv2d_backward_nhwc."""
+    k = w.shape[0]
+    if _is_block12(k, stride, cpad, x.shape[1], x.shape[2]):
+        if not hasattr(w, 'data_ptr'):
+            w = torch.from_numpy(np.ascontiguousarray(w, dtype=np.float32)).to(x.device)
+        assert tuple(w.shape[:2]) == (4, 4)
+        dx, dwi, db = conv2d_k2s2_backward_nhwc(x, w[1:3, 1:3].contiguous(), dy, y, relu=relu, dtype=dtype, splitk=splitk, need=need,
+                                                workspace=workspace)
+        dw = None
+        if dwi is not None:
+            dw = torch.zeros_like(w)
+            dw[1:3, 1:3] = dwi
+        return dx, dw, db
+    if k != 3 or tuple(w.shape[:2]) != (3, 3):
+        raise _lib.RonError('conv2d_padded_backward_nhwc: filter %s, stride %d, cpad %d on a %d x %d map: 3x3 filters, or the 4x4 '
+                            'filter with cpad 1 on a 2x2 map' % (tuple(w.shape[:2]), stride, cpad, x.shape[1], x.shape[2]))
+
+    def describe(x, w, dy):
+        n, h, wd, cin = x.shape
+        cout = w.shape[3]
+        assert tuple(w.shape) == (3, 3, cin, cout), 'w %s' % (tuple(w.shape),)
+        if (stride, cpad) in ((2, 1), (1, 0)) and min(h, wd) + 2 * cpad >= 3:
+            assert tuple(dy.shape) == (n,) + _padded_out_hw(h, wd, 3, stride, cpad) + (cout,), 'dy %s' % (tuple(dy.shape),)
+        return cout, lambda: _padded_desc(n, h, wd, cin, cout, stride, relu, dtype, splitk)
+    return _conv_backward_call('conv2d_padded_backward', describe, x, w, dy, y, relu, need, workspace, extra=(int(cpad),))
+
+
+class _Conv2dPaddedNhwcFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w, bias, stride, cpad, relu, dtype):
+        b = None if bias is None else bias.detach().cpu().numpy()
+        wh = w.detach().cpu().numpy()
+        k, (h, wd) = w.shape[0], x.shape[1:3]
+        if _is_block12(k, stride, cpad, h, wd):
+            y = conv2d_nhwc(x.detach(), wh[1:3, 1:3], b, stride=2, relu=relu, dtype=dtype)
+        elif tuple(w.shape[:2]) == (3, 3) and (stride, cpad) in ((2, 1), (1, 0)) and min(h, wd) + 2 * cpad >= 3:
+            # the stride-1 SAME convolution sampled at (o + stride oy, o + stride ox): the same values
+            o = 1 - cpad
+            ho, wo = _padded_out_hw(h, wd, 3, stride, cpad)
+            full = conv2d_nhwc(x.detach(), wh, b, relu=relu, dtype=dtype)
+            y = full[:, o::stride, o::stride][:, :ho, :wo].contiguous()
+        else:
+            raise _lib.RonError('conv2d_padded_nhwc_fn: filter %s, stride %d, cpad %d on a %d x %d map: 3x3 with (stride, cpad) = (2, 1) '
+                                'or (1, 0), or 4x4 with cpad 1 on a 2x2 map' % (tuple(w.shape[:2]), stride, cpad, h, wd))
+        ctx.save_for_backward(x, w, y)
+        ctx.cfg = (stride, cpad, relu, dtype, bias is not None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, w, y = ctx.saved_tensors
+        stride, cpad, relu, dtype, has_bias = ctx.cfg
+        need = _needed_grads(ctx, has_bias)
+        dx, dw, db = (conv2d_padded_backward_nhwc(x, w, dy, y, stride=stride, cpad=cpad, relu=relu, dtype=dtype, need=need) if need
+                      else (None, None, None))
+        return dx, dw, db, None, None, None, None
+
+
+def conv2d_padded_nhwc_fn(x, w, bias, stride=2, cpad=1, relu=True, dtype='bf16'):
+    """act(conv_VALID(pad2d(x, cpad), w, stride) + bias) for the convolutions of the SSD extra blocks as a torch.autograd.Function on GPU
+    fp32 tensors: 3x3 with (stride, cpad) = (2, 1) or (1, 0), or 4x4 with cpad 1 on a 2x2 map (block12 of SSD-512); anything else
+    raises RonError.  The forward of the 3x3 forms is ron_conv2d_nhwc at stride 1, sliced (host weights, synchronises: tests and
+    small experiments); the backward is ONE entry-point call on the current stream (conv2d_padded_backward_nhwc)."""
+    return _Conv2dPaddedNhwcFn.apply(x, w, bias, stride, cpad, relu, dtype)
 
 
 # --------------------------------------------------------------------------- #
