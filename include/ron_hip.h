@@ -622,6 +622,27 @@ int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, const float* w
  * split-K factor, tile order (0 = column tiles fastest inside an XCD's run, 1 = row tiles fastest, P >= 2 = panels of P column tiles
  * walked row by row), K order (1 = taps innermost)}.  Allocates and frees the operands like ron_conv2d_nhwc does. */
 int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]);
+/* ... and the columns of the row-gather kernel's tile for the same launch: the width of the tile configuration (64 / 128 / 256), or 224
+ * where a bf16 / f16 convolution of 193 .. 224 output channels runs the four-wave 256 x 256 configuration on its 256 x 224 form
+ * (environment RON_IGEMM224=0, read per call by the single-operator entry points only - a test / sweep hook, the graph does not
+ * read it: never); 0 for the halo-patch and resident-weight kernels. */
+int ron_conv_plan_n_tile(const ron_conv_desc* d, int32_t* n_tile);
+/* Tests / tooling: one or two plain stride-1 convolutions (db NULL: one), each over its own input, with the fp32 output of the
+ * graph's head layers - the kernel's epilogue writes y [n,h,w,cout] (device, fp32) itself.  grouped = 0: launches of their own
+ * (tile_cfg / splitk of each descriptor); grouped != 0: both as the members of ONE grouped launch of 256 x 256 tiles (what the
+ * batch plan does with the class heads of the coarse scales; both padded widths must be multiples of 256 and tile_cfg -1 or 0,
+ * else RON_ERR_INVALID; splitk of the descriptors when both are >= 1, else the group's own plan).  n_tiles (may be NULL): the
+ * column-tile width each convolution ran on (64 / 128 / 256, or 224), one per convolution. */
+int ron_conv2d_f32out_nhwc(const ron_conv_desc* da, const float* xa, const float* wa, const float* ba, float* ya,
+                           const ron_conv_desc* db, const float* xb, const float* wb, const float* bb, float* yb,
+                           int grouped, int32_t* n_tiles, void* stream);
+/* Tests / tooling: the skinny heads of a scale as the batch plan launches them - two plain 3x3 convolutions of at most 64 output
+ * channels over channel slices of ONE tensor x [n,h,w,in_cstride] (device fp32; both descriptors carry the same in_cstride > 0 and
+ * their own in_coff), as one launch of the halo-patch pair kernel, fp32 outputs ya / yb [n,h,w,cout] (device).  bf16 / f16: a pair of
+ * up to 32 and up to 48 output channels multiplies 32 + 48 columns instead of 64 + 64; full_width != 0 keeps 64 + 64.
+ * columns (may be NULL): the columns each member multiplies. */
+int ron_conv2d_patch_pair_nhwc(const ron_conv_desc* da, const ron_conv_desc* db, const float* x, const float* wa, const float* ba,
+                               const float* wb, const float* bb, float* ya, float* yb, int full_width, int32_t* columns, void* stream);
 /* Two fp32 head tensors from one convolution over a shared input - the class and the box convolution of an SSD feature layer
  * (nets/ssd_vgg_300.py:403-431), which the SSD-512 graph runs as one launch: w HWIO [kh,kw,cin,cout], its first `split_first`
  * output channels go to y_first [n,h,w,split_first], the other cout - split_first to y_second [n,h,w,cout - split_first]

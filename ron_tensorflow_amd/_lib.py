@@ -197,6 +197,9 @@ SIGNATURES = {
     'ron_conv2d_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     'ron_conv2d_pool2_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P]),
     'ron_conv_plan': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
+    'ron_conv_plan_n_tile': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(C.c_int32)]),
+    'ron_conv2d_f32out_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, C.POINTER(ConvDesc), _P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), _P]),
+    'ron_conv2d_patch_pair_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, C.c_int, C.POINTER(C.c_int32), _P]),
     'ron_conv2d_heads_nhwc': (C.c_int, [C.POINTER(ConvDesc), C.c_int, _P, _P, _P, _P, _P, _P]),
     'ron_maxpool2x2_nhwc': (C.c_int, [_P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
     'ron_conv2d_bench': (C.c_int, [C.POINTER(ConvDesc), C.c_int, C.c_int, C.POINTER(C.c_float)]),

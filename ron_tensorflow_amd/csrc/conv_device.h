@@ -17,14 +17,17 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 typedef __attribute__((ext_vector_type(8))) unsigned u32x8;
 typedef __attribute__((ext_vector_type(32))) float f32x32;
 
-template <int N> struct alignas(4 * N) F32Vec { float v[N]; };
+// A lane's vector of N adjacent channels is aligned to its size when N is a power of two; the seven channels of the 256 x 224 tile
+// start at any multiple of 7, so their vector is element-aligned (the largest power of two that divides N elements)
+constexpr int vec_align_elems(int n) { return n & -n; }
+template <int N> struct alignas(4 * vec_align_elems(N)) F32Vec { float v[N]; };
 template <int N> __device__ __forceinline__ void store_f32_vec(float* p, const float* v) {
   F32Vec<N> t;
 #pragma unroll
   for (int j = 0; j < N; ++j) t.v[j] = v[j];
   *reinterpret_cast<F32Vec<N>*>(p) = t;
 }
-template <class E, int N> struct alignas(sizeof(E) * N) EVec { E v[N]; };
+template <class E, int N> struct alignas(sizeof(E) * vec_align_elems(N)) EVec { E v[N]; };
 
 struct ConvArgs {
   const void* in;

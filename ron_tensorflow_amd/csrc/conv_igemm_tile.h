@@ -60,6 +60,14 @@ struct AccAgpr4wN128 {
   }
 };
 
+// ... of the 256 x 224 tile: block (i, j), j < 7, in a[4 * (7 * i + j) : +3] (a[0:223]); a lane's seven values are adjacent channels
+struct AccAgpr4wN224 {
+  static constexpr bool kSpecialise = true;
+  __device__ __forceinline__ void row(int i, int e, float (&v)[7]) const {
+    switch (i * 4 + e) { RON_ACC4W_N224_CASES }
+  }
+};
+
 // Everything after the K loop of conv_igemm_tile: raw fp32 slab store of a split-K slice, or the conv epilogue.
 template <class Tr, int MR, int NR, int MT, int EPA, int TM, int TN, class Reader>
 __device__ __forceinline__ void igemm_finish(const ConvArgs& p, const Reader& rd, const int* s_out_off, const int* s_out2_off, int zsplit,
@@ -123,13 +131,17 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, const unsigne
   constexpr int kRingBytes = S * (kABytes + kBBytes);
   constexpr int kChunkElems = kRowBytes / Tr::kEsz;
   static_assert(BM % kRowsPerIt == 0 && BN % kRowsPerIt == 0 && kRowsPerIt % 16 == 0, "tile / thread-count mismatch");
-  static_assert(TM % 32 == 0 && TN % 32 == 0 && S >= 2 && S <= 5, "bad wave tile / stage count");
+  static_assert(TM % 32 == 0 && (TN % 32 == 0 || (BN == 224 && TN == 112)) && S >= 2 && S <= 5, "bad wave tile / stage count");
   static_assert(NR <= 8, "vector epilogue: at most 8 channels per lane");
   static_assert(SPREAD == 1 || SPREAD == 2, "SPREAD");
   // The 256 x 256 tile on FOUR waves (128 x 128 per wave, one wave per SIMD, 256 accumulator + 256 vector registers) runs its K loop
   // as the assembly of kloop4w.inc (tools/gen_kloop4w.py): two tiles of LDS-DMA in flight over two LDS stages, three barriers per
   // K step.  bf16, f16 and the split-precision form (three MFMAs per block); fp32 stays on the eight-wave loop.
-  constexpr bool kAsmLoop = AsmLoop<Tr>::value && BM == 256 && (BN == 256 || BN == 128) && WM == 2 && WN == 2 && S == 2;
+  // 256 x 224 (bf16 / f16): the same loop with 8 x 7 blocks per wave for convolutions of 193 .. 224 output channels (the class heads:
+  // 210) - every wave issues 112 MFMAs per K step instead of 128, the two right-hand waves start at column 112.  The packed weights
+  // keep Npad = 256: rows 224 .. 255 are never staged.
+  static_assert(BN != 224 || (AsmLoop<Tr>::value && !IsSplit<Tr>::value && BM == 256 && WM == 2 && WN == 2 && S == 2), "224 columns: the four-wave bf16 / f16 tile only");
+  constexpr bool kAsmLoop = AsmLoop<Tr>::value && BM == 256 && (BN == 256 || BN == 224 || BN == 128) && WM == 2 && WN == 2 && S == 2;
   // layout: [A stage 0 .. S-1][B stage 0 .. S-1][in_off: BM ints][out_off: BM ints][out2_off: BM ints][step table (kAsmLoop)]
   char* s_a = smem;
   char* s_b = smem + S * kABytes;
@@ -308,7 +320,7 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, const unsigne
   const int a_base = wm * TM * kRowBytes;
   const int b_base = wn * TN * kRowBytes;
   if constexpr (kAsmLoop) {
-    static_assert(KS == 2 && MR == 8 && (NR == 8 || NR == 4) && A_IT == 8 && B_IT == NR, "kloop4w.inc is written for these tiles");
+    static_assert(KS == 2 && MR == 8 && (NR == 8 || NR == 7 || NR == 4) && A_IT == 8 && B_IT == NR, "kloop4w.inc is written for these tiles");
     // Step table: entry q = {soffset of the A pieces, soffset of the B pieces} of the tile's K step kt0 + q, in the launch's K order
     // (tap-major / taps innermost / position-major walk, see the loop of the other tiles below); two more entries than steps: the
     // loop stages two tiles ahead, past the end with zero-record descriptors.
@@ -365,6 +377,10 @@ __device__ __forceinline__ void conv_igemm_tile(const ConvArgs& p, const unsigne
       else if constexpr (Tr::kIsBf16) asm volatile(RON_KLOOP4W_BF16 RON_KLOOP4W_OPERANDS);
       else asm volatile(RON_KLOOP4W_F16 RON_KLOOP4W_OPERANDS);
       igemm_finish<Tr, MR, NR, MT, EPA, TM, TN>(p, AccAgpr4w{}, s_out_off, s_out2_off, zsplit, m0, n0, wm, wn, fr, fh);
+    } else if constexpr (NR == 7) {
+      if constexpr (Tr::kIsBf16) asm volatile(RON_KLOOP4W_N224_BF16 RON_KLOOP4W_OPERANDS);
+      else asm volatile(RON_KLOOP4W_N224_F16 RON_KLOOP4W_OPERANDS);
+      igemm_finish<Tr, MR, NR, MT, EPA, TM, TN>(p, AccAgpr4wN224{}, s_out_off, s_out2_off, zsplit, m0, n0, wm, wn, fr, fh);
     } else {
       if constexpr (IsSplit<Tr>::value) asm volatile(RON_KLOOP4W_N128_F16X3 RON_KLOOP4W_OPERANDS);
       else if constexpr (Tr::kIsBf16) asm volatile(RON_KLOOP4W_N128_BF16 RON_KLOOP4W_OPERANDS);
@@ -537,8 +553,12 @@ struct ConvGroupArgs {
   int enwg[kMaxEntries];      // workgroups of the member as a whole (the tile order is computed from it)
   int n;                      // members
   int ne;                     // entries
-  unsigned narrow;            // kGroupMixed: bit k set = member k runs on 128 x 64 tiles, else on 128 x 128
+  unsigned narrow;            // kGroupMixed: bit k set = member k runs on 128 x 64 tiles, else on 128 x 128;
+                              // the four-wave 256 x 256 group: bit k set = member k runs on 256 x 224 tiles
 };
+// tile forms whose grouped kernel also holds the 256 x 224 tile: the four-wave 256 x 256 tile of bf16 / f16
+template <class Tr, int BM, int BN, int WM, int WN, int S>
+constexpr bool kHas224 = AsmLoop<Tr>::value && !IsSplit<Tr>::value && BM == 256 && BN == 256 && WM == 2 && WN == 2 && S == 2;
 struct GroupPick { int k; unsigned bid, nwg; };
 __device__ __forceinline__ GroupPick pick_group_entry(const ConvGroupArgs& g, int b) {
   int k = g.eop[0], f = 0, bid0 = g.ebid0[0], nwg = g.enwg[0];
@@ -559,11 +579,22 @@ __device__ __forceinline__ ConvArgs load_group_op(int k) {
   return p;
 }
 
-template <class Tr, int BM, int BN, int WM, int WN, int S, int SPREAD>
+// N224: the instantiation for launches that HAVE a member on 256 x 224 tiles - a kernel of its own, so that every other 256 x 256
+// group runs the kernel with the one loop (both loops in one kernel cost such a group 1.2 % and ten scalar registers: profiles/r08)
+template <class Tr, int BM, int BN, int WM, int WN, int S, int SPREAD, bool N224 = false>
 __global__ __launch_bounds__(WM * WN * 64, (igemm_lds_bytes(BM, BN, S) > 80 * 1024) ? (WM * WN + 3) / 4 : 2) void conv_igemm_group_kernel(ConvGroupArgs g) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const GroupPick e = pick_group_entry(g, (int)blockIdx.x);
   const ConvArgs p = load_group_op(e.k);
+  // the four-wave 256 x 256 group (bf16 / f16): a member of 193 .. 224 output channels on the 256 x 224 tile (bit k of `narrow`,
+  // launch_conv_group) - same rows, same LDS budget, one workgroup per CU either way
+  static_assert(!N224 || kHas224<Tr, BM, BN, WM, WN, S>, "no 256 x 224 tile beside this one");
+  if constexpr (N224) {
+    if ((g.narrow >> e.k) & 1u) {
+      conv_igemm_tile<Tr, 256, 224, 2, 2, 2, SPREAD>(p, e.bid, e.nwg, smem);
+      return;
+    }
+  }
   conv_igemm_tile<Tr, BM, BN, WM, WN, S, SPREAD>(p, e.bid, e.nwg, smem);
 }
 
@@ -678,12 +709,12 @@ int launch_group_finalize(const ConvGroupArgs& g, hipStream_t s) {
   return RON_OK;
 }
 
-template <class Tr, int BM, int BN, int WM, int WN, int S, int SPREAD>
+template <class Tr, int BM, int BN, int WM, int WN, int S, int SPREAD, bool N224 = false>
 int launch_group_t(const ConvGroupArgs& g, bool any_split, hipStream_t s) {
   const size_t lds = (size_t)igemm_lds_bytes(BM, BN, S, AsmLoop<Tr>::value && BM == 256 && WM == 2);
   static PerDeviceOnce once;
-  RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_group_kernel<Tr, BM, BN, WM, WN, S, SPREAD>), (int)lds));
-  RON_LAUNCH((conv_igemm_group_kernel<Tr, BM, BN, WM, WN, S, SPREAD>), dim3(g.first[g.ne]), dim3(WM * WN * 64), lds, s, g);
+  RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&conv_igemm_group_kernel<Tr, BM, BN, WM, WN, S, SPREAD, N224>), (int)lds));
+  RON_LAUNCH((conv_igemm_group_kernel<Tr, BM, BN, WM, WN, S, SPREAD, N224>), dim3(g.first[g.ne]), dim3(WM * WN * 64), lds, s, g);
   if (any_split) launch_group_finalize<Tr>(g, s);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -708,7 +739,8 @@ template <> struct DtypeOf<TraitsF32S> { static constexpr int value = RON_DTYPE_
 template <> struct DtypeOf<TraitsF16X3S> { static constexpr int value = RON_DTYPE_F16X3; };
 
 // The four-wave tiles with the assembly K loop (bf16 / f16 / f16x3), instantiated in conv_mfma4w.hip: the 256 x bn tile of one
-// convolution (bn = 256 or 128), and the grouped form of the 256 x 256 tile.
+// convolution (bn = 256 or 128; 224: bf16 / f16 only), and the grouped form of the 256 x 256 tile (ConvGroupArgs::narrow: its members
+// on 256 x 224 tiles).
 int launch_igemm4w(int dtype, int bn, const ConvArgs& a, hipStream_t s);
 int launch_igemm4w_group(int dtype, const ConvGroupArgs& g, bool any_split, hipStream_t s);
 

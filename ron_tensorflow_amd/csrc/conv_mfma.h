@@ -53,6 +53,9 @@ struct ConvLaunch {
   int split_n = 0, split_first = 0;
   int center_from = 0;           // > 0: output channels >= center_from have weights in the CENTRE tap only (a 1x1 branch packed beside
                                  // 3x3 ones: nets/ron_vgg_320.py:378-397); their column tiles run that tap's K steps alone
+  int n224 = -1;                 // -1: 193 .. 224 output channels run the four-wave 256 x 256 configuration on 256 x 224 tiles where the rule
+                                 // of conv_mfma.hip (conv_takes_224) says so, and a skinny pair of the patch kernel multiplies 32 + 48 columns
+                                 // (conv_patch.hip); 0: never - full-width tiles (the single-operator entry points, for side-by-side runs)
   int halo_skip = 1;             // position-major rows + per-tile skipping of filter rows that only see the halo, where it pays (0: never)
   int cfg = -1;                  // tile configuration (kCfg* below); -1 = pick by shape
   int splitk = -1;               // split-K factor; -1 = pick by grid size, 1 = off
@@ -96,8 +99,10 @@ constexpr int kConvMaxTileOrder = 63;    // ConvArgs::m_fastest
 int check_conv_desc(const ron_conv_desc* d);
 
 int launch_conv(const ConvLaunch& c, hipStream_t stream);
-// what launch_conv would do with `c`: out = {tile configuration (kCfg*), split-K factor, tile order (ConvArgs::m_fastest), K order (taps_inner)}
-int conv_describe(const ConvLaunch& c, int out[4]);
+// what launch_conv would do with `c`: out = {tile configuration (kCfg*), split-K factor, tile order (ConvArgs::m_fastest), K order (taps_inner)};
+// n_tile (may be null): columns of the row-gather kernel's tile - the configuration's own width, or 224 where a convolution of
+// 193 .. 224 output channels runs the four-wave 256 x 256 configuration on its 256 x 224 form; 0 for the other kernels
+int conv_describe(const ConvLaunch& c, int out[4], int* n_tile = nullptr);
 // 3x3 / stride 1 / pad 1 on a 64-channel map, weights resident in LDS (conv_c64.hip); pack_conv_c64_weights builds wgt_c64
 bool conv_c64_applicable(const ConvLaunch& c);
 int launch_conv_c64(const ConvLaunch& c, hipStream_t stream);
@@ -108,7 +113,10 @@ int conv_patch_pick(const ConvLaunch& c);          // kCfgPatch* when the patch 
 int launch_conv_patch(const ConvLaunch& c, int cfg, hipStream_t stream);
 // two convolutions over channel slices of the same map as ONE launch of the patch kernel (the skinny heads of a scale)
 bool conv_patch_pair_applicable(const ConvLaunch& a, const ConvLaunch& b);
-int launch_conv_patch_pair(const ConvLaunch& a, const ConvLaunch& b, hipStream_t stream);
+// force_cfg >= 0 (tooling): that patch configuration whatever the grid size (the pair must still share its input tensor)
+int launch_conv_patch_pair(const ConvLaunch& a, const ConvLaunch& b, hipStream_t stream, int force_cfg = -1);
+// columns each member of such a pair multiplies on the 64-column tile: 32 / 48 / 64 (conv_patch.hip, patch_pair_widths)
+int conv_patch_pair_columns(const ConvLaunch& a, const ConvLaunch& b, int out[2]);
 // Elements along K one staging step covers for this dtype (Cin must be a multiple of it).
 int conv_k_chunk(int dtype);
 int conv_n_tile(int cout);       // granularity Cout is padded to (64 or 128)
@@ -119,7 +127,9 @@ int64_t conv_scratch_bytes(const ConvLaunch& c);   // fp32 split-K slabs this la
 // Several mutually independent convolutions as ONE launch of the row-gather kernel (tile kCfgIgemm128x64, kCfgIgemm128 or kGroupMixed)
 // sk_plan: the members' split-K factors from conv_group_plan (depends on the members' geometry and the batch only: callers cache it;
 // the mixed-width form models the launch's schedule, ~1 ms of host time), or null to compute them here
-int launch_conv_group(const ConvLaunch* ls, int n, int cfg, void* scratch, int64_t scratch_bytes, hipStream_t stream, const int* sk_plan = nullptr);
+// n_tiles (may be null): the width of the column tile member k runs on (the configuration's own, or 224), in the order of `ls`
+int launch_conv_group(const ConvLaunch* ls, int n, int cfg, void* scratch, int64_t scratch_bytes, hipStream_t stream, const int* sk_plan = nullptr,
+                      int* n_tiles = nullptr);
 void conv_group_plan(const ConvLaunch* ls, int n, int cfg, int* sk);
 int64_t conv_group_scratch_bytes(const ConvLaunch* ls, int n, int cfg, const int* sk_plan = nullptr);   // sk_plan: from conv_group_plan, or null
 constexpr int kMaxConvGroup = 8;

@@ -31,11 +31,12 @@ static bool asm_loop_ok(int steps_per_wg) {
 }
 
 template <class Tr>
-int launch_cfg(int cfg, const ConvArgs& a, hipStream_t s) {
+int launch_cfg(int cfg, int bn, const ConvArgs& a, hipStream_t s) {
   switch (cfg) {
     case kCfgIgemm256: case kCfgIgemm256TapsInner:                                                      // (the K order: ConvArgs::taps_inner)
       if constexpr (AsmLoop<Tr>::value) {
-        if (asm_loop_ok(a.kt_split)) return launch_igemm4w(DtypeOf<Tr>::value, 256, a, s);               // four waves, assembly K loop (conv_mfma4w.hip)
+        // four waves, assembly K loop (conv_mfma4w.hip); bn = 224: its 256 x 224 form (conv_takes_224)
+        if (asm_loop_ok(a.kt_split)) return launch_igemm4w(DtypeOf<Tr>::value, bn == 224 ? 224 : 256, a, s);
       }
       return launch_t<Tr, 256, 256, 4, 2, 2, 1>(a, s);
     case kCfgIgemm128: return launch_t<Tr, 128, 128, 2, 2, 2, 1>(a, s);
@@ -86,6 +87,18 @@ int check_conv_desc(const ron_conv_desc* d) {
 }
 
 static bool igemm_is256(int cfg) { return cfg == kCfgIgemm256 || cfg == kCfgIgemm256TapsInner; }
+
+// The 256 x 224 form of the four-wave 256 x 256 tile: a plain bf16 / f16 convolution of 193 .. 224 output channels in one column
+// tile (the class-prediction heads: Cout = 210, 46 of 256 columns padding) runs 8 x 7 blocks per wave instead of 8 x 8: an eighth
+// fewer MFMAs and B fragment reads per K step, evenly over the four waves.  Which columns a workgroup computes changes, the K order of
+// an output element does not: the results are the 256-column tile's, bit for bit.  Not a tile configuration of its own - it is the
+// width launch_conv / launch_conv_group run kCfgIgemm256[TapsInner] at for such a launch (conv_describe reports it as the N tile).
+// `steps_per_wg`: the K steps of a workgroup (the assembly loop's step table).  ConvLaunch::n224 = 0: always 256 columns (what the
+// single-operator entry points set under RON_IGEMM224=0, so that tests and sweeps can run both forms side by side).
+static bool conv_takes_224(const ConvLaunch& c, int steps_per_wg) {
+  return c.n224 != 0 && dtype_is_half(c.dtype) && c.Npad == 256 && c.Cout > 192 && c.Cout <= 224 && c.up == 0 && !c.pool && c.center_from == 0 &&
+         c.split_n == 0 && c.out2.base == nullptr && asm_loop_ok(steps_per_wg);
+}
 static int igemm_bm(int cfg) { return (igemm_is256(cfg) || cfg == kCfgIgemm256x128) ? 256 : 128; }
 static int igemm_bn(int cfg) { return igemm_is256(cfg) ? 256 : (cfg == kCfgIgemm128x64 ? 64 : 128); }
 // workgroups of a configuration the chip holds at once (256 CUs; 64 KB of LDS lets two share a CU)
@@ -271,14 +284,16 @@ int conv_pick_cfg(const ConvLaunch& c) {
   return cfg;
 }
 
-// Everything launch_conv decides before it launches: the tile configuration and the kernel arguments (split-K, tile order, K order).
-static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out);
+// Everything launch_conv decides before it launches: the tile configuration, the kernel arguments (split-K, tile order, K order) and
+// the width of the row-gather kernel's column tile (the configuration's own, or 224: conv_takes_224; 0 for the other kernels).
+static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out, int* bn_out);
 
-int conv_describe(const ConvLaunch& c, int out[4]) {
-  int cfg = -1;
+int conv_describe(const ConvLaunch& c, int out[4], int* n_tile) {
+  int cfg = -1, bn = 0;
   ConvArgs a = ConvArgs();
-  const int rc = plan_conv(c, &cfg, &a);
+  const int rc = plan_conv(c, &cfg, &a, &bn);
   if (rc != RON_OK) return rc;
+  if (n_tile != nullptr) *n_tile = bn;
   out[0] = cfg;
   const bool gather = !conv_cfg_is_patch(cfg) && cfg != kCfgC64Resident;
   out[1] = gather ? a.splitk : 1; out[2] = gather ? a.m_fastest : 0; out[3] = gather ? a.taps_inner : 0;
@@ -286,16 +301,16 @@ int conv_describe(const ConvLaunch& c, int out[4]) {
 }
 
 int launch_conv(const ConvLaunch& c, hipStream_t stream) {
-  int cfg = -1;
+  int cfg = -1, bn = 0;
   ConvArgs a = ConvArgs();
-  int rc = plan_conv(c, &cfg, &a);
+  int rc = plan_conv(c, &cfg, &a, &bn);
   if (rc != RON_OK) return rc;
   if (conv_cfg_is_patch(cfg)) return launch_conv_patch(c, cfg, stream);
   if (cfg == kCfgC64Resident) return launch_conv_c64(c, stream);
-  if (c.dtype == RON_DTYPE_BF16) rc = launch_cfg<TraitsBF16S>(cfg, a, stream);
-  else if (c.dtype == RON_DTYPE_F16) rc = launch_cfg<TraitsF16S>(cfg, a, stream);
-  else if (c.dtype == RON_DTYPE_F32) rc = launch_cfg<TraitsF32S>(cfg, a, stream);
-  else if (c.dtype == RON_DTYPE_F16X3) rc = launch_cfg<TraitsF16X3S>(cfg, a, stream);
+  if (c.dtype == RON_DTYPE_BF16) rc = launch_cfg<TraitsBF16S>(cfg, bn, a, stream);
+  else if (c.dtype == RON_DTYPE_F16) rc = launch_cfg<TraitsF16S>(cfg, bn, a, stream);
+  else if (c.dtype == RON_DTYPE_F32) rc = launch_cfg<TraitsF32S>(cfg, bn, a, stream);
+  else if (c.dtype == RON_DTYPE_F16X3) rc = launch_cfg<TraitsF16X3S>(cfg, bn, a, stream);
   else { ron::set_error("conv: unknown dtype %d", c.dtype); return RON_ERR_INVALID; }
   if (rc != RON_OK || a.splitk == 1) return rc;
   if (c.dtype == RON_DTYPE_BF16) return launch_finalize<TraitsBF16S>(a, stream);
@@ -304,8 +319,9 @@ int launch_conv(const ConvLaunch& c, hipStream_t stream) {
   return launch_finalize<TraitsF32S>(a, stream);
 }
 
-static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out) {
+static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out, int* bn_out) {
   ConvArgs& a = *a_out;
+  *bn_out = 0;
   {
     const int rc = check_conv_fields(c);      // before the pickers divide by any of it
     if (rc != RON_OK) return rc;
@@ -370,6 +386,11 @@ static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out) {
     RON_REQUIRE(c.center_from % BN == 0 && (c.kh & 1) && (c.kw & 1) && c.up == 0,
                 "conv: centre-tap-only columns need an odd filter and a boundary on the N tile (%d)", BN);
   RON_REQUIRE((int64_t)c.Npad * K * esz == c.wgt_bytes, "conv: packed weight size mismatch");
+  // 193 .. 224 output channels on the four-wave 256 x 256 tile: its 224-column form.  A split factor this function chose itself keeps
+  // the 256 columns: those are the launches of fewer than 129 tiles (block4_cls_pred below batch 24), which nobody has measured on
+  // the narrower tile; a factor the caller forces (single-operator entry points, the sweep) does not stand in the way.
+  *bn_out = BN;
+  if (igemm_is256(cfg) && (a.splitk == 1 || c.splitk >= 0) && conv_takes_224(c, a.kt_split)) *bn_out = 224;
   return RON_OK;
 }
 
@@ -459,6 +480,10 @@ static void group_splitks_scheduled(const ConvLaunch* ls, int n, int cfg, int* s
     const int mcfg = group_member_cfg(cfg, c), BM = igemm_bm(mcfg);
     step_us[k] = mcfg == kCfgIgemm256 ? 1.4 : (mcfg == kCfgIgemm128 ? 1.15 : 0.75);
     KT[k] = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
+    // a member on the 256 x 224 tile: 7/8 of the MFMAs of a step (block4_cls_pred alone measured 0.83 x, profiles/r08).  The plans of
+    // RON-320 full at batches 1 .. 64 are the same for any value from 1.15 to 1.4 here: the entry moves no split factor today.
+    // (KT, not the slice the plan will give the member: a slice is never longer, so the step-table limit cannot turn out tighter.)
+    if (mcfg == kCfgIgemm256 && conv_takes_224(c, KT[k])) step_us[k] = 1.4 * 7 / 8;
     // centre-tap-only column tiles are a ninth of a tile: count them as that
     const int cols = c.Npad / igemm_bn(mcfg), cols_long = c.center_from > 0 ? c.center_from / igemm_bn(mcfg) : cols;
     tiles[k] = ((M + BM - 1) / BM) * cols_long + ((M + BM - 1) / BM) * (cols - cols_long) / (c.kh * c.kw);
@@ -551,7 +576,8 @@ void conv_group_plan(const ConvLaunch* ls, int n, int cfg, int* sk) {
   group_splitks(ls, n, cfg, sk);
 }
 
-int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, int64_t scratch_bytes, hipStream_t stream, const int* sk_plan) {
+int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, int64_t scratch_bytes, hipStream_t stream, const int* sk_plan,
+                      int* n_tiles) {
   RON_REQUIRE(n >= 1 && n <= kMaxGroup, "conv group: %d launches (1..%d)", n, kMaxGroup);
   for (int k = 0; k < n; ++k) RON_REQUIRE(ls_in[k].split_n == 0, "conv group: a two-output convolution is a launch of its own");
   if (cfg == kCfgPatch64) {
@@ -598,6 +624,7 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
     const int esz = (int)dtype_size(c.dtype), chunk = conv_k_chunk(c.dtype);
     const int mcfg = group_member_cfg(cfg, c), BM = igemm_bm(mcfg), BN = igemm_bn(mcfg);
     if (mcfg == kCfgIgemm128x64) g.narrow |= 1u << k;
+    // (a four-wave 256 x 256 group: bit k = member k on the 256 x 224 tile, set below once its split factor is known)
     RON_REQUIRE(c.dtype == ls[0].dtype, "conv group: mixed dtypes");
     RON_REQUIRE(c.in.C % chunk == 0 && c.in.pad >= c.cpad, "conv group: bad input (Cin %d, halo %d < %d)", c.in.C, c.in.pad, c.cpad);
     RON_REQUIRE(c.in.bytes > 0 && c.in.bytes < (int64_t)1 << 32 && c.wgt_bytes > 0 && c.wgt_bytes < (int64_t)1 << 32,
@@ -623,6 +650,7 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
       if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
       else { used += need; any_split = true; }
     }
+    if (group_4w && conv_takes_224(c, a.kt_split)) g.narrow |= 1u << k;
     const int tile_order = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, group_4w ? a.kt_split : 0);
     RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "conv group: tile order %d: 0 .. %d", tile_order, kConvMaxTileOrder);
     a.m_fastest = tile_order;
@@ -634,6 +662,9 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
                     (mcfg == kCfgIgemm128 || (mcfg == kCfgIgemm256 && n_long <= kTapsInnerMaxN))) ? 1 : 0;
     if (c.center_from > 0) RON_REQUIRE(c.center_from % BN == 0 && (c.kh & 1) && (c.kw & 1), "conv group: bad centre-tap-only columns");
   }
+  if (n_tiles != nullptr)
+    for (int k = 0; k < n; ++k)
+      n_tiles[order[k]] = (group_4w && ((g.narrow >> k) & 1u)) ? 224 : igemm_bn(group_member_cfg(cfg, ls[k]));
   // entries, longest K chain first (see ConvGroupArgs)
   struct Ent { int op, bid0, cnt, chain; };
   Ent ents[kMaxEntries];

@@ -71,11 +71,16 @@ struct PatchArgs {
 // together, 3 x KS k-steps of MFMAs between two barriers.  For N <= 64 a tap is only MR * NR * KS = 16 MFMAs per wave, too few to
 // hide a step's fixed cost (counted wait + barrier, LDS-DMA issue, first-fragment latency: ~1500 cycles per step whatever is in
 // flight, profiles/r03/skinny_heads_pair.txt); three taps per barrier triple the work behind it.
-template <class Tr, int BN, int WN, int SB, int TPS = 1>
+// BNC <= BN: the columns the waves MULTIPLY (a multiple of 16 per wave across).  The weights are staged BN rows per tap as ever (a
+// piece is 64 rows); with BNC < BN only the first BNC LDS rows are read: a convolution of 20 output channels padded to 64 runs one
+// column block per wave (BNC = 32, WN = 2) instead of two, one of 40 three blocks per wave on an 8 x 1 wave layout (BNC = 48, WN = 1)
+// instead of 2 x 2 on 4 x 2 - in both every wave of the workgroup issues the same number of MFMAs.
+template <class Tr, int BN, int WN, int SB, int TPS = 1, int BNC = BN>
 __device__ __forceinline__ void conv3x3_patch_tile(const PatchArgs& pa, const ConvArgs& p, const unsigned bid, const unsigned nwg) {
   constexpr int BM = 256, WM = 8 / WN, kThreads = 512;
   constexpr int MT = Tr::kMT, kGroups = 64 / MT, KS = 8 / kGroups, EPA = MT * MT / 64;
-  constexpr int TM = BM / WM, TN = BN / WN;
+  constexpr int TM = BM / WM, TN = BNC / WN;
+  static_assert(BNC <= BN && BNC % (WN * MT) == 0 && (BNC == BN || BN == 64), "computed columns: whole blocks per wave, one N tile");
   constexpr int MR = TM / MT, NR = TN / MT;
   constexpr int B_IT = BN / 64;                   // B pieces per thread and step
   constexpr int G = B_IT + 1;                     // LDS-DMA instructions per thread and step (the weights + one patch piece)
@@ -171,7 +176,8 @@ __device__ __forceinline__ void conv3x3_patch_tile(const PatchArgs& pa, const Co
   for (int it = 0; it < B_IT; ++it) {
     const int lrow = it * 64 + (tid >> 3);
     const int grp = lrow / TN, loc = lrow % TN;
-    const int nrow = n0 + grp * TN + (loc % MT) * NR + (loc / MT);
+    // (rows from BNC on are staged where they are and never read)
+    const int nrow = lrow < BNC ? n0 + grp * TN + (loc % MT) * NR + (loc / MT) : n0 + lrow;
     b_voff[it] = (int)((unsigned)(nrow >> 6) * (unsigned)p.KT * (unsigned)kWeightBlockBytes + (unsigned)(nrow & 63) * kRowBytes) +
                  (((tid & 7) ^ ((tid >> 4) & 7)) << 4);
   }
@@ -413,19 +419,20 @@ __global__ __launch_bounds__(512, 2) void conv3x3_patch_kernel(PatchArgs pa) {
 // Two convolutions over the SAME input tensor geometry (channel slices of one map: the Cout = 20 / 40 heads of a scale read
 // slices of the per-scale concatenated tensor, nets/ron_vgg_320.py:406-415,427-428) in ONE launch: workgroups [0, first) run
 // `pa.c`, the rest `second`, each exactly as its own launch would.  Alone each fills 200 of the 512 workgroup slots.
-template <class Tr, int BN, int WN, int SB, int TPS>
+// CA / WNA, CB / WNB: computed columns and waves across of the first / second member (conv3x3_patch_tile, BNC)
+template <class Tr, int BN, int WN, int SB, int TPS, int CA = BN, int WNA = WN, int CB = BN, int WNB = WN>
 __global__ __launch_bounds__(512, 2) void conv3x3_patch_pair_kernel(PatchArgs pa, ConvArgs second, int first) {
   const int b = (int)blockIdx.x;
-  if (b < first) conv3x3_patch_tile<Tr, BN, WN, SB, TPS>(pa, pa.c, (unsigned)b, (unsigned)first);
-  else conv3x3_patch_tile<Tr, BN, WN, SB, TPS>(pa, second, (unsigned)(b - first), gridDim.x - (unsigned)first);
+  if (b < first) conv3x3_patch_tile<Tr, BN, WNA, SB, TPS, CA>(pa, pa.c, (unsigned)b, (unsigned)first);
+  else conv3x3_patch_tile<Tr, BN, WNB, SB, TPS, CB>(pa, second, (unsigned)(b - first), gridDim.x - (unsigned)first);
 }
 
-template <class Tr, int BN, int WN, int SB, int TPS>
+template <class Tr, int BN, int WN, int SB, int TPS, int CA = BN, int WNA = WN, int CB = BN, int WNB = WN>
 int launch_patch_pair_t(const PatchArgs& a, const ConvArgs& second, int first, int grid, hipStream_t s) {
   const size_t lds = 2 * (size_t)kPatchRows * kRowBytes + SB * TPS * (size_t)BN * kRowBytes + 2 * 256 * sizeof(int) + 1024;
   static PerDeviceOnce once;
-  RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_patch_pair_kernel<Tr, BN, WN, SB, TPS>), (int)lds));
-  RON_LAUNCH((conv3x3_patch_pair_kernel<Tr, BN, WN, SB, TPS>), dim3(grid), dim3(512), lds, s, a, second, first);
+  RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&conv3x3_patch_pair_kernel<Tr, BN, WN, SB, TPS, CA, WNA, CB, WNB>), (int)lds));
+  RON_LAUNCH((conv3x3_patch_pair_kernel<Tr, BN, WN, SB, TPS, CA, WNA, CB, WNB>), dim3(grid), dim3(512), lds, s, a, second, first);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
 }
@@ -524,23 +531,50 @@ static int patch_args(const ConvLaunch& c, int cfg, PatchArgs* out, int* grid) {
 
 // Can `a` and `b` share a launch of the patch kernel (conv3x3_patch_pair_kernel)?  Same input tensor and geometry (channel
 // slices may differ), same dtype and N tile, no fused pool, and each big enough for the patch kernel to be the choice at all.
-bool conv_patch_pair_applicable(const ConvLaunch& a, const ConvLaunch& b) {
+static bool patch_pair_same_tensor(const ConvLaunch& a, const ConvLaunch& b) {
   if (!conv_patch_applicable(a) || !conv_patch_applicable(b) || a.pool || b.pool) return false;
-  if (a.dtype != b.dtype || a.in.base != b.in.base || a.in.bytes != b.in.bytes || a.in.N != b.in.N || a.in.H != b.in.H || a.in.W != b.in.W ||
-      a.in.pad != b.in.pad || a.in.cstride != b.in.cstride || a.in.C != b.in.C)
-    return false;
+  return !(a.dtype != b.dtype || a.in.base != b.in.base || a.in.bytes != b.in.bytes || a.in.N != b.in.N || a.in.H != b.in.H || a.in.W != b.in.W ||
+           a.in.pad != b.in.pad || a.in.cstride != b.in.cstride || a.in.C != b.in.C);
+}
+bool conv_patch_pair_applicable(const ConvLaunch& a, const ConvLaunch& b) {
+  if (!patch_pair_same_tensor(a, b)) return false;
   const int ca = conv_patch_pick(a), cb = conv_patch_pick(b);
   return ca >= 0 && ca == cb;
 }
 
-int launch_conv_patch_pair(const ConvLaunch& ca, const ConvLaunch& cb, hipStream_t stream) {
-  RON_REQUIRE(conv_patch_pair_applicable(ca, cb), "patch kernel pair: the two convolutions cannot share a launch");
-  const int cfg = conv_patch_pick(ca);
+// Columns the pair's members multiply on the 64-column N tile (bf16 / f16): 32 + 48 for up to 32 and up to 48 output channels (the
+// block4 score pair: 20 and 40), in either order; else (and with ConvLaunch::n224 = 0, the side-by-side switch) 64 + 64.
+static int patch_pair_widths(const ConvLaunch& a, const ConvLaunch& b, int cfg) {
+  if (cfg != kCfgPatch64 || !dtype_is_half(a.dtype) || a.n224 == 0 || b.n224 == 0 || a.Npad != 64 || b.Npad != 64) return 0;
+  if (a.Cout <= 32 && b.Cout <= 48) return 1;
+  if (a.Cout <= 48 && b.Cout <= 32) return 2;
+  return 0;
+}
+
+int conv_patch_pair_columns(const ConvLaunch& a, const ConvLaunch& b, int out[2]) {
+  const int w = patch_pair_widths(a, b, kCfgPatch64);
+  out[0] = w == 1 ? 32 : (w == 2 ? 48 : 64);
+  out[1] = w == 1 ? 48 : (w == 2 ? 32 : 64);
+  return RON_OK;
+}
+
+int launch_conv_patch_pair(const ConvLaunch& ca, const ConvLaunch& cb, hipStream_t stream, int force_cfg) {
+  if (force_cfg >= 0) RON_REQUIRE(patch_pair_same_tensor(ca, cb) && conv_cfg_is_patch(force_cfg), "patch kernel pair: the two convolutions cannot share a launch");
+  else RON_REQUIRE(conv_patch_pair_applicable(ca, cb), "patch kernel pair: the two convolutions cannot share a launch");
+  const int cfg = force_cfg >= 0 ? force_cfg : conv_patch_pick(ca);
   PatchArgs a, b;
   int grid_a = 0, grid_b = 0, rc;
   if ((rc = patch_args(ca, cfg, &a, &grid_a)) || (rc = patch_args(cb, cfg, &b, &grid_b))) return rc;
   const int grid = grid_a + grid_b;
   const int BN = patch_bn(cfg);
+  const int widths = patch_pair_widths(ca, cb, cfg);
+  if (widths != 0) {
+    const bool bf = ca.dtype == RON_DTYPE_BF16;
+    if (widths == 1) return bf ? launch_patch_pair_t<TraitsBF16S, 64, 2, 2, 3, 32, 2, 48, 1>(a, b.c, grid_a, grid, stream)
+                               : launch_patch_pair_t<TraitsF16S, 64, 2, 2, 3, 32, 2, 48, 1>(a, b.c, grid_a, grid, stream);
+    return bf ? launch_patch_pair_t<TraitsBF16S, 64, 2, 2, 3, 48, 1, 32, 2>(a, b.c, grid_a, grid, stream)
+              : launch_patch_pair_t<TraitsF16S, 64, 2, 2, 3, 48, 1, 32, 2>(a, b.c, grid_a, grid, stream);
+  }
 #define RON_PATCH_PAIR(Tr)                                                                          \
   do {                                                                                              \
     if (BN == 256) return launch_patch_pair_t<Tr, 256, 2, 2, 1>(a, b.c, grid_a, grid, stream);      \

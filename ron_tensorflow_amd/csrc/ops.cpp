@@ -125,6 +125,9 @@ int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool w
     c.res = S->d_res.p;
   }
   c.splitk = d->splitk;
+  // tests / sweeps: RON_IGEMM224=0 keeps 193 .. 224 output channels on 256-column tiles (ConvLaunch::n224), read per call so that
+  // one process can run both forms; the graph does not read it
+  if (const char* e = getenv("RON_IGEMM224")) { if (atoi(e) == 0) c.n224 = 0; }
   c.center_from = d->transpose ? 0 : d->center_from;
   const int64_t sb = conv_scratch_bytes(c);
   if (sb > 0) {
@@ -213,9 +216,8 @@ extern "C" int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, con
 }
 
 // How ron_conv2d_nhwc would launch `d` (no launch): the decisions of launch_conv for the same ConvLaunch.
-extern "C" int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]) {
+static int plan_of_desc(const ron_conv_desc* d, int o[4], int* n_tile) {
   using namespace ron;
-  RON_REQUIRE(d != nullptr && out != nullptr, "NULL argument");
   RON_REQUIRE(!(d->cin == 3), "the 3-channel stem has a kernel of its own");
   if (int rc0 = check_conv_desc(d)) return rc0;       // (before the weights are sized from it)
   const size_t wn = (size_t)d->kh * d->kw * d->cin * d->cout;
@@ -223,10 +225,127 @@ extern "C" int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]) {
   ConvSetup S;
   int rc;
   if ((rc = setup_conv(d, w.data(), nullptr, false, &S))) return rc;
+  return conv_describe(S.c, o, n_tile);
+}
+
+extern "C" int ron_conv_plan(const ron_conv_desc* d, int32_t out[4]) {
+  RON_REQUIRE(d != nullptr && out != nullptr, "NULL argument");
   int o[4];
-  if ((rc = conv_describe(S.c, o))) return rc;
+  if (int rc = plan_of_desc(d, o, nullptr)) return rc;
   for (int i = 0; i < 4; ++i) out[i] = o[i];
   return RON_OK;
+}
+
+// ... and the width of the row-gather kernel's column tile for the same launch (conv_describe)
+extern "C" int ron_conv_plan_n_tile(const ron_conv_desc* d, int32_t* n_tile) {
+  RON_REQUIRE(d != nullptr && n_tile != nullptr, "NULL argument");
+  int o[4], bn = 0;
+  if (int rc = plan_of_desc(d, o, &bn)) return rc;
+  *n_tile = bn;
+  return RON_OK;
+}
+
+// One or two head convolutions with the fp32 output the graph's head layers have (ConvLaunch::out_f32: the kernel's epilogue writes
+// the dense fp32 tensor itself), each over its own input: as launches of their own, or as the two members of one grouped launch of
+// 256 x 256 tiles (launch_conv_group, kCfgIgemm256: what the batch plan does with the class heads of the coarse scales).
+extern "C" int ron_conv2d_f32out_nhwc(const ron_conv_desc* da, const float* xa, const float* wa, const float* ba, float* ya,
+                                      const ron_conv_desc* db, const float* xb, const float* wb, const float* bb, float* yb,
+                                      int grouped, int32_t* n_tiles, void* stream) {
+  using namespace ron;
+  RON_REQUIRE(da && xa && wa && ya, "NULL argument");
+  RON_REQUIRE(db == nullptr || (xb && wb && yb), "NULL argument (second convolution)");
+  RON_REQUIRE(!grouped || db != nullptr, "a grouped launch takes two convolutions");
+  hipStream_t s = (hipStream_t)stream;
+  const ron_conv_desc* ds[2] = {da, db};
+  const float* xs[2] = {xa, xb};
+  const float* ws[2] = {wa, wb};
+  const float* bs[2] = {ba, bb};
+  float* ys[2] = {ya, yb};
+  const int n = db != nullptr ? 2 : 1;
+  ConvSetup S[2];
+  ConvLaunch L[2];
+  int rc;
+  for (int k = 0; k < n; ++k) {
+    const ron_conv_desc* d = ds[k];
+    if (int rc0 = check_conv_desc(d)) return rc0;
+    RON_REQUIRE(!d->transpose && !d->pool && d->center_from == 0 && d->stride == 1 && d->cin % conv_k_chunk(d->dtype) == 0,
+                "fp32-output convolution: a plain stride-1 convolution");
+    // the grouped launch has one tile configuration, the 256 x 256 one: a descriptor that asks for another is refused, not ignored
+    RON_REQUIRE(!grouped || d->tile_cfg < 0 || d->tile_cfg == kCfgIgemm256, "grouped fp32-output convolutions: tile_cfg %d (-1 or %d)", d->tile_cfg, kCfgIgemm256);
+    if ((rc = setup_conv(d, ws[k], bs[k], false, &S[k]))) return rc;
+    RON_REQUIRE(!grouped || S[k].c.Npad % 256 == 0, "grouped fp32-output convolutions: cout %d pads to %d, not a multiple of 256", d->cout, S[k].c.Npad);
+    ConvLaunch& c = S[k].c;
+    TensorView v;
+    v.base = ys[k]; v.N = d->n; v.H = S[k].ho; v.W = S[k].wo; v.pad = 0; v.coff = 0; v.C = d->cout; v.cstride = d->cout;
+    v.bytes = (int64_t)d->n * S[k].ho * S[k].wo * d->cout * 4;
+    c.out = v;
+    c.out_f32 = 1;
+    if ((rc = launch_pack_input(xs[k], c.in, d->dtype, s))) return rc;
+    L[k] = c;
+  }
+  // (after the first launch an error return waits for the stream first: the operands are freed on the way out)
+  DevBuf scratch;
+  int widths[2] = {0, 0};
+  if (!grouped) {
+    for (int k = 0; k < n; ++k) {
+      int o[4];
+      if ((rc = conv_describe(L[k], o, &widths[k])) || (rc = launch_conv(L[k], s))) { (void)hipStreamSynchronize(s); return rc; }
+    }
+  } else {
+    // split factors: the descriptors' where both give one (>= 1), else the group's own plan
+    int sk[2] = {da->splitk, db->splitk};
+    const int* plan = (sk[0] >= 1 && sk[1] >= 1) ? sk : nullptr;
+    for (int k = 0; k < 2; ++k) { L[k].scratch = nullptr; L[k].scratch_bytes = 0; L[k].splitk = plan ? sk[k] : -1; }
+    const int64_t sb = conv_group_scratch_bytes(L, 2, kCfgIgemm256, plan);
+    if (sb > 0 && (rc = alloc(&scratch, sb, false))) { (void)hipStreamSynchronize(s); return rc; }
+    if ((rc = launch_conv_group(L, 2, kCfgIgemm256, scratch.p, sb, s, plan, widths))) { (void)hipStreamSynchronize(s); return rc; }
+  }
+  RON_HIP_CHECK(hipStreamSynchronize(s));
+  if (n_tiles != nullptr) for (int k = 0; k < n; ++k) n_tiles[k] = widths[k];
+  return RON_OK;
+}
+
+// The skinny heads of a scale as the graph launches them at large batches: two 3x3 convolutions of at most 64 output channels over
+// channel slices of ONE tensor, one launch of the halo-patch pair kernel (64-column configuration, whatever the grid size), fp32 outputs.
+extern "C" int ron_conv2d_patch_pair_nhwc(const ron_conv_desc* da, const ron_conv_desc* db, const float* x, const float* wa, const float* ba,
+                                          const float* wb, const float* bb, float* ya, float* yb, int full_width, int32_t* columns,
+                                          void* stream) {
+  using namespace ron;
+  RON_REQUIRE(da && db && x && wa && wb && ya && yb, "NULL argument");
+  if (int rc0 = check_conv_desc(da)) return rc0;
+  if (int rc0 = check_conv_desc(db)) return rc0;
+  RON_REQUIRE(da->n == db->n && da->h == db->h && da->w == db->w && da->cin == db->cin && da->dtype == db->dtype &&
+              da->in_cstride > 0 && da->in_cstride == db->in_cstride, "patch pair: the two convolutions read slices of one tensor");
+  hipStream_t s = (hipStream_t)stream;
+  const ron_conv_desc* ds[2] = {da, db};
+  const float* ws[2] = {wa, wb};
+  const float* bs[2] = {ba, bb};
+  float* ys[2] = {ya, yb};
+  ConvSetup S[2];
+  int rc;
+  for (int k = 0; k < 2; ++k) {
+    const ron_conv_desc* d = ds[k];
+    RON_REQUIRE(!d->transpose && !d->pool && d->center_from == 0 && d->stride == 1 && d->dilation == 1 && d->kh == 3 && d->kw == 3 &&
+                d->cout <= 64 && d->cin % conv_k_chunk(d->dtype) == 0, "patch pair: plain 3x3 convolutions of at most 64 output channels");
+    if ((rc = setup_conv(d, ws[k], bs[k], false, &S[k]))) return rc;
+    ConvLaunch& c = S[k].c;
+    TensorView v;
+    v.base = ys[k]; v.N = d->n; v.H = S[k].ho; v.W = S[k].wo; v.pad = 0; v.coff = 0; v.C = d->cout; v.cstride = d->cout;
+    v.bytes = (int64_t)d->n * S[k].ho * S[k].wo * d->cout * 4;
+    c.out = v;
+    c.out_f32 = 1;
+    if (full_width) c.n224 = 0;
+  }
+  S[1].c.in.base = S[0].c.in.base;              // one tensor: the second convolution's own allocation stays unused
+  TensorView wide = S[0].c.in;
+  wide.C = da->in_cstride; wide.coff = 0;
+  if ((rc = launch_pack_input(x, wide, da->dtype, s))) return rc;
+  int cols[2];
+  conv_patch_pair_columns(S[0].c, S[1].c, cols);
+  if (columns != nullptr) { columns[0] = cols[0]; columns[1] = cols[1]; }
+  rc = launch_conv_patch_pair(S[0].c, S[1].c, s, kCfgPatch64);
+  RON_HIP_CHECK(hipStreamSynchronize(s));
+  return rc;
 }
 
 // Two fp32 head tensors from ONE convolution over a shared input (ConvLaunch::split_n; the graph's pack_box_pair for the class and box

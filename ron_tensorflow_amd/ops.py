@@ -477,6 +477,53 @@ def conv_plan(n, h, w, cin, cout, k=3, stride=1, dilation=1, dtype='bf16', tile_
     return dict(tile_cfg=out[0], splitk=out[1], tile_order=out[2], taps_inner=out[3])
 
 
+def conv_plan_n_tile(n, h, w, cin, cout, k=3, dtype='bf16', tile_cfg=-1, splitk=-1):
+    """Columns of the tile conv2d_nhwc would run this convolution on (ron_conv_plan_n_tile): 64 / 128 / 256, 224 for the 256 x 224 form
+    of the four-wave tile, 0 for the kernels that are not the row-gather kernel."""
+    d = _lib.ConvDesc(n, h, w, cin, cout, k, k, 1, 1, 1, 0, _lib.DTYPES[dtype], tile_cfg, 0, 0, 0, splitk, 0)
+    out = C.c_int32(0)
+    check(lib().ron_conv_plan_n_tile(C.byref(d), C.byref(out)))
+    return out.value
+
+
+def conv2d_f32out_nhwc(convs, grouped=False, dtype='bf16', with_tiles=False):
+    """One or two head convolutions with fp32 outputs written by the kernel (ron_conv2d_f32out_nhwc).  convs: a list of one or two
+    dict(x=GPU fp32 [N,H,W,Cin], w=HWIO numpy, bias=numpy or None, tile_cfg=-1, splitk=-1); grouped: both as one grouped launch of
+    256 x 256 tiles.  Returns the list of outputs [N,H,W,Cout] fp32; with_tiles: (outputs, [column-tile width each ran on])."""
+    args, keep, ys = [], [], []
+    for cv in convs:
+        x = cv['x'].contiguous()
+        w = np.ascontiguousarray(cv['w'], dtype=np.float32)
+        n, h, wd, cin = x.shape
+        kh, kw, _, cout = w.shape
+        d = _lib.ConvDesc(n, h, wd, cin, cout, kh, kw, 1, 1, 0, 0, _lib.DTYPES[dtype], cv.get('tile_cfg', -1), 0, 0, 0, cv.get('splitk', -1), 0)
+        b = None if cv.get('bias') is None else np.ascontiguousarray(cv['bias'], dtype=np.float32)
+        y = torch.empty((n, h, wd, cout), dtype=torch.float32, device=x.device)
+        keep += [x, w, b, d]
+        ys.append(y)
+        args += [C.byref(d), ptr(x), ptr(w), ptr(b), ptr(y)]
+    if len(convs) == 1:
+        args += [None, None, None, None, None]
+    tiles = (C.c_int32 * 2)()
+    check(lib().ron_conv2d_f32out_nhwc(*args, int(grouped), tiles, current_stream()))
+    return (ys, [tiles[k] for k in range(len(convs))]) if with_tiles else ys
+
+
+def conv2d_patch_pair_nhwc(x, cin, wa, ba, coff_a, wb, bb, coff_b, dtype='bf16', full_width=False):
+    """Two 3x3 head convolutions over the channel slices [coff, coff + cin) of one tensor x (GPU fp32 [N,H,W,C]) as one launch of the
+    halo-patch pair kernel (ron_conv2d_patch_pair_nhwc) -> (ya, yb, [columns each member multiplied])."""
+    x = x.contiguous()
+    n, h, wd, cs = x.shape
+    ws = [np.ascontiguousarray(w, dtype=np.float32) for w in (wa, wb)]
+    bs = [None if b is None else np.ascontiguousarray(b, dtype=np.float32) for b in (ba, bb)]
+    ds = [_lib.ConvDesc(n, h, wd, cin, w.shape[3], 3, 3, 1, 1, 0, 0, _lib.DTYPES[dtype], -1, cs, coff, 0, 1, 0) for w, coff in zip(ws, (coff_a, coff_b))]
+    ys = [torch.empty((n, h, wd, w.shape[3]), dtype=torch.float32, device=x.device) for w in ws]
+    cols = (C.c_int32 * 2)()
+    check(lib().ron_conv2d_patch_pair_nhwc(C.byref(ds[0]), C.byref(ds[1]), ptr(x), ptr(ws[0]), ptr(bs[0]), ptr(ws[1]), ptr(bs[1]),
+                                           ptr(ys[0]), ptr(ys[1]), int(full_width), cols, current_stream()))
+    return ys[0], ys[1], [cols[0], cols[1]]
+
+
 def conv2d_heads_nhwc(x, w, split_first, bias=None, dilation=1, relu=False, dtype='bf16', tile_cfg=-1, splitk=-1):
     """One convolution, two fp32 head tensors (ron_conv2d_heads_nhwc: what the SSD-512 graph does with the class and box convolutions of
     a feature layer, nets/ssd_vgg_300.py:403-431): w HWIO with cout = both heads' channels, the first `split_first` of them -> y_first."""

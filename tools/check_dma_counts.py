@@ -107,20 +107,51 @@ def check_patch(name, lines):
     return problems
 
 
+def asm4w_pieces(name):
+    """LDS-DMA pieces per wave and K step of every assembly K loop the kernel holds: 8 of A + BN / 32 of B (256 x 256: 16, 256 x 224:
+    15, 256 x 128: 12).  The grouped kernel of the 256 x 256 tile exists a second time with the 256 x 224 loop beside its own (bf16 / f16,
+    template argument N224 = true: ConvGroupArgs::narrow)."""
+    own = 8 + template_ints(name)[1] // 32
+    if 'group_kernel' in name and 'ELb1E' in name:          # <..., N224 = true>: launches with a member on 256 x 224 tiles
+        return [own, 8 + 224 // 32]
+    return [own]
+
+
 def check_asm4w(name, lines):
-    """The four-wave assembly K loop (kloop4w.inc, tools/gen_kloop4w.py): two whole tiles (2 x 16 pieces; 256 x 128: 2 x 12) in the
-    prologue and `vmcnt(pieces)` before the first fragment reads; 16 (12) pieces per K step; the loop's one `vmcnt(N)` has exactly N of them in front of
-    it in the loop body (the previous step's tile has then landed), the rest behind."""
-    pieces = 8 + template_ints(name)[1] // 32          # per wave and K step: 8 of A + BN / 32 of B (256 x 256: 16, 256 x 128: 12)
-    top = [i for i, l in enumerate(lines) if re.match(r'^\.Lk4w_loop_\d+:', l)]
-    if len(top) != 1:
-        return ['%d assembly K loops found, expected 1' % len(top)]
-    top = top[0]
-    start = max(i for i in range(top) if '#ASMSTART' in lines[i])
-    end = [i for i in range(top, len(lines)) if re.search(r's_cbranch_scc0 \.Lk4w_loop_\d+', lines[i])]
-    if len(end) != 1:
-        return ['loop end not found']
-    end = end[0]
+    """The four-wave assembly K loop (kloop4w.inc, tools/gen_kloop4w.py): two whole tiles (2 x 16 pieces; 256 x 224: 2 x 15; 256 x 128:
+    2 x 12) in the prologue and `vmcnt(pieces)` before the first fragment reads; 16 (15, 12) pieces per K step; the loop's one `vmcnt(N)`
+    has exactly N of them in front of it in the loop body (the previous step's tile has then landed), the rest behind.  A kernel that
+    holds two loops (asm4w_pieces) is checked loop by loop, each against the width its own piece count says it is."""
+    want = asm4w_pieces(name)
+    tops = [i for i, l in enumerate(lines) if re.match(r'^\.Lk4w_loop_\d+:', l)]
+    if len(tops) != len(want):
+        return ['%d assembly K loops found, expected %d' % (len(tops), len(want))]
+    problems, seen, accounted, first_end = [], [], 0, None
+    for top in tops:
+        start = max(i for i in range(top) if '#ASMSTART' in lines[i])
+        end = [i for i in range(top, len(lines)) if re.search(r's_cbranch_scc0 \.Lk4w_loop_\d+', lines[i])]
+        if not end:
+            return ['loop end not found']
+        end = end[0]
+        if first_end is None:
+            first_end = end
+        n_step = sum(1 for l in lines[top:end] if DMA.search(l))
+        pieces = n_step if n_step in want else want[0]       # which width this loop is: read off its own count
+        seen.append(pieces)
+        sub = check_asm4w_loop(lines, start, top, end, pieces)
+        problems += sub[0]
+        accounted += sub[1]
+    if sorted(seen) != sorted(want):
+        problems.append('K loops with %s LDS-DMA pieces per step, expected %s' % (sorted(seen), sorted(want)))
+    total = sum(1 for l in lines if DMA.search(l))
+    if total != accounted:
+        problems.append('%d LDS-DMA instructions outside the assembly loops' % (total - accounted))
+    return problems + check_asm4w_tail(lines, first_end)
+
+
+def check_asm4w_loop(lines, start, top, end, pieces):
+    """One assembly K loop: lines[start] opens its asm statement, lines[top] is the loop label, lines[end] the branch back.
+    ([problems], LDS-DMA instructions of the statement's prologue and loop)"""
     problems = []
     pro = sum(1 for l in lines[start:top] if DMA.search(l))
     if pro != 2 * pieces:
@@ -140,11 +171,14 @@ def check_asm4w(name, lines):
             problems.append('vmcnt(%d) with %d LDS-DMA instructions of the step in front of it' % (waits[0][1], before))
     if sum(1 for l in body if 's_barrier' in l) != 3:
         problems.append('%d barriers per K step, expected 3' % sum(1 for l in body if 's_barrier' in l))
-    total = sum(1 for l in lines if DMA.search(l))
-    if total != pro + n_dma:
-        problems.append('%d LDS-DMA instructions outside the assembly loop' % (total - pro - n_dma))
-    # The loop leaves its sums in a[0:255] and declares them clobbered; the epilogue reads them in asm statements of its own.  Between
-    # the loop and the end of the kernel the COMPILER's code must not touch an accumulation register (it would only as spill space).
+    return problems, pro + n_dma
+
+
+def check_asm4w_tail(lines, end):
+    """The loop leaves its sums in a[0:255] and declares them clobbered; the epilogue reads them in asm statements of its own.  Between
+    the (first) loop and the end of the kernel the COMPILER's code must not touch an accumulation register (it would only as spill
+    space).  lines[end]: the first loop's branch back."""
+    problems = []
     loop_end = next(i for i in range(end, len(lines)) if '#ASMEND' in lines[i])
     inside, touched, reads = False, [], 0
     for l in lines[loop_end + 1:]:
@@ -164,7 +198,7 @@ def check_asm4w(name, lines):
 
 
 def is_asm4w(name):
-    return template_ints(name)[:5] in ([256, 256, 2, 2, 2], [256, 128, 2, 2, 2]) and ('TraitsBF16S' in name or 'TraitsF16S' in name or 'TraitsF16X3S' in name) and 'mixed' not in name
+    return template_ints(name)[:5] in ([256, 256, 2, 2, 2], [256, 224, 2, 2, 2], [256, 128, 2, 2, 2]) and ('TraitsBF16S' in name or 'TraitsF16S' in name or 'TraitsF16X3S' in name) and 'mixed' not in name
 
 
 def check_igemm(name, lines):
@@ -205,7 +239,7 @@ def check_igemm(name, lines):
 def describe(name):
     tr = re.search(r'Traits(\w+?)SE', name).group(1)
     kind = re.search(r'\d+(conv\w+?kernel)I', name).group(1)
-    extra = ', TI' if 'ELb1E' in name else ''
+    extra = (', +224' if 'group_kernel' in name else ', TI') if 'ELb1E' in name else ''
     return '%-5s %-26s <%s%s>' % (tr, kind, ', '.join(str(i) for i in template_ints(name)), extra)
 
 
@@ -225,8 +259,10 @@ def check_file(source, asm_path=None):
 
 
 # instantiations the Makefile's build holds (dtypes x tile forms); a different count means the check no longer sees all of them
-# (+ the four-wave assembly forms: the 256 x 256 tile and its grouped kernel, the 256 x 128 tile: bf16, f16, f16x3)
-EXPECTED = {'conv_patch.hip': 4 * (3 + 3), 'conv_mfma.hip': 4 * (4 + 3 + 1), 'conv_mfma4w.hip': 3 * 2 + 3}
+# (conv_patch.hip: + the skinny pair at 32 + 48 / 48 + 32 computed columns, bf16 and f16)
+# (+ the four-wave assembly forms: the 256 x 256 tile and its grouped kernel, the 256 x 128 tile: bf16, f16, f16x3; the 256 x 224
+# tile and the grouped kernel that holds its loop too: bf16, f16)
+EXPECTED = {'conv_patch.hip': 4 * (3 + 3) + 2 * 2, 'conv_mfma.hip': 4 * (4 + 3 + 1), 'conv_mfma4w.hip': 3 * 2 + 3 + 2 + 2}
 
 
 def main():

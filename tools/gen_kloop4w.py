@@ -23,7 +23,8 @@ Interface (physical registers; conv_mfma.hip, conv_igemm_tile, binds them):
        first A fragment is read from in stage 0 for k-half 0 / 1, v118 / v119 the same for B, v120 LDS byte address of the step
        table: entry q = {soffset of the A pieces, soffset of the B pieces} of K step q, steps + 2 entries
   out: a[0:255] accumulators (declared as clobbers: see main()), block (i, j) of the wave's 8 x 8 grid of 16 x 16 tiles in
-       a[4 * (8 * i + j) : +3] (256 x 128 tile: a[4 * (4 * i + j) : +3])
+       a[4 * (8 * i + j) : +3] (256 x 128 tile: a[4 * (4 * i + j) : +3]; 256 x 224: 8 x 7 blocks, a[4 * (7 * i + j) : +3], a[0:223];
+       its B side has seven pieces and seven fragments per k-half: v[108:114], v[160:187] / v[224:251])
   clobbers: s[48:64], v[84:99], v[121:255], scc, M0
 """
 import os
@@ -40,8 +41,8 @@ def vr(first, n=4):
 
 
 def schedule(NB, split):
-    """Where (after which MFMA of the step) every event of a K step goes.  NB = 16-column tiles per wave: 8 (256 x 256 tile) or 4
-    (256 x 128).  MFMA m of a phase is (row tile i, column tile j) = divmod(m % (8 * NB), NB)."""
+    """Where (after which MFMA of the step) every event of a K step goes.  NB = 16-column tiles per wave: 8 (256 x 256 tile), 7
+    (256 x 224) or 4 (256 x 128).  MFMA m of a phase is (row tile i, column tile j) = divmod(m % (8 * NB), NB)."""
     if NB == 8 and not split:
         d = dict(NM=128, b1_rd=[0, 2, 4, 6, 8, 10, 12, 14], valid=(5, 7), tab_wait=(10, 5), m0b=19, w1=20,
                  bdma=[22, 25, 28, 31, 34, 52, 55, 58], a1_rd=[24, 27, 30, 33, 36, 38, 40, 42], w2=50,
@@ -64,6 +65,15 @@ def schedule(NB, split):
                     adma=[61, 64, 67, 70, 73, 76, 79, 82], xor=120, vm=123, b0_rd=[128, 130, 132, 134, 136, 138, 140, 142],
                     a0_rd=[137, 145, 153, 161, 169, 177, 185],
                     end_wait='s_waitcnt lgkmcnt(1)')       # everything but the newest read (hi(A) of row tile 6, needed at MFMA 48)
+    if NB == 7:
+        # 256 x 224 (class-prediction heads, Cout = 210): every wave 8 x 7 blocks, 112 MFMAs per step for 30 fragment reads and 15 DMA
+        # pieces.  The events of the 256 x 256 step in the same order at 7/8 of their MFMA index (rounded so that no LDS-DMA piece
+        # follows an M0 write directly); the vmcnt immediate follows from the pieces in front of it: 7 of B + 5 of A = 12
+        assert not split, 'the split-precision loop reuses dying fragment registers: no 224-column form'
+        return dict(NM=112, b1_rd=[0, 2, 4, 6, 8, 10, 12], valid=(5, 7), tab_wait=(10, 5), m0b=17, w1=18,
+                    bdma=[20, 22, 25, 27, 30, 46, 49], a1_rd=[21, 23, 26, 29, 31, 33, 35, 37], w2=44,
+                    adma=[53, 56, 74, 76, 78, 84, 88, 108], xor=72, vm=80, b0_rd=[82, 83, 84, 85, 86, 89, 90],
+                    a0_rd=[92, 93, 95, 98, 100, 102, 105, 107], end_wait='s_waitcnt lgkmcnt(0)')
     if NB == 4 and not split:
         # 64 MFMAs per step carry the same 24 fragment reads and 12 DMA pieces
         return dict(NM=64, b1_rd=[0, 2, 4, 6], valid=(3, 5), tab_wait=(7, 3), m0b=8, w1=9,
@@ -81,9 +91,9 @@ def gen(mfma, split=False, NB=8):
     NM = sc['NM']
     STAGE_B = NB * 2 * 16 * 128                   # the B stage: 2 waves across x NB column tiles x 16 rows x 128 B
     NBP = NB                                      # B pieces per wave and K step (A: 8)
-    if NB == 8:
+    if NB >= 7:
         FA = [[128 + 4 * i for i in range(8)], [192 + 4 * i for i in range(8)]]     # FA[half][i]: first VGPR of A fragment i
-        FB = [[160 + 4 * j for j in range(8)], [224 + 4 * j for j in range(8)]]
+        FB = [[160 + 4 * j for j in range(NB)], [224 + 4 * j for j in range(NB)]]   # (NB = 7 keeps the map of 8, one fragment short)
     else:
         FA = [[128 + 4 * i for i in range(8)], [160 + 4 * i for i in range(8)]]
         FB = [[192 + 4 * j for j in range(4)], [208 + 4 * j for j in range(4)]]
@@ -212,7 +222,7 @@ def gen(mfma, split=False, NB=8):
     at(NM - 2, sc['end_wait'])
     n_dma = sum(1 for m in ev for s_ in ev[m] if s_.startswith('buffer_load'))
     assert n_dma == 8 + NBP
-    assert n_before in (13, 8 + NBP), n_before
+    assert n_before == (8 + NBP if split or NB == 4 else {8: 13, 7: 12}[NB]), n_before
     # every LDS-DMA instruction has at least one instruction between it and the M0 write in front of it
     flat = [s_ for m in range(NM) for s_ in (['MFMA'] + ev[m])]
     for k, s_ in enumerate(flat):
@@ -246,9 +256,11 @@ def main():
     with open(out, 'w') as f:
         f.write('// GENERATED by tools/gen_kloop4w.py - do not edit.  The K loop of the 256 x 256 tile on four waves as inline assembly;\n')
         f.write('// interface, schedule and rationale: the generator\'s docstring.\n')
-        for NB, tag in ((8, ''), (4, 'N128_')):
+        for NB, tag in ((8, ''), (4, 'N128_'), (7, 'N224_')):
             for name, mfma, split in (('BF16', 'v_mfma_f32_16x16x32_bf16', False), ('F16', 'v_mfma_f32_16x16x32_f16', False),
                                       ('F16X3', 'v_mfma_f32_16x16x32_f16', True)):
+                if NB == 7 and split:
+                    continue                      # no split-precision 224-column form (schedule())
                 f.write('#define RON_KLOOP4W_%s%s \\\n' % (tag, name))
                 lines = gen(mfma, split, NB)
                 for k, s in enumerate(lines):
@@ -269,6 +281,15 @@ def main():
             for e_ in range(4):
                 txt = ''.join('v_accvgpr_read_b32 %%%d, a%d\\n' % (j, 16 * i + 4 * j + e_) for j in range(4))
                 outs = ', '.join('"=v"(v[%d])' % j for j in range(4))
+                last = (i == 7 and e_ == 3)
+                f.write('  case %d: asm volatile("%s" : %s); break;%s\n' % (i * 4 + e_, txt, outs, '' if last else ' \\'))
+        f.write('\n')
+        # the 256 x 224 tile: block (i, j), j < 7, in a[4 * (7 * i + j) : +3]
+        f.write('#define RON_ACC4W_N224_CASES \\\n')
+        for i in range(8):
+            for e_ in range(4):
+                txt = ''.join('v_accvgpr_read_b32 %%%d, a%d\\n' % (j, 28 * i + 4 * j + e_) for j in range(7))
+                outs = ', '.join('"=v"(v[%d])' % j for j in range(7))
                 last = (i == 7 and e_ == 3)
                 f.write('  case %d: asm volatile("%s" : %s); break;%s\n' % (i * 4 + e_, txt, outs, '' if last else ' \\'))
         f.write('\n')
