@@ -47,12 +47,23 @@ struct HeadsDev {
   const float* aw[RON_MAX_LAYERS];
 };
 
-struct PostDev {
+// What the three post-processing forms share of their configuration; a form's own struct adds only what is its own.
+struct PostCore {
   float obj_thr, sel_thr, nms_thr;
-  int top_k;
-  float ref[4];
+  float ref[4];                     // bbox_img / clipping_bbox
   float ps[4];
   unsigned flags;
+};
+struct PostDev : PostCore {         // np_methods form: ron_post_np, ron_detect
+  int top_k;
+};
+struct TfeDev : PostCore {          // TF-evaluation form: ron_post_tfe, ron_detect_tfe
+  int top_k, keep_top_k, nms_mode, clip;
+  float min_size;
+};
+struct EvalDev : PostCore {         // ron_eval.py form: ron_post_eval
+  int keep_top_k, nms_mode;
+  const float* min_size;            // [n] filter_boxes' min_size per image
 };
 
 struct DetDev {
@@ -76,70 +87,155 @@ __device__ __forceinline__ u64 make_key_any(float score, unsigned p) {
   return ((u64)u << 32) | (u64)(0xFFFFFFFFu - p);
 }
 
+__device__ __forceinline__ void decode_box(const float* l, float ya, float xa, float ha, float wa,
+                                           const float* ps, float* box) {
+  // np_methods.py:41-50 (== ssd_common.py:464-472)
+  const float cx = l[0] * wa * ps[0] + xa;
+  const float cy = l[1] * ha * ps[1] + ya;
+  const float w = wa * expf(l[2] * ps[2]);
+  const float h = ha * expf(l[3] * ps[3]);
+  box[0] = cy - h / 2.f;
+  box[1] = cx - w / 2.f;
+  box[2] = cy + h / 2.f;
+  box[3] = cx + w / 2.f;
+}
+
 // ------------------------------------------------------------------------------------------
-// K-select: one thread per anchor.  The block's class tensor chunk (256 anchors x C floats,
-// contiguous) is staged through LDS with coalesced loads; each thread then reads its C values
-// at stride C (C odd -> conflict free).
+// The box of an anchor, for every form: anchor index -> layer -> (cell, a) -> offsets -> box.
+// ------------------------------------------------------------------------------------------
+enum ClipMode {
+  kClipNone = 0,
+  kClipNp = 1,       // np_methods.py:153-164: no ymin <= ymax repair
+  kClipRepair = 2,   // tf_extended/bboxes.py:130-142: ymin <= ymax, xmin <= xmax afterwards
+};
+
+__device__ __forceinline__ int layer_of_anchor(const HeadsDev& hd, int anchor) {
+  int layer = 0;
+#pragma unroll
+  for (int l = 1; l < RON_MAX_LAYERS; ++l)
+    if (l < hd.num_layers && anchor >= hd.anchor_base[l]) layer = l;
+  return layer;
+}
+
+// `local`: the anchor's index inside its layer.  Decoded, or copied under RON_IN_LOC_DECODED, then clipped to pc.ref.
+__device__ __forceinline__ void anchor_box(const HeadsDev& hd, const PostCore& pc, int clip, int img, int layer, int local,
+                                           float* box) {
+  const int A = hd.num_anchors[layer];
+  const int cell = local / A, a = local - cell * A;
+  const size_t n_anchor_layer = (size_t)hd.cells[layer] * A;
+  const float* l4 = hd.loc[layer] + ((size_t)img * n_anchor_layer + local) * 4;
+  if (pc.flags & RON_IN_LOC_DECODED) {
+    box[0] = l4[0]; box[1] = l4[1]; box[2] = l4[2]; box[3] = l4[3];
+  } else {
+    decode_box(l4, hd.ay[layer][cell], hd.ax[layer][cell], hd.ah[layer][a], hd.aw[layer][a], pc.ps, box);
+  }
+  if (clip != kClipNone) {
+    box[0] = fmaxf(box[0], pc.ref[0]); box[1] = fmaxf(box[1], pc.ref[1]);
+    box[2] = fminf(box[2], pc.ref[2]); box[3] = fminf(box[3], pc.ref[3]);
+  }
+  if (clip == kClipRepair) {
+    box[0] = fminf(box[0], box[2]);    box[1] = fminf(box[1], box[3]);
+  }
+}
+
+// the same for a flattened anchor index (all layers, coarse -> fine)
+__device__ __forceinline__ void anchor_box(const HeadsDev& hd, const PostCore& pc, int clip, int img, int anchor, float* box) {
+  const int layer = layer_of_anchor(hd, anchor);
+  anchor_box(hd, pc, clip, img, layer, anchor - hd.anchor_base[layer], box);
+}
+
+// ------------------------------------------------------------------------------------------
+// The front end of every select kernel: one thread per anchor.  The block's class tensor chunk
+// (256 anchors x C floats, contiguous) is staged through LDS with coalesced loads; each thread
+// then reads its C values at stride C (C odd -> conflict free).
+// None of these helpers lets a lane leave: the kernels keep a `live` flag wherever a ballot or
+// shuffle follows.
+// ------------------------------------------------------------------------------------------
+struct SelectBlock {
+  int layer;
+  int first;            // first anchor of this block inside its layer
+  int n_here;           // anchors of this block: kSelectThreads, fewer in a layer's last block
+  int n_anchor_layer;
+  int local;            // this thread's anchor inside its layer (in range when threadIdx.x < n_here)
+};
+
+// locates the block (blockIdx.x: block of a layer, blockIdx.y: image), copies its n_here * C class values to `stage`; barrier
+__device__ __forceinline__ SelectBlock select_stage(const HeadsDev& hd, float* stage) {
+  SelectBlock b;
+  const int tid = threadIdx.x;
+  b.layer = 0;
+#pragma unroll
+  for (int l = 1; l < RON_MAX_LAYERS; ++l)
+    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) b.layer = l;
+  const int C = hd.num_classes;
+  b.n_anchor_layer = hd.cells[b.layer] * hd.num_anchors[b.layer];
+  b.first = ((int)blockIdx.x - hd.block_base[b.layer]) * kSelectThreads;
+  b.n_here = min(kSelectThreads, b.n_anchor_layer - b.first);
+  b.local = b.first + tid;
+  const float* cls = hd.cls[b.layer] + ((size_t)blockIdx.y * b.n_anchor_layer + b.first) * C;
+  for (int i = tid; i < b.n_here * C; i += kSelectThreads) stage[i] = cls[i];
+  __syncthreads();
+  return b;
+}
+
+// P(object) of this thread's anchor (eval_ron_network.py:227-229): the value itself under RON_IN_OBJ_IS_PROB, else
+// softmax(pair)[1] as softmax_last_kernel computes it.  The layer's obj tensor must exist.
+__device__ __forceinline__ float objectness(const HeadsDev& hd, unsigned flags, int img, const SelectBlock& b) {
+  const size_t i = (size_t)img * b.n_anchor_layer + b.local;
+  if (flags & RON_IN_OBJ_IS_PROB) return hd.obj[b.layer][i];
+  const float2 o = *reinterpret_cast<const float2*>(hd.obj[b.layer] + i * 2);
+  const float m = fmaxf(o.x, o.y);
+  const float e0 = expf(o.x - m), e1 = expf(o.y - m);
+  return e1 / (e0 + e1);
+}
+
+// Softmax of a staged row of logits, in place: row[c] <- expf(row[c] - mx), *sum <- their sum taken in the order c = 0..C-1
+// (softmax_last_kernel's).  The score of class c is then row[c] / *sum whichever pass of a kernel asks for it, and however often:
+// the same exponential divided by the same sum.
+//   exit_thr > 0 enables the early exit: softmax_c = exp(x_c - mx) / sum <= exp(x_c - mx) (the sum holds exp(0) = 1), so when
+// even the best non-background class stays below exit_thr by a margin far above any rounding of the real computation, no class of
+// the anchor passes a test `score > exit_thr`; the row is left as it is, its C exponentials are skipped and false is returned
+// (background-dominated anchors: most of a real image).  exit_thr = 0: never (logf(0) = -inf).
+__device__ __forceinline__ bool row_softmax(float* row, int C, float exit_thr, float* sum) {
+  float mx1 = -INFINITY;                       // best non-background logit
+  for (int c = 1; c < C; ++c) mx1 = fmaxf(mx1, row[c]);
+  const float mx = fmaxf(row[0], mx1);
+  if (mx1 - mx < logf(exit_thr) - 1e-2f) return false;
+  float s = 0.f;
+  for (int c = 0; c < C; ++c) {
+    const float e = expf(row[c] - mx);
+    row[c] = e;
+    s += e;
+  }
+  *sum = s;
+  return true;
+}
+
+// score of class c of a row: probability inputs (RON_IN_CLS_IS_PROB) are the scores themselves, nothing is computed
+__device__ __forceinline__ float row_score(const float* row, int c, float sum, bool is_prob) {
+  return is_prob ? row[c] : row[c] / sum;
+}
+
+// ------------------------------------------------------------------------------------------
+// K-select (np_methods form).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kSelectThreads) void select_kernel(HeadsDev hd, PostDev pc, u64* keys,
                                                                 int* counts, int cap) {
   extern __shared__ __attribute__((aligned(16))) float stage[];
   const int img = blockIdx.y;
   const int tid = threadIdx.x;
-  int layer = 0;
-#pragma unroll
-  for (int l = 1; l < RON_MAX_LAYERS; ++l)
-    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) layer = l;
   const int C = hd.num_classes;
-  const int n_anchor_layer = hd.cells[layer] * hd.num_anchors[layer];
-  const int first = ((int)blockIdx.x - hd.block_base[layer]) * kSelectThreads;
-  const int n_here = min(kSelectThreads, n_anchor_layer - first);
+  const SelectBlock b = select_stage(hd, stage);
+  const int layer = b.layer, local = b.local;
+  bool gate = tid < b.n_here;
+  if (gate && hd.obj[layer] != nullptr) gate = objectness(hd, pc.flags, img, b) > pc.obj_thr;
 
-  const float* cls = hd.cls[layer] + ((size_t)img * n_anchor_layer + first) * C;
-  for (int i = tid; i < n_here * C; i += kSelectThreads) stage[i] = cls[i];
-  __syncthreads();
-
-  const bool active = tid < n_here;
-  const int local = first + tid;
-  bool gate = active;
-  if (active && hd.obj[layer] != nullptr) {
-    float objp;
-    if (pc.flags & RON_IN_OBJ_IS_PROB) {
-      objp = hd.obj[layer][(size_t)img * n_anchor_layer + local];
-    } else {
-      const float2 o = *reinterpret_cast<const float2*>(hd.obj[layer] + ((size_t)img * n_anchor_layer + local) * 2);
-      const float m = fmaxf(o.x, o.y);
-      const float e0 = expf(o.x - m), e1 = expf(o.y - m);
-      objp = e1 / (e0 + e1);
-    }
-    gate = objp > pc.obj_thr;   // eval_ron_network.py:227-229
-  }
-
-  // scores of this anchor.  The row's exponentials are computed ONCE and kept in the row's own LDS slots (the three passes
-  // below divide the same values by the same sum: the bits of a score do not depend on which pass computed it).
-  float inv_sum = 1.f, mx = 0.f;
+  // scores of this anchor: the three passes below divide the same values by the same sum (row_softmax)
+  float sum = 1.f;
   float* row = stage + tid * C;
   const bool is_prob = (pc.flags & RON_IN_CLS_IS_PROB) != 0;
   const bool argmax_mode = pc.sel_thr == 0.f;
-  if (gate && !is_prob) {
-    mx = row[0];
-    float mx1 = -INFINITY;                       // best non-background logit
-    for (int c = 1; c < C; ++c) mx1 = fmaxf(mx1, row[c]);
-    mx = fmaxf(mx, mx1);
-    // softmax_c = exp(x_c - mx) / sum <= exp(x_c - mx) (the sum holds exp(0) = 1): when even the best class stays below the
-    // threshold by a margin far above any rounding of the real computation, the anchor selects nothing and its 2 C
-    // exponentials and C divisions are skipped (background-dominated anchors: most of a real image)
-    if (!argmax_mode && mx1 - mx < logf(pc.sel_thr) - 1e-2f) gate = false;
-  }
-  if (gate && !is_prob) {
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) {
-      const float e = expf(row[c] - mx);
-      row[c] = e;
-      s += e;
-    }
-    inv_sum = s;
-  }
+  if (gate && !is_prob) gate = row_softmax(row, C, pc.sel_thr, &sum);
   int n_sel = 0;
   // select_threshold 0 / None: the "score > no-label" branch of ssd_bboxes_select_layer (np_methods.py:82-89): ONE candidate per
   // anchor, the arg-max over ALL classes (first maximum, like np.argmax), kept when it is not the background class.  A gated-out
@@ -147,15 +243,15 @@ __global__ __launch_bounds__(kSelectThreads) void select_kernel(HeadsDev hd, Pos
   int best_c = 0;
   float best_sc = 0.f;
   if (gate && argmax_mode) {
-    best_sc = is_prob ? row[0] : row[0] / inv_sum;
+    best_sc = row_score(row, 0, sum, is_prob);
     for (int c = 1; c < C; ++c) {
-      const float sc = is_prob ? row[c] : row[c] / inv_sum;
+      const float sc = row_score(row, c, sum, is_prob);
       if (sc > best_sc) { best_sc = sc; best_c = c; }
     }
     n_sel = best_c > 0 ? 1 : 0;
   } else if (gate) {
     for (int c = 1; c < C; ++c) {
-      const float sc = is_prob ? row[c] : row[c] / inv_sum;
+      const float sc = row_score(row, c, sum, is_prob);
       n_sel += (sc > pc.sel_thr) ? 1 : 0;
     }
   }
@@ -180,7 +276,7 @@ __global__ __launch_bounds__(kSelectThreads) void select_kernel(HeadsDev hd, Pos
       return;
     }
     for (int c = 1; c < C; ++c) {
-      const float sc = is_prob ? row[c] : row[c] / inv_sum;
+      const float sc = row_score(row, c, sum, is_prob);
       if (sc > pc.sel_thr) {
         if (pos < cap) out[pos] = make_key(sc, p0 + (unsigned)(c - 1));
         ++pos;
@@ -690,19 +786,6 @@ __device__ void store_sorted(const ImageLds& lds, int n, const DetDev& out, int 
   if (threadIdx.x == 0) out.count[img] = min(n, out.capacity);
 }
 
-__device__ __forceinline__ void decode_box(const float* l, float ya, float xa, float ha, float wa,
-                                           const float* ps, float* box) {
-  // np_methods.py:41-50 (== ssd_common.py:464-472)
-  const float cx = l[0] * wa * ps[0] + xa;
-  const float cy = l[1] * ha * ps[1] + ya;
-  const float w = wa * expf(l[2] * ps[2]);
-  const float h = ha * expf(l[3] * ps[3]);
-  box[0] = cy - h / 2.f;
-  box[1] = cx - w / 2.f;
-  box[2] = cy + h / 2.f;
-  box[3] = cx + w / 2.f;
-}
-
 // ------------------------------------------------------------------------------------------
 // K-topk-partial: blockIdx.x = range of the image's key list, blockIdx.y = image.  Only for images with > kPartMin keys.
 // ------------------------------------------------------------------------------------------
@@ -748,26 +831,9 @@ __global__ __launch_bounds__(kTopkThreads) void topk_nms_kernel(HeadsDev hd, Pos
     const unsigned p = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
     const int anchor = (int)(p / (unsigned)C1);
     const int cls = (int)(p - (unsigned)anchor * (unsigned)C1) + 1;
-    int layer = 0;
-#pragma unroll
-    for (int l = 1; l < RON_MAX_LAYERS; ++l)
-      if (l < hd.num_layers && anchor >= hd.anchor_base[l]) layer = l;
-    const int local = anchor - hd.anchor_base[layer];
-    const int A = hd.num_anchors[layer];
-    const int cell = local / A, a = local - cell * A;
-    const size_t n_anchor_layer = (size_t)hd.cells[layer] * A;
-    const float* l4 = hd.loc[layer] + ((size_t)img * n_anchor_layer + local) * 4;
     float box[4];
-    if (pc.flags & RON_IN_LOC_DECODED) {
-      box[0] = l4[0]; box[1] = l4[1]; box[2] = l4[2]; box[3] = l4[3];
-    } else {
-      decode_box(l4, hd.ay[layer][cell], hd.ax[layer][cell], hd.ah[layer][a], hd.aw[layer][a], pc.ps, box);
-    }
-    // np_methods.py:153-164 (clip: no ymin<=ymax repair)
-    lds.box[r][0] = fmaxf(box[0], pc.ref[0]);
-    lds.box[r][1] = fmaxf(box[1], pc.ref[1]);
-    lds.box[r][2] = fminf(box[2], pc.ref[2]);
-    lds.box[r][3] = fminf(box[3], pc.ref[3]);
+    anchor_box(hd, pc, kClipNp, img, anchor, box);
+    lds.box[r][0] = box[0]; lds.box[r][1] = box[1]; lds.box[r][2] = box[2]; lds.box[r][3] = box[3];
     lds.score[r] = score;
     lds.cls[r] = cls;
     lds.anchor[r] = anchor;
@@ -891,16 +957,73 @@ int to_det_dev(const ron_detections* d, DetDev* out, int top_k, const char* what
   return RON_OK;
 }
 
-// = ron_post_np_workspace_bytes for k images of `cap` candidates each
-int64_t np_bytes_for(int64_t cap, int64_t k) {
-  return 2 * ron::align_up(k * kCountStride * 4, 256) + k * cap * 8 + k * kPartChunks * kMaxTopK * 8;
+void fill_core(PostCore* pc, float objectness_thres, float select_threshold, float nms_threshold, const float ref[4],
+               const float prior_scaling[4], unsigned flags) {
+  pc->obj_thr = objectness_thres; pc->sel_thr = select_threshold; pc->nms_thr = nms_threshold; pc->flags = flags;
+  for (int i = 0; i < 4; ++i) { pc->ref[i] = ref[i]; pc->ps[i] = prior_scaling[i]; }
+}
+
+// Launches one of the select kernels: blocks of all layers x images, the block's class rows in dynamic LDS.  The kernel is a
+// template argument so that each kernel has a once-object of its own: the dynamic-LDS attribute is per function.
+template <auto Kernel, class Dev>
+int launch_select(const HeadsDev& hd, const Dev& pc, int n, u64* keys, int* counts, int cap, hipStream_t s) {
+  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
+  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
+    static ron::PerDeviceOnce once;
+    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(Kernel), (int)lds));
+  }
+  RON_LAUNCH(Kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys, counts, cap);
+  return RON_OK;
+}
+
+// Workspace of the np_methods form for k images of `cap` candidates each:
+//   [candidate counts][survivor counts of the partial pass][keys][survivors]
+struct NpLayout {
+  int64_t cnt_bytes;      // each of the two counter regions
+  int64_t keys_off, part_off, bytes;
+};
+NpLayout np_layout(int64_t cap, int64_t k) {
+  NpLayout w;
+  w.cnt_bytes = ron::align_up(k * kCountStride * 4, 256);
+  w.keys_off = 2 * w.cnt_bytes;
+  w.part_off = w.keys_off + k * cap * 8;
+  w.bytes = w.part_off + k * kPartChunks * kMaxTopK * 8;
+  return w;
 }
 // images a self-cleaning workspace (kPostWsClean) lays its counters out for: the most it holds, not n, so that the counters stay
 // where they are for calls of any n (laid out for n, a batch of 1 wrote its keys over the counters of a later batch of 32)
 int np_clean_layout_images(int64_t cap, int n, int64_t workspace_bytes) {
   int k = n;
-  while (np_bytes_for(cap, k + 1) <= workspace_bytes) ++k;
+  while (np_layout(cap, k + 1).bytes <= workspace_bytes) ++k;
   return k;
+}
+
+// Workspace of the TF-evaluation form: [counters, one int per (image, class) list][keys: lists x anchors]
+struct TfeLayout {
+  int64_t cnt_bytes;      // = the offset of the keys
+  int64_t bytes;
+};
+TfeLayout tfe_layout(int64_t lists, int64_t anchors) {
+  TfeLayout w;
+  w.cnt_bytes = ron::align_up(lists * 4, 256);
+  w.bytes = w.cnt_bytes + lists * anchors * 8;
+  return w;
+}
+
+// Workspace of the ron_eval.py form: [counters, one 128-byte line per list][keys: lists x anchors][nms_mode | 4: best, n x anchors]
+struct EvalLayout {
+  int64_t lists;          // n, or n x num_classes score columns under nms_mode | 4
+  int64_t cnt_bytes;      // = the offset of the keys
+  int64_t best_off, best_bytes, bytes;
+};
+EvalLayout eval_layout(int64_t n, int num_classes, int64_t anchors, int nms_mode) {
+  EvalLayout w;
+  w.lists = (nms_mode & 4) ? n * num_classes : n;
+  w.cnt_bytes = ron::align_up(w.lists * kCountStride * 4, 256);
+  w.best_off = w.cnt_bytes + w.lists * anchors * 8;
+  w.best_bytes = (nms_mode & 4) ? n * anchors * 8 : 0;
+  w.bytes = w.best_off + w.best_bytes;
+  return w;
 }
 
 }  // namespace
@@ -908,9 +1031,7 @@ int np_clean_layout_images(int64_t cap, int n, int64_t workspace_bytes) {
 extern "C" int64_t ron_post_np_workspace_bytes(const ron_heads* heads, int n) {
   HeadsDev hd;
   if (build_heads_dev(heads, &hd, false) != RON_OK || n <= 0) return -1;
-  const int64_t cap = (int64_t)hd.anchor_base[RON_MAX_LAYERS] * (heads->num_classes - 1);
-  // [candidate counts][survivor counts of the partial pass][keys][survivors]
-  return np_bytes_for(cap, n);
+  return np_layout((int64_t)hd.anchor_base[RON_MAX_LAYERS] * (heads->num_classes - 1), n).bytes;
 }
 
 extern "C" int ron_post_np(const ron_heads* heads, int n, const ron_post_cfg* cfg, void* workspace,
@@ -929,27 +1050,19 @@ extern "C" int ron_post_np(const ron_heads* heads, int n, const ron_post_cfg* cf
   if ((rc = to_det_dev(out, &d_out, cfg->top_k, "out", false)) != RON_OK) return rc;
   if ((rc = to_det_dev(sorted_out, &d_sorted, cfg->top_k, "sorted_out", true)) != RON_OK) return rc;
   PostDev pc;
-  pc.obj_thr = cfg->objectness_thres; pc.sel_thr = cfg->select_threshold; pc.nms_thr = cfg->nms_threshold;
-  pc.top_k = cfg->top_k; pc.flags = cfg->input_flags;
-  for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->bbox_img[i]; pc.ps[i] = cfg->prior_scaling[i]; }
+  fill_core(&pc, cfg->objectness_thres, cfg->select_threshold, cfg->nms_threshold, cfg->bbox_img, cfg->prior_scaling, cfg->input_flags);
+  pc.top_k = cfg->top_k;
   hipStream_t s = (hipStream_t)stream;
-  // Layout: [counts][part_total][keys of n images][partial keys].  A self-cleaning workspace (kPostWsClean) is reused by calls of
-  // different n and must keep its counters where they are (np_clean_layout_images)
+  // A self-cleaning workspace (kPostWsClean) is reused by calls of different n and must keep its counters where they are
+  // (np_clean_layout_images)
   const int cap = hd.anchor_base[RON_MAX_LAYERS] * (hd.num_classes - 1);
-  const int n_layout = (cfg->input_flags & ron::kPostWsClean) ? np_clean_layout_images(cap, n, workspace_bytes) : n;
-  const int64_t cnt_bytes = ron::align_up((int64_t)n_layout * kCountStride * 4, 256);
+  const NpLayout w = np_layout(cap, (cfg->input_flags & ron::kPostWsClean) ? np_clean_layout_images(cap, n, workspace_bytes) : n);
   int* counts = (int*)workspace;
-  int* part_total = (int*)((char*)workspace + cnt_bytes);
-  u64* keys = (u64*)((char*)workspace + 2 * cnt_bytes);
-  u64* part_keys = keys + (size_t)n_layout * cap;
-  if (!(cfg->input_flags & ron::kPostWsClean)) RON_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * cnt_bytes, s));
-  dim3 grid(hd.block_base[RON_MAX_LAYERS], n);
-  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
-  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
-    static ron::PerDeviceOnce once;
-    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&select_kernel), (int)lds));
-  }
-  RON_LAUNCH(select_kernel, grid, dim3(kSelectThreads), lds, s, hd, pc, keys, counts, cap);
+  int* part_total = (int*)((char*)workspace + w.cnt_bytes);
+  u64* keys = (u64*)((char*)workspace + w.keys_off);
+  u64* part_keys = (u64*)((char*)workspace + w.part_off);
+  if (!(cfg->input_flags & ron::kPostWsClean)) RON_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * w.cnt_bytes, s));
+  if ((rc = launch_select<select_kernel>(hd, pc, n, keys, counts, cap, s)) != RON_OK) return rc;
   // only lists that can exceed kPartMin need the partial pass at all (its workgroups return at once for shorter ones)
   if (cap > kPartMin)
     RON_LAUNCH(topk_partial_kernel, dim3(kPartChunks, n), dim3(kTopkThreads), 0, s, keys, counts, cap, pc.top_k, part_keys, part_total);
@@ -1045,90 +1158,59 @@ extern "C" int ron_softmax_last(const float* x, int64_t rows, int c, int pick, f
 // ==========================================================================================
 namespace {
 
-struct TfeDev {
-  float obj_thr, sel_thr, nms_thr;
-  int top_k, keep_top_k, nms_mode, clip;
-  float ref[4];
-  float min_size;
-  float ps[4];
-  unsigned flags;
-};
+__device__ __forceinline__ int tfe_clip(const TfeDev& pc) { return pc.clip ? kClipRepair : kClipNone; }
 
-__device__ __forceinline__ void tfe_box(const HeadsDev& hd, const TfeDev& pc, int img, int layer, int local, float* box) {
-  const int A = hd.num_anchors[layer];
-  const int cell = local / A, a = local - cell * A;
-  const size_t n_anchor_layer = (size_t)hd.cells[layer] * A;
-  const float* l4 = hd.loc[layer] + ((size_t)img * n_anchor_layer + local) * 4;
-  if (pc.flags & RON_IN_LOC_DECODED) {
-    box[0] = l4[0]; box[1] = l4[1]; box[2] = l4[2]; box[3] = l4[3];
-  } else {
-    decode_box(l4, hd.ay[layer][cell], hd.ax[layer][cell], hd.ah[layer][a], hd.aw[layer][a], pc.ps, box);
-  }
-  if (pc.clip) {   // tf_extended/bboxes.py:130-142
-    box[0] = fmaxf(box[0], pc.ref[0]); box[1] = fmaxf(box[1], pc.ref[1]);
-    box[2] = fminf(box[2], pc.ref[2]); box[3] = fminf(box[3], pc.ref[3]);
-    box[0] = fminf(box[0], box[2]);    box[1] = fminf(box[1], box[3]);
-  }
-}
-
-// one thread per anchor; candidates go to per-(image, class) lists keyed by (score, anchor index)
-__global__ __launch_bounds__(kSelectThreads) void tfe_select_kernel(HeadsDev hd, TfeDev pc, u64* keys, int* counts,
-                                                                    int cap) {
+// The select of the TF-evaluation form (ron_post_tfe and ron_detect_tfe): one thread per anchor; candidates go to per-(image,
+// class) lists keyed by (score, anchor index).  Any input form: logits or probabilities, objectness logit pairs, probabilities or
+// none, raw offsets or decoded boxes.
+//   - an anchor of logits whose best class stays below the background's by more than -log(select_threshold) + 1e-2 selects
+//     nothing and skips its exponentials (row_softmax); never for select_threshold 0, never for probabilities;
+//   - the box of an anchor that lists something is decoded once, by all such lanes of the wave together;
+//   - one atomic per (wave, class) that has passing lanes, each lane's slot by prefix popcount of the wave's ballot (list order
+//     does not matter: keys carry the anchor index and are sorted), instead of one per (anchor, class).
+// Counters: one int per (image, class) list, zero on entry; tfe_topk_nms_kernel zeroes them again (kPostWsClean).
+__global__ __launch_bounds__(kSelectThreads) void tfe_select_kernel(HeadsDev hd, TfeDev pc, u64* keys, int* counts, int cap) {
   extern __shared__ __attribute__((aligned(16))) float stage[];
   const int img = blockIdx.y;
-  const int tid = threadIdx.x;
-  int layer = 0;
-#pragma unroll
-  for (int l = 1; l < RON_MAX_LAYERS; ++l)
-    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) layer = l;
+  const int tid = threadIdx.x, lane = tid & 63;
   const int C = hd.num_classes;
-  const int n_anchor_layer = hd.cells[layer] * hd.num_anchors[layer];
-  const int first = ((int)blockIdx.x - hd.block_base[layer]) * kSelectThreads;
-  const int n_here = min(kSelectThreads, n_anchor_layer - first);
-  const float* cls = hd.cls[layer] + ((size_t)img * n_anchor_layer + first) * C;
-  for (int i = tid; i < n_here * C; i += kSelectThreads) stage[i] = cls[i];
-  __syncthreads();
-  if (tid >= n_here) return;
-  const int local = first + tid;
-  if (hd.obj[layer] != nullptr) {
-    float objp;
-    if (pc.flags & RON_IN_OBJ_IS_PROB) {
-      objp = hd.obj[layer][(size_t)img * n_anchor_layer + local];
-    } else {
-      const float2 o = *reinterpret_cast<const float2*>(hd.obj[layer] + ((size_t)img * n_anchor_layer + local) * 2);
-      const float m = fmaxf(o.x, o.y);
-      const float e0 = expf(o.x - m), e1 = expf(o.y - m);
-      objp = e1 / (e0 + e1);
-    }
-    if (!(objp > pc.obj_thr)) return;
-  }
-  const float* row = stage + tid * C;
+  const SelectBlock b = select_stage(hd, stage);
+  bool live = tid < b.n_here;
+  if (live && hd.obj[b.layer] != nullptr) live = objectness(hd, pc.flags, img, b) > pc.obj_thr;
+  float* row = stage + tid * C;
   const bool is_prob = (pc.flags & RON_IN_CLS_IS_PROB) != 0;
-  float sum = 1.f, mx = 0.f;
-  if (!is_prob) {
-    mx = row[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-    float s = 0.f;
-    for (int c = 0; c < C; ++c) s += expf(row[c] - mx);
-    sum = s;
+  float s = 1.f;
+  if (live && !is_prob) live = row_softmax(row, C, pc.sel_thr, &s);
+  // an anchor with a passing class: decode, clip with repair, bboxes_filter_min (ron_vgg_320.py:222-225), all lanes of the wave
+  // at once (decoded in the class loop, lanes whose first passing class differs would wait for their loads one after another)
+  if (live) {
+    bool any = false;
+    for (int c = 1; c < C && !any; ++c) any = row_score(row, c, s, is_prob) > pc.sel_thr;
+    live = any;
   }
-  bool have_box = false, size_ok = true;
+  if (live) {
+    float box[4];
+    anchor_box(hd, pc, tfe_clip(pc), img, b.layer, b.local, box);
+    if (pc.min_size >= 0.f && !((box[3] - box[1]) > pc.min_size && (box[2] - box[0]) > pc.min_size)) live = false;
+  }
+  const u64 below = (1ull << lane) - 1ull;
+  const unsigned anchor = (unsigned)(hd.anchor_base[b.layer] + b.local);
+  const int C1 = C - 1;
+  // (every branch below that a ballot or shuffle follows is wave-uniform: the lanes stay converged)
+  if (__ballot(live) == 0ull) return;
   for (int c = 1; c < C; ++c) {
-    const float sc = is_prob ? row[c] : expf(row[c] - mx) / sum;
-    if (!(sc > pc.sel_thr)) continue;
-    if (!have_box) {
-      float box[4];
-      tfe_box(hd, pc, img, layer, local, box);
-      if (pc.min_size >= 0.f) {   // ron_vgg_320.py:222-225
-        const float h = box[2] - box[0], w = box[3] - box[1];
-        size_ok = (w > pc.min_size) && (h > pc.min_size);
-      }
-      have_box = true;
+    const float sc = live ? row_score(row, c, s, is_prob) : 0.f;
+    const bool pass = live && sc > pc.sel_thr;
+    const u64 bal = __ballot(pass);
+    if (bal == 0ull) continue;
+    const int leader = __ffsll((long long)bal) - 1;
+    int base = 0;
+    if (lane == leader) base = atomicAdd(&counts[(size_t)img * C1 + (c - 1)], __popcll(bal));
+    base = __shfl(base, leader, 64);
+    if (pass) {
+      const int pos = base + __popcll(bal & below);
+      if (pos < cap) keys[((size_t)img * C1 + (c - 1)) * cap + pos] = make_key(sc, anchor);
     }
-    if (!size_ok) break;
-    const size_t list = (size_t)img * (C - 1) + (c - 1);
-    const int pos = atomicAdd(&counts[list], 1);
-    if (pos < cap) keys[list * cap + pos] = make_key(sc, (unsigned)(hd.anchor_base[layer] + local));
   }
 }
 
@@ -1144,12 +1226,8 @@ __global__ __launch_bounds__(kTopkThreads) void tfe_topk_nms_kernel(HeadsDev hd,
   for (int r = tid; r < n; r += blockDim.x) {
     const u64 k = lds.sort[r];
     const int anchor = (int)(0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull));
-    int layer = 0;
-#pragma unroll
-    for (int l = 1; l < RON_MAX_LAYERS; ++l)
-      if (l < hd.num_layers && anchor >= hd.anchor_base[l]) layer = l;
     float box[4];
-    tfe_box(hd, pc, img, layer, anchor - hd.anchor_base[layer], box);
+    anchor_box(hd, pc, tfe_clip(pc), img, anchor, box);
     lds.box[r][0] = box[0]; lds.box[r][1] = box[1]; lds.box[r][2] = box[2]; lds.box[r][3] = box[3];
     lds.score[r] = __uint_as_float((unsigned)(k >> 32));
     lds.cls[r] = c1 + 1;
@@ -1174,175 +1252,55 @@ __global__ __launch_bounds__(kTopkThreads) void tfe_topk_nms_kernel(HeadsDev hd,
   }
 }
 
-// The select of ron_detect_tfe: the context's raw heads (logits, objectness logit pairs or none, raw offsets), the scores of
-// tfe_select_kernel bit for bit, leaner:
-//   - the row's C exponentials are computed once and kept in its own LDS slots (tfe_select_kernel computes 2 C), then divided by
-//     the sum: expf(x_c - m) / s with m and s taken in softmax_last_kernel's order;
-//   - an anchor whose best class logit stays below the background's by more than -log(select_threshold) + 1e-2 selects nothing
-//     (select_kernel's bound: score_c <= exp(x_c - m)) and skips its exponentials; never for select_threshold 0;
-//   - the box of an anchor that lists something is decoded once, by all such lanes of the wave together;
-//   - one atomic per (wave, class) that has passing lanes, each lane's slot by prefix popcount of the wave's ballot (list order
-//     does not matter: keys carry the anchor index and are sorted), instead of one per (anchor, class).
-// Counters: one int per (image, class) list, zero on entry; tfe_topk_nms_kernel zeroes them again (kPostWsClean).
-__global__ __launch_bounds__(kSelectThreads) void tfe_select_raw_kernel(HeadsDev hd, TfeDev pc, u64* keys, int* counts, int cap) {
-  extern __shared__ __attribute__((aligned(16))) float stage[];
-  const int img = blockIdx.y;
-  const int tid = threadIdx.x, lane = tid & 63;
-  int layer = 0;
-#pragma unroll
-  for (int l = 1; l < RON_MAX_LAYERS; ++l)
-    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) layer = l;
-  const int C = hd.num_classes;
-  const int n_anchor_layer = hd.cells[layer] * hd.num_anchors[layer];
-  const int first = ((int)blockIdx.x - hd.block_base[layer]) * kSelectThreads;
-  const int n_here = min(kSelectThreads, n_anchor_layer - first);
-  const float* cls = hd.cls[layer] + ((size_t)img * n_anchor_layer + first) * C;
-  for (int i = tid; i < n_here * C; i += kSelectThreads) stage[i] = cls[i];
-  __syncthreads();
-  const int local = first + tid;
-  bool live = tid < n_here;
-  if (live && hd.obj[layer] != nullptr) {      // eval_ron_network.py:227-229, objness = softmax(pair)[1] as softmax_last_kernel
-    const float2 o = *reinterpret_cast<const float2*>(hd.obj[layer] + ((size_t)img * n_anchor_layer + local) * 2);
-    const float m = fmaxf(o.x, o.y);
-    const float e0 = expf(o.x - m), e1 = expf(o.y - m);
-    live = e1 / (e0 + e1) > pc.obj_thr;
-  }
-  float* row = stage + tid * C;
-  float s = 1.f;
-  if (live) {
-    float mx = row[0], mx1 = -INFINITY;
-    for (int c = 1; c < C; ++c) { mx = fmaxf(mx, row[c]); mx1 = fmaxf(mx1, row[c]); }
-    if (mx1 - mx < logf(pc.sel_thr) - 1e-2f) live = false;
-    if (live) {
-      s = 0.f;
-      for (int c = 0; c < C; ++c) {
-        const float e = expf(row[c] - mx);
-        row[c] = e;
-        s += e;
-      }
-    }
-  }
-  // an anchor with a passing class: decode, clip with repair, bboxes_filter_min (ron_vgg_320.py:222-225), all lanes of the wave
-  // at once (decoded in the class loop, lanes whose first passing class differs would wait for their loads one after another)
-  if (live) {
-    bool any = false;
-    for (int c = 1; c < C && !any; ++c) any = row[c] / s > pc.sel_thr;
-    live = any;
-  }
-  if (live) {
-    float box[4];
-    tfe_box(hd, pc, img, layer, local, box);
-    if (pc.min_size >= 0.f && !((box[3] - box[1]) > pc.min_size && (box[2] - box[0]) > pc.min_size)) live = false;
-  }
-  const u64 below = (1ull << lane) - 1ull;
-  const unsigned anchor = (unsigned)(hd.anchor_base[layer] + local);
-  const int C1 = C - 1;
-  // (every branch below that a ballot or shuffle follows is wave-uniform: the lanes stay converged)
-  if (__ballot(live) == 0ull) return;
-  for (int c = 1; c < C; ++c) {
-    const float sc = live ? row[c] / s : 0.f;
-    const bool pass = live && sc > pc.sel_thr;
-    const u64 bal = __ballot(pass);
-    if (bal == 0ull) continue;
-    const int leader = __ffsll((long long)bal) - 1;
-    int base = 0;
-    if (lane == leader) base = atomicAdd(&counts[(size_t)img * C1 + (c - 1)], __popcll(bal));
-    base = __shfl(base, leader, 64);
-    if (pass) {
-      const int pos = base + __popcll(bal & below);
-      if (pos < cap) keys[((size_t)img * C1 + (c - 1)) * cap + pos] = make_key(sc, anchor);
-    }
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // ron_eval.py variant (the reference's second, per-image harness): flaten_predict (ron_eval.py:111-144) ->
 // tfe.bboxes_clip -> filter_boxes (:369-392) -> tf_bboxes_nms (:146-206, class agnostic) -> bboxes_resize.
 // ------------------------------------------------------------------------------------------
-struct EvalDev {
-  float obj_thr, sel_thr, nms_thr;
-  int keep_top_k, nms_mode;
-  float ref[4];
-  float ps[4];
-  unsigned flags;
-  const float* min_size;     // [n] filter_boxes' min_size per image
-};
-
-__device__ __forceinline__ void eval_box(const HeadsDev& hd, const EvalDev& pc, int img, int layer, int local, float* box) {
-  TfeDev t;
-  t.flags = pc.flags; t.clip = 1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) { t.ref[i] = pc.ref[i]; t.ps[i] = pc.ps[i]; }
-  tfe_box(hd, t, img, layer, local, box);
-}
-
 // one thread per anchor: score[c] = objectness * class probability, label = argmax over ALL classes (first maximum),
 // kept when label > 0 and objectness > thres, the clipped box passes filter_boxes and score[label] > select_threshold.
 // key = (score, anchor * 64 + label): score descending, then the flattened anchor order like tf.nn.top_k.
+// (No ballot or shuffle in this kernel: a lane that has nothing to list leaves.)
 __global__ __launch_bounds__(kSelectThreads) void eval_select_kernel(HeadsDev hd, EvalDev pc, u64* keys, int* counts, int cap) {
   extern __shared__ __attribute__((aligned(16))) float stage[];
   const int img = blockIdx.y;
   const int tid = threadIdx.x;
-  int layer = 0;
-#pragma unroll
-  for (int l = 1; l < RON_MAX_LAYERS; ++l)
-    if (l < hd.num_layers && (int)blockIdx.x >= hd.block_base[l]) layer = l;
   const int C = hd.num_classes;
-  const int n_anchor_layer = hd.cells[layer] * hd.num_anchors[layer];
-  const int first = ((int)blockIdx.x - hd.block_base[layer]) * kSelectThreads;
-  const int n_here = min(kSelectThreads, n_anchor_layer - first);
-  const float* cls = hd.cls[layer] + ((size_t)img * n_anchor_layer + first) * C;
-  for (int i = tid; i < n_here * C; i += kSelectThreads) stage[i] = cls[i];
-  __syncthreads();
-  if (tid >= n_here) return;
-  const int local = first + tid;
-  float objp;
-  if (pc.flags & RON_IN_OBJ_IS_PROB) {
-    objp = hd.obj[layer][(size_t)img * n_anchor_layer + local];
-  } else {
-    const float2 o = *reinterpret_cast<const float2*>(hd.obj[layer] + ((size_t)img * n_anchor_layer + local) * 2);
-    const float m = fmaxf(o.x, o.y);
-    const float e0 = expf(o.x - m), e1 = expf(o.y - m);
-    objp = e1 / (e0 + e1);
-  }
+  const SelectBlock b = select_stage(hd, stage);
+  if (tid >= b.n_here) return;
+  const float objp = objectness(hd, pc.flags, img, b);
   if (!(objp > pc.obj_thr)) return;
-  const float* row = stage + tid * C;
+  float* row = stage + tid * C;
   const bool is_prob = (pc.flags & RON_IN_CLS_IS_PROB) != 0;
-  float sum = 1.f, mx = 0.f;
-  if (!is_prob) {
-    mx = row[0];
-    for (int c = 1; c < C; ++c) mx = fmaxf(mx, row[c]);
-    float sacc = 0.f;
-    for (int c = 0; c < C; ++c) sacc += expf(row[c] - mx);
-    sum = sacc;
-  }
+  float sum = 1.f;
+  if (!is_prob) row_softmax(row, C, 0.f, &sum);      // no early exit: the arg-max runs over all classes
   int label = 0;
-  float best = objp * (is_prob ? row[0] : expf(row[0] - mx) / sum);
+  float best = objp * row_score(row, 0, sum, is_prob);
   for (int c = 1; c < C; ++c) {
-    const float sc = objp * (is_prob ? row[c] : expf(row[c] - mx) / sum);
+    const float sc = objp * row_score(row, c, sum, is_prob);
     if (sc > best) { best = sc; label = c; }
   }
   if (label == 0 || !(best > pc.sel_thr)) return;
   float box[4];
-  eval_box(hd, pc, img, layer, local, box);
+  anchor_box(hd, pc, kClipRepair, img, b.layer, b.local, box);
   const float ws = box[3] - box[1], hs = box[2] - box[0];
   const float xc = box[1] + ws / 2.f, yc = box[0] + hs / 2.f;
   const float ms = pc.min_size[img];
   if (!(ws > ms && hs > ms && xc > 0.f && yc > 0.f && xc < 1.f && yc < 1.f)) return;
+  const unsigned anchor = (unsigned)(hd.anchor_base[b.layer] + b.local);
   if (pc.nms_mode & 4) {
     // tf_bboxes_nms_by_class (ron_eval.py:212-280): one list per score column, background included; a row is a candidate of every
     // class whose score passes select_threshold (:226)
     for (int c = 0; c < C; ++c) {
-      const float sc = objp * (is_prob ? row[c] : expf(row[c] - mx) / sum);
+      const float sc = objp * row_score(row, c, sum, is_prob);
       if (!(sc > pc.sel_thr)) continue;
       const size_t list = (size_t)img * C + c;
       const int pos = atomicAdd(&counts[list * kCountStride], 1);
-      if (pos < cap) keys[list * cap + pos] = make_key(sc, (unsigned)(hd.anchor_base[layer] + local) * (unsigned)kMaxClasses + (unsigned)c);
+      if (pos < cap) keys[list * cap + pos] = make_key(sc, anchor * (unsigned)kMaxClasses + (unsigned)c);
     }
     return;
   }
   const int pos = atomicAdd(&counts[img * kCountStride], 1);
-  if (pos < cap) keys[(size_t)img * cap + pos] = make_key(best, (unsigned)(hd.anchor_base[layer] + local) * (unsigned)kMaxClasses + (unsigned)label);
+  if (pos < cap) keys[(size_t)img * cap + pos] = make_key(best, anchor * (unsigned)kMaxClasses + (unsigned)label);
 }
 
 constexpr int kEvalCand = 1024;     // NMS candidates of the ron_eval.py variant per pass: one thread each
@@ -1384,12 +1342,7 @@ __global__ __launch_bounds__(kTopkThreads) void eval_nms_kernel(HeadsDev hd, Eva
       const u64 k = lds.sort[tid];
       my_score = __uint_as_float((unsigned)(k >> 32));
       my_p = 0xFFFFFFFFu - (unsigned)(k & 0xFFFFFFFFull);
-      const int anchor = (int)(my_p / (unsigned)kMaxClasses);
-      int layer = 0;
-#pragma unroll
-      for (int l = 1; l < RON_MAX_LAYERS; ++l)
-        if (l < hd.num_layers && anchor >= hd.anchor_base[l]) layer = l;
-      eval_box(hd, pc, img, layer, anchor - hd.anchor_base[layer], my);
+      anchor_box(hd, pc, kClipRepair, img, (int)(my_p / (unsigned)kMaxClasses), my);
     }
     if (n > 0) below = lds.sort[n - 1];                                     // the next pass continues under this key
     __syncthreads();                                                        // every key is read before boxes overwrite the tail
@@ -1474,12 +1427,8 @@ __global__ __launch_bounds__(kTopkThreads) void eval_merge_kernel(HeadsDev hd, E
       all += wave_sum[w];
     }
     if (has && pos < out.capacity) {
-      int layer = 0;
-#pragma unroll
-      for (int l = 1; l < RON_MAX_LAYERS; ++l)
-        if (l < hd.num_layers && anchor >= hd.anchor_base[l]) layer = l;
       float b[4];
-      eval_box(hd, pc, img, layer, anchor - hd.anchor_base[layer], b);
+      anchor_box(hd, pc, kClipRepair, img, anchor, b);
       const size_t o = (size_t)img * out.capacity + pos;
       out.classes[o] = 255 - (int)(v & 0xFFull);
       out.scores[o] = __uint_as_float((unsigned)(v >> 8));
@@ -1563,15 +1512,10 @@ extern "C" int ron_bboxes_filter_min(const float* scores, const float* bboxes, i
   return RON_OK;
 }
 
-static int64_t eval_lists(const ron_heads* heads, int n, int nms_mode) { return (nms_mode & 4) ? (int64_t)n * heads->num_classes : (int64_t)n; }
-
-// workspace: [counters, one 128-byte line per list][keys: lists x anchors][nms_mode | 4: best, n x anchors]
 extern "C" int64_t ron_post_eval_workspace_bytes_mode(const ron_heads* heads, int n, int nms_mode) {
   HeadsDev hd;
   if (heads == nullptr || build_heads_dev(heads, &hd, false) != RON_OK || n <= 0) return -1;
-  const int64_t lists = eval_lists(heads, n, nms_mode);
-  return ron::align_up(lists * kCountStride * 4, 256) + lists * hd.anchor_base[RON_MAX_LAYERS] * 8 +
-         ((nms_mode & 4) ? (int64_t)n * hd.anchor_base[RON_MAX_LAYERS] * 8 : 0);
+  return eval_layout(n, hd.num_classes, hd.anchor_base[RON_MAX_LAYERS], nms_mode).bytes;
 }
 
 extern "C" int64_t ron_post_eval_workspace_bytes(const ron_heads* heads, int n) { return ron_post_eval_workspace_bytes_mode(heads, n, 0); }
@@ -1594,27 +1538,19 @@ extern "C" int ron_post_eval(const ron_heads* heads, int n, const float* min_siz
   for (int i = 0; i < hd.num_layers; ++i) RON_REQUIRE(hd.obj[i] != nullptr, "ron_post_eval needs the objectness tensors");
   DetDev d_out;
   if ((rc = to_det_dev(out, &d_out, cfg->keep_top_k, "out", false))) return rc;
-  const int64_t need = ron_post_eval_workspace_bytes_mode(heads, n, cfg->nms_mode);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)need);
+  const int cap = hd.anchor_base[RON_MAX_LAYERS];
+  const EvalLayout w = eval_layout(n, hd.num_classes, cap, cfg->nms_mode);
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= w.bytes, "workspace too small: %lld < %lld", (long long)workspace_bytes, (long long)w.bytes);
   EvalDev pc;
-  pc.obj_thr = cfg->objectness_thres; pc.sel_thr = cfg->select_threshold; pc.nms_thr = cfg->nms_threshold;
-  pc.keep_top_k = cfg->keep_top_k; pc.nms_mode = cfg->nms_mode; pc.flags = cfg->input_flags; pc.min_size = min_sizes;
-  for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->bbox_img[i]; pc.ps[i] = cfg->prior_scaling[i]; }
+  fill_core(&pc, cfg->objectness_thres, cfg->select_threshold, cfg->nms_threshold, cfg->bbox_img, cfg->prior_scaling, cfg->input_flags);
+  pc.keep_top_k = cfg->keep_top_k; pc.nms_mode = cfg->nms_mode; pc.min_size = min_sizes;
   hipStream_t s = (hipStream_t)stream;
   int* counts = (int*)workspace;
-  const int64_t lists = eval_lists(heads, n, cfg->nms_mode);
-  const int64_t cbytes = ron::align_up(lists * kCountStride * 4, 256);
-  u64* keys = (u64*)((char*)workspace + cbytes);
-  const int cap = hd.anchor_base[RON_MAX_LAYERS];
-  u64* best = per_class_lists ? keys + lists * cap : nullptr;
-  RON_HIP_CHECK(hipMemsetAsync(counts, 0, cbytes, s));
-  if (per_class_lists) RON_HIP_CHECK(hipMemsetAsync(best, 0, (size_t)n * cap * 8, s));
-  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
-  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
-    static ron::PerDeviceOnce once;
-    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&eval_select_kernel), (int)lds));
-  }
-  RON_LAUNCH(eval_select_kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys, counts, cap);
+  u64* keys = (u64*)((char*)workspace + w.cnt_bytes);
+  u64* best = per_class_lists ? (u64*)((char*)workspace + w.best_off) : nullptr;
+  RON_HIP_CHECK(hipMemsetAsync(counts, 0, w.cnt_bytes, s));
+  if (per_class_lists) RON_HIP_CHECK(hipMemsetAsync(best, 0, (size_t)w.best_bytes, s));
+  if ((rc = launch_select<eval_select_kernel>(hd, pc, n, keys, counts, cap, s)) != RON_OK) return rc;
   RON_LAUNCH(eval_nms_kernel, dim3(n, per_class_lists ? hd.num_classes : 1), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, d_out, best);
   if (per_class_lists) RON_LAUNCH(eval_merge_kernel, dim3(n), dim3(kTopkThreads), 0, s, hd, pc, best, cap, d_out);
   RON_HIP_CHECK(ron::launch_error());
@@ -1624,8 +1560,7 @@ extern "C" int ron_post_eval(const ron_heads* heads, int n, const float* min_siz
 extern "C" int64_t ron_post_tfe_workspace_bytes(const ron_heads* heads, int n) {
   HeadsDev hd;
   if (build_heads_dev(heads, &hd, false) != RON_OK || n <= 0) return -1;
-  const int64_t lists = (int64_t)n * (heads->num_classes - 1);
-  return ron::align_up(lists * 4, 256) + lists * hd.anchor_base[RON_MAX_LAYERS] * 8;
+  return tfe_layout((int64_t)n * (hd.num_classes - 1), hd.anchor_base[RON_MAX_LAYERS]).bytes;
 }
 
 int ron::tfe_cfg_check(const ron_tfe_cfg* cfg) {
@@ -1639,11 +1574,20 @@ int ron::tfe_cfg_check(const ron_tfe_cfg* cfg) {
 
 static TfeDev tfe_dev(const ron_tfe_cfg* cfg, unsigned flags) {
   TfeDev pc;
-  pc.obj_thr = cfg->objectness_thres; pc.sel_thr = cfg->select_threshold; pc.nms_thr = cfg->nms_threshold;
+  fill_core(&pc, cfg->objectness_thres, cfg->select_threshold, cfg->nms_threshold, cfg->clipping_bbox, cfg->prior_scaling, flags);
   pc.top_k = cfg->top_k; pc.keep_top_k = cfg->keep_top_k; pc.nms_mode = cfg->nms_mode; pc.clip = cfg->clip;
-  pc.min_size = cfg->min_size; pc.flags = flags;
-  for (int i = 0; i < 4; ++i) { pc.ref[i] = cfg->clipping_bbox[i]; pc.ps[i] = cfg->prior_scaling[i]; }
+  pc.min_size = cfg->min_size;
   return pc;
+}
+
+// select + per-class top-k / NMS of n images into (scores, bboxes); the counters are zero on entry
+static int tfe_launch(const HeadsDev& hd, const TfeDev& pc, int n, u64* keys, int* counts, float* scores, float* bboxes, hipStream_t s) {
+  const int cap = hd.anchor_base[RON_MAX_LAYERS];
+  const int rc = launch_select<tfe_select_kernel>(hd, pc, n, keys, counts, cap, s);
+  if (rc != RON_OK) return rc;
+  RON_LAUNCH(tfe_topk_nms_kernel, dim3(hd.num_classes - 1, n), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, scores, bboxes);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
 }
 
 extern "C" int ron_post_tfe(const ron_heads* heads, int n, const ron_tfe_cfg* cfg, void* workspace,
@@ -1654,27 +1598,13 @@ extern "C" int ron_post_tfe(const ron_heads* heads, int n, const ron_tfe_cfg* cf
   HeadsDev hd;
   rc = build_heads_dev(heads, &hd, (cfg->input_flags & RON_IN_LOC_DECODED) == 0);
   if (rc != RON_OK) return rc;
-  const int64_t need = ron_post_tfe_workspace_bytes(heads, n);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "workspace too small: %lld < %lld",
-              (long long)workspace_bytes, (long long)need);
-  const TfeDev pc = tfe_dev(cfg, cfg->input_flags);
+  const TfeLayout w = tfe_layout((int64_t)n * (hd.num_classes - 1), hd.anchor_base[RON_MAX_LAYERS]);
+  RON_REQUIRE(workspace != nullptr && workspace_bytes >= w.bytes, "workspace too small: %lld < %lld",
+              (long long)workspace_bytes, (long long)w.bytes);
   hipStream_t s = (hipStream_t)stream;
-  const int C1 = hd.num_classes - 1;
-  const int64_t lists = (int64_t)n * C1;
   int* counts = (int*)workspace;
-  u64* keys = (u64*)((char*)workspace + ron::align_up(lists * 4, 256));
-  const int cap = hd.anchor_base[RON_MAX_LAYERS];
-  RON_HIP_CHECK(hipMemsetAsync(counts, 0, ron::align_up(lists * 4, 256), s));
-  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
-  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
-    static ron::PerDeviceOnce once;
-    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&tfe_select_kernel), (int)lds));
-  }
-  RON_LAUNCH(tfe_select_kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys,
-                     counts, cap);
-  RON_LAUNCH(tfe_topk_nms_kernel, dim3(C1, n), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, scores, bboxes);
-  RON_HIP_CHECK(ron::launch_error());
-  return RON_OK;
+  RON_HIP_CHECK(hipMemsetAsync(counts, 0, w.cnt_bytes, s));
+  return tfe_launch(hd, tfe_dev(cfg, cfg->input_flags), n, (u64*)((char*)workspace + w.cnt_bytes), counts, scores, bboxes, s);
 }
 
 // ron_detect_tfe's post stage.  Workspace (the context's, sized by ron_post_np_workspace_bytes for max_batch):
@@ -1691,22 +1621,14 @@ int ron::post_tfe_ctx(const ron_heads* heads, int n, int max_batch, const ron_tf
   if ((rc = build_heads_dev(heads, &hd, true)) != RON_OK) return rc;
   const int C1 = hd.num_classes - 1;
   const int cap = hd.anchor_base[RON_MAX_LAYERS];
-  const int64_t np_cnt = 2 * ron::align_up((int64_t)np_clean_layout_images((int64_t)cap * C1, 1, workspace_bytes) * kCountStride * 4, 256);
-  const int64_t cnt_bytes = ron::align_up((int64_t)max_batch * C1 * 4, 256);
-  const int64_t need = np_cnt + cnt_bytes + (int64_t)max_batch * C1 * cap * 8;
-  RON_REQUIRE(workspace_bytes >= need, "ron_detect_tfe: workspace too small for the TF lists: %lld < %lld", (long long)workspace_bytes,
-              (long long)need);
+  // the np counters end where ron_detect's keys begin, in the layout ron_detect's self-cleaning workspace has
+  const int64_t np_cap = (int64_t)cap * C1;
+  const int64_t np_cnt = np_layout(np_cap, np_clean_layout_images(np_cap, 1, workspace_bytes)).keys_off;
+  const TfeLayout w = tfe_layout((int64_t)max_batch * C1, cap);
+  RON_REQUIRE(workspace_bytes >= np_cnt + w.bytes, "ron_detect_tfe: workspace too small for the TF lists: %lld < %lld",
+              (long long)workspace_bytes, (long long)(np_cnt + w.bytes));
   int* counts = (int*)((char*)workspace + np_cnt);
-  u64* keys = (u64*)((char*)workspace + np_cnt + cnt_bytes);
-  const TfeDev pc = tfe_dev(cfg, ron::kPostWsClean);     // raw heads: logits, objectness logit pairs, offsets
-  if (zero_counters) RON_HIP_CHECK(ron::dev_memset_async(counts, 0, (size_t)cnt_bytes, s));
-  const size_t lds = (size_t)kSelectThreads * hd.num_classes * sizeof(float);
-  if (lds > 48 * 1024) {          // beyond ~48 classes the staging tile needs the dynamic-LDS limit raised (128 classes: 128 KB of the CU's 160)
-    static ron::PerDeviceOnce once;
-    RON_HIP_CHECK(once.max_dynamic_lds(reinterpret_cast<const void*>(&tfe_select_raw_kernel), (int)lds));
-  }
-  RON_LAUNCH(tfe_select_raw_kernel, dim3(hd.block_base[RON_MAX_LAYERS], n), dim3(kSelectThreads), lds, s, hd, pc, keys, counts, cap);
-  RON_LAUNCH(tfe_topk_nms_kernel, dim3(C1, n), dim3(kTopkThreads), 0, s, hd, pc, keys, counts, cap, scores, bboxes);
-  RON_HIP_CHECK(ron::launch_error());
-  return RON_OK;
+  if (zero_counters) RON_HIP_CHECK(ron::dev_memset_async(counts, 0, (size_t)w.cnt_bytes, s));
+  // raw heads: logits, objectness logit pairs, offsets
+  return tfe_launch(hd, tfe_dev(cfg, ron::kPostWsClean), n, (u64*)((char*)workspace + np_cnt + w.cnt_bytes), counts, scores, bboxes, s);
 }

@@ -5,8 +5,8 @@
             detected_bboxes (ron_post_tfe)
   tfe     : RONNet.detect_tfe (ron_detect_tfe: forward + the same post-processing in one enqueue)
   np      : RONNet.detect (ron_detect, np_methods post-processing), for reference
-  post_raw: (not in the default set) ron_post_tfe alone on the raw heads of one forward (its own tfe_select_kernel applies softmax,
-            gate and decode): with a kernel trace, the select kernels of ron_post_tfe and ron_detect_tfe on the same heads
+  post_raw: (not in the default set) ron_post_tfe alone on the raw heads of one forward (tfe_select_kernel applies softmax, gate
+            and decode): with a kernel trace, the one TF select kernel as ron_post_tfe and as ron_detect_tfe launch it, same heads
 
 per variant (reducedfc / full), batch (1: the latency plan, 32) and regime: 'dense' = the synthetic weights as they are, 'biased'
 = the Conv2d_pred_3x3 background bias raised (+10 instead of +8) so that the lists are sparse, like a trained net's.  Each
