@@ -458,7 +458,7 @@ int run_backward(const ron_bn_desc* d, const BnPlan& P, const float* x, const fl
 }  // namespace ron
 
 extern "C" int64_t ron_batchnorm_workspace_bytes(const ron_bn_desc* d) {
-  ron::BnPlan P;
+  ron::BnPlan P = ron::BnPlan();
   if (ron::plan_bn("batchnorm", d, &P) != RON_OK) return -1;
   return P.total;
 }
@@ -468,7 +468,7 @@ extern "C" int ron_batchnorm_train_nhwc(const ron_bn_desc* d, const float* x, co
                                         void* stream) {
   using namespace ron;
   const char* what = "batchnorm forward";
-  BnPlan P;
+  BnPlan P = BnPlan();
   if (int rc = plan_bn(what, d, &P)) return rc;
   RON_REQUIRE(x != nullptr && gamma != nullptr && beta != nullptr && y != nullptr && mean != nullptr && var != nullptr,
               "%s: x, gamma, beta, y, mean and var must not be NULL", what);
@@ -491,7 +491,7 @@ extern "C" int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x,
                                            int64_t workspace_bytes, void* stream) {
   using namespace ron;
   const char* what = "batchnorm backward";
-  BnPlan P;
+  BnPlan P = BnPlan();
   if (int rc = plan_bn(what, d, &P)) return rc;
   RON_REQUIRE(x != nullptr && dy != nullptr && gamma != nullptr && mean != nullptr && var != nullptr,
               "%s: x, dy, gamma, mean and var must not be NULL", what);

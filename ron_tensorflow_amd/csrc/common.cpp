@@ -32,7 +32,29 @@ hipError_t dev_memset(void* p, int v, size_t bytes) {
   const hipError_t e = hipMemset(p, v, bytes);
   return e != hipSuccess ? e : hipStreamSynchronize(nullptr);
 }
-hipError_t dev_memset_async(void* p, int v, size_t bytes, hipStream_t s) { return plan_only() ? hipSuccess : hipMemsetAsync(p, v, bytes, s); }
+FILE* plan_trace() {
+  static FILE* const f = [] {
+    const char* path = plan_only() ? getenv("RON_PLAN_TRACE") : nullptr;
+    FILE* t = path != nullptr ? fopen(path, "a") : nullptr;
+    if (t != nullptr) setvbuf(t, nullptr, _IOLBF, 0);      // whole lines: the sweep appends its headings to the same file
+    return t;
+  }();
+  return f;
+}
+void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t lds, int nargs, const size_t* sizes, const uint32_t* crcs) {
+  std::string line = kernel;
+  char buf[96];
+  snprintf(buf, sizeof buf, " grid %u %u %u block %u %u %u lds %zu args", grid.x, grid.y, grid.z, block.x, block.y, block.z, lds);
+  line += buf;
+  for (int i = 0; i < nargs; ++i) { snprintf(buf, sizeof buf, " %zu:%08x", sizes[i], crcs[i]); line += buf; }
+  fprintf(plan_trace(), "%s\n", line.c_str());
+}
+hipError_t dev_memset_async(void* p, int v, size_t bytes, hipStream_t s) {
+  if (!plan_only()) return hipMemsetAsync(p, v, bytes, s);
+  if (plan_trace()) fprintf(plan_trace(), "memset %p value %d bytes %zu\n", p, v, bytes);
+  return hipSuccess;
+}
+hipError_t dev_stream_sync(hipStream_t s) { return plan_only() ? hipSuccess : hipStreamSynchronize(s); }
 hipError_t dev_memcpy(void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
   return plan_only() ? hipSuccess : hipMemcpy(dst, src, bytes, kind);
 }

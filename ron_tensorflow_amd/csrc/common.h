@@ -72,9 +72,24 @@ using DevBuf = Owned<void*, dev_free>;
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using Event = Owned<hipEvent_t, hipEventDestroy>;
 hipError_t dev_upload(DevBuf* b, const void* host, size_t bytes);      // a new allocation of `bytes` bytes holding the host data
-#define RON_LAUNCH(...)                                          \
-  do {                                                           \
-    if (!ron::plan_only()) hipLaunchKernelGGL(__VA_ARGS__);      \
+hipError_t dev_stream_sync(hipStream_t s);
+
+// Launch trace of the dry run (RON_PLAN_TRACE=<file> beside RON_PLAN_ONLY=1): one line per skipped launch - the kernel as spelled at
+// the RON_LAUNCH site, grid, block, dynamic LDS bytes and, per by-value argument, its size and the CRC32C of its bytes - and one per
+// dev_memset_async.  Two trees whose traces are equal launch the same kernels with the same arguments (tools/plan_sweep.cpp,
+// tests/test_plan_trace_cpu.py).  Nothing is evaluated outside the dry run.
+FILE* plan_trace();      // the open trace file (appended to, line-buffered), or null
+void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t lds, int nargs, const size_t* sizes, const uint32_t* crcs);
+template <class... A>
+void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t, const A&... args) {
+  const size_t sizes[] = {sizeof(A)..., 0};
+  const uint32_t crcs[] = {ron_crc32c(&args, sizeof(A), 0)..., 0};
+  trace_launch(kernel, grid, block, lds, (int)sizeof...(A), sizes, crcs);
+}
+#define RON_LAUNCH(kernel, ...)                                                  \
+  do {                                                                           \
+    if (!ron::plan_only()) hipLaunchKernelGGL(kernel, __VA_ARGS__);              \
+    else if (ron::plan_trace()) ron::trace_launch(#kernel, __VA_ARGS__);         \
   } while (0)
 
 // hipFuncSetAttribute applies to the current device only: one of these per kernel instantiation remembers on which

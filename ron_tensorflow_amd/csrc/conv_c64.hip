@@ -259,7 +259,7 @@ bool conv_c64_applicable(const ConvLaunch& c) {
 int launch_conv_c64(const ConvLaunch& c, hipStream_t stream) {
   RON_REQUIRE(conv_c64_applicable(c), "resident-weight kernel: 3x3 / stride 1 / pad 1 on a 64-channel bf16 / f16 map whose size the 8 x 32 tile "
               "divides, 64 / 128 / 256 outputs, tensors < 2 GiB, packed weight image present");
-  C64Args a;
+  C64Args a = C64Args();
   a.in = c.in.base; a.in_bytes = (unsigned)c.in.bytes;
   a.in_Hp = c.in.Hp(); a.in_Wp = c.in.Wp(); a.in_pad = c.in.pad;
   a.wimg = (const u32x4*)c.wgt_c64; a.bias = c.bias;

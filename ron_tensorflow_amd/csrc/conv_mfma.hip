@@ -86,7 +86,38 @@ int check_conv_desc(const ron_conv_desc* d) {
   return RON_OK;
 }
 
+// ---- the planner: everything the host decides about a row-gather launch, each rule in one place ------------------------------------
+//   tile_of / ConvGeom   tile shapes (rows, columns, slots of the chip, K-step cost); M, K, KT, taps and tile counts of a ConvLaunch
+//   conv_pick_cfg        the tile configuration of a launch of its own; single_splitk: its split factor (launching and sizing both ask)
+//   taps_inner_rule      the K order
+//   plan_member          ONE convolution on a given tile: checks, kernel arguments, tile counts, split, tile order, pos_major, K order,
+//                        224-column form - for a launch of its own (plan_conv) and for each member of a group (launch_conv_group)
+//   with_traits          dtype -> traits class of the kernels
 static bool igemm_is256(int cfg) { return cfg == kCfgIgemm256 || cfg == kCfgIgemm256TapsInner; }
+
+// Tile of a row-gather configuration: BM x BN, the workgroups of it the chip holds at once (256 CUs; 64 KB of LDS lets two share a
+// CU) and what a K step of a workgroup costs with the slots full - the schedule model of a group (measured, tools/_tune in HISTORY.md;
+// 0: no grouped form, never measured).  The configurations with kernels of their own, and numbers out of range until plan_conv refuses
+// them, read as the 128 x 128 tile: conv_scratch_bytes has always sized kCfgC64Resident that way (the kernel never splits; no reason
+// found, kept so that no allocation changes).
+struct Tile { int bm, bn, slots; double step_us; };
+static const Tile& tile_of(int cfg) {
+  static const Tile t256 = {256, 256, 256, 1.4}, t128 = {128, 128, 512, 1.15}, t128x64 = {128, 64, 512, 0.75}, t256x128 = {256, 128, 256, 0.0};
+  if (igemm_is256(cfg)) return t256;
+  return cfg == kCfgIgemm128x64 ? t128x64 : (cfg == kCfgIgemm256x128 ? t256x128 : t128);
+}
+
+struct ConvGeom {
+  int M, taps, K, KT, Npad, n_long;      // GEMM rows (un-pooled), filter taps, K in elements and in steps, columns, the long ones (center_from)
+  explicit ConvGeom(const ConvLaunch& c)
+      : M(c.in.N * c.Ho * c.Wo), taps(c.kh * c.kw), K(taps * c.in.C), KT(K / conv_k_chunk(c.dtype)), Npad(c.Npad),
+        n_long(c.center_from > 0 ? c.center_from : c.Npad) {}
+  int rows(const Tile& t) const { return (M + t.bm - 1) / t.bm; }
+  int cols(const Tile& t) const { return Npad / t.bn; }
+  int long_cols(const Tile& t) const { return n_long / t.bn; }      // centre-tap-only columns: the tiles that run every tap
+  int tiles(const Tile& t) const { return rows(t) * cols(t); }
+};
+static int64_t slab_bytes(const ConvLaunch& c, int sk) { return (int64_t)sk * ConvGeom(c).M * c.Npad * 4; }      // fp32 slabs of sk K slices
 
 // The 256 x 224 form of the four-wave 256 x 256 tile: a plain bf16 / f16 convolution of 193 .. 224 output channels in one column
 // tile (the class-prediction heads: Cout = 210, 46 of 256 columns padding) runs 8 x 7 blocks per wave instead of 8 x 8: an eighth
@@ -99,17 +130,12 @@ static bool conv_takes_224(const ConvLaunch& c, int steps_per_wg) {
   return c.n224 != 0 && dtype_is_half(c.dtype) && c.Npad == 256 && c.Cout > 192 && c.Cout <= 224 && c.up == 0 && !c.pool && c.center_from == 0 &&
          c.split_n == 0 && c.out2.base == nullptr && asm_loop_ok(steps_per_wg);
 }
-static int igemm_bm(int cfg) { return (igemm_is256(cfg) || cfg == kCfgIgemm256x128) ? 256 : 128; }
-static int igemm_bn(int cfg) { return igemm_is256(cfg) ? 256 : (cfg == kCfgIgemm128x64 ? 64 : 128); }
-// workgroups of a configuration the chip holds at once (256 CUs; 64 KB of LDS lets two share a CU)
-static int igemm_slots(int cfg) { return (igemm_is256(cfg) || cfg == kCfgIgemm256x128) ? 256 : 512; }
 
 // Split-K factor for grids that leave most CUs idle: such launches are a serial chain of KT dependent
 // HBM round trips per workgroup, so the K loop is spread over enough workgroups to fill the chip (>= 8 steps each).
 int conv_pick_splitk(int tiles, int KT, int slots, int tile_elems) {
   if (tiles < 1 || tiles * 2 > slots || KT < 16) return 1;
-  int sk = slots / tiles;
-  int min_steps = 8;
+  int sk = slots / tiles, min_steps = 8;
   if (sk > KT / min_steps) sk = KT / min_steps;
   if (sk <= 1) return 1;
   // A split launch pays a second launch and writes, then reads, sk fp32 copies of its output: with many rows and a short K that
@@ -119,7 +145,7 @@ int conv_pick_splitk(int tiles, int KT, int slots, int tile_elems) {
   // SSD-512 batch 1 0.697 -> 0.685 ms, batch 4 1.157 -> 1.147, RON and the batch-16 / 32 / 64 benchmark configurations unchanged.
   static const bool veto = getenv("RON_SPLITK_NO_VETO") == nullptr;
   if (veto) {
-    const double step_us = 1.1, launch_us = 5.0, bytes_per_us = 4e6;
+    const double step_us = 1.1, launch_us = 5.0, bytes_per_us = 4e6;      // (a lone launch, slots not full: not Tile::step_us)
     const double tile_bytes = 4.0 * tile_elems;       // fp32 slab of one tile (BM x BN of the configuration: 256 x 128 is half of 256 x 256)
     const double t_split = ((KT + sk - 1) / sk) * step_us + launch_us + 2.0 * sk * tiles * tile_bytes / bytes_per_us;
     if (t_split >= KT * step_us) return 1;
@@ -127,7 +153,13 @@ int conv_pick_splitk(int tiles, int KT, int slots, int tile_elems) {
   return sk;
 }
 
-constexpr int kAsmLoopMaxStepsHost = detail::kAsmLoopMaxSteps;
+// The split factor of a launch of its own on `cfg`: the caller's, else by the grid.  plan_conv launches with it and conv_scratch_bytes
+// sizes the slabs by it, so the two cannot disagree.  (A fused pool or transposed conv of its own never splits, whatever this says: plan_member.)
+static int single_splitk(const ConvLaunch& c, int cfg) {
+  const Tile& t = tile_of(cfg);
+  const ConvGeom g(c);
+  return c.splitk >= 0 ? c.splitk : conv_pick_splitk(g.tiles(t), g.KT, t.slots, t.bm * t.bn);
+}
 
 // Default tile of the row-gather kernel, from tools/sweep_conv.py on MI355X at batch 32 (profiles/r01/sweep_*.txt).
 // The 256x256 tile wins once it yields >= ~160 workgroups; below that the grid is the problem and the 128x128 /
@@ -159,14 +191,16 @@ int conv_pick_igemm_cfg(int M, int Npad, int taps, int K, bool may_split) {
 // 16 column tiles of 12.8 MB of weights each - N fastest makes every XCD stream all 205 MB: 1.66 GB fetched per launch, 0.65 GB
 // M fastest, 566 -> 541 us; fc7 113 -> 102 us).  Forced on every launch it costs the activation-heavy layers 2-4 %; walking the
 // column tiles of an XCD's rows in blocks of 1-3 instead changed nothing (both measured, not kept).
+// `tiles_m`: the row tiles of the launch (a fused pool's rows are not ConvGeom's).
 constexpr int kPanelCols = 8;      // the panel width of wide and tall launches (plain GEMM shapes)
-static int pick_m_fastest(const ConvLaunch& c, int BM, int BN, int tiles_m, int tiles_n, int splitk, int panel_steps) {
+static int pick_m_fastest(const ConvLaunch& c, const Tile& t, int tiles_m, int splitk, int panel_steps) {
+  const ConvGeom g(c);
+  const int tiles_n = g.cols(t), cols = g.long_cols(t);      // (centre-tap-only columns: panels among the long ones)
   // split-K: the workgroups of one K slice are consecutive, an XCD's run then covers (nearly) every tile of its slices either way
   if (tiles_m < 2 || tiles_n < 2 || splitk > 1) return 0;
   const double esz = (double)dtype_size(c.dtype);
-  const int taps = c.kh * c.kw;
-  const double a_tile = (double)BM * c.in.C * esz * (c.stride > 1 ? taps : (taps > 1 ? 2 : 1));   // unique input bytes of a row tile
-  const double b_tile = (double)BN * taps * c.in.C * esz;
+  const double a_tile = (double)t.bm * c.in.C * esz * (c.stride > 1 ? g.taps : (g.taps > 1 ? 2 : 1));   // unique input bytes of a row tile
+  const double b_tile = (double)t.bn * g.K * esz;
   const int per_xcd = std::max(1, tiles_m * tiles_n / 8);
   const double cost_n = (per_xcd / tiles_n + 1) * a_tile + std::min(tiles_n, per_xcd) * b_tile;
   const double cost_m = std::min(tiles_m, per_xcd) * a_tile + (per_xcd / tiles_m + 1) * b_tile;
@@ -175,12 +209,12 @@ static int pick_m_fastest(const ConvLaunch& c, int BM, int BN, int tiles_m, int 
   // batch 4: the groups that carry block4 / block5_deconv_right 8-10 us slower in panel order)
   // Only the four-wave tiles decode it (conv_igemm_tile): `panel_steps` = the K steps of a workgroup when the launch may go to
   // them, 0 when it may not (members of a grouped launch).
-  const bool panels_ok = BM == 256 && c.dtype != RON_DTYPE_F32 && panel_steps > 0 && asm_loop_ok(panel_steps) && c.up == 0;
+  const bool panels_ok = t.bm == 256 && c.dtype != RON_DTYPE_F32 && panel_steps > 0 && asm_loop_ok(panel_steps) && c.up == 0;
   // experiments (tools/experiments/r06_calls/r06_panels.sh): RON_PANEL_COLS = P forces panels of P column tiles on every launch that
   // can decode them (P = 1: row tiles fastest, 0: column tiles fastest)
   static const char* force = getenv("RON_PANEL_COLS");
   if (force != nullptr && panels_ok) {
-    const int P = atoi(force), cols = c.center_from > 0 ? c.center_from / BN : tiles_n;     // (centre-tap-only columns: panels among the long ones)
+    const int P = atoi(force);
     return P >= cols ? 0 : P;
   }
   int pick = cost_m < 0.95 * cost_n ? 1 : 0;
@@ -198,9 +232,8 @@ static int pick_m_fastest(const ConvLaunch& c, int BM, int BN, int tiles_m, int 
   // these launches are not short of fabric bandwidth, and the bytes saved did not come back as clock either - the choice is made for the
   // traffic alone, and only where the model sees a clear difference.  A row tile's unique input lines: ~1.3 x its own rows for a 3 x 3
   // filter on these maps (the halo rows), not the 2 x of the column / row estimate above.
-  const int cols = c.center_from > 0 ? c.center_from / BN : tiles_n;
   if (panels_ok && cols >= 3) {
-    const double a_round = (double)BM * c.in.C * esz * (c.stride > 1 ? taps : (taps > 1 ? 1.3 : 1.0));
+    const double a_round = (double)t.bm * c.in.C * esz * (c.stride > 1 ? g.taps : (g.taps > 1 ? 1.3 : 1.0));
     const int resident = std::min(32, std::max(1, tiles_m * cols / 8));
     auto per_round = [&](int P) {
       P = std::max(1, std::min(P, cols));
@@ -211,8 +244,8 @@ static int pick_m_fastest(const ConvLaunch& c, int BM, int BN, int tiles_m, int 
     double best_cost = now;
     for (int P : {2, 3, 4, 8}) {
       if (P >= cols) break;
-      const double t = per_round(P);
-      if (t < 0.95 * best_cost) { best = P; best_cost = t; }
+      const double t_round = per_round(P);
+      if (t_round < 0.95 * best_cost) { best = P; best_cost = t_round; }
     }
     if (best_cost < 0.95 * now) pick = best;
   }
@@ -223,12 +256,12 @@ static int pick_m_fastest(const ConvLaunch& c, int BM, int BN, int tiles_m, int 
 // launch executes drop by >= 5 % (fc6 7x7 on 10 x 10: 91 -> 77 filter rows over its 13 row tiles; conv6 of SSD-512, rate 6).
 // Only the tap-major K order (a skipped filter row is a contiguous K range), no fused pool / transposed conv; split-K slices
 // share what is left of a tile's K range.
-static int pick_pos_major(const ConvLaunch& c, int cfg, int BM) {
+static int pick_pos_major(const ConvLaunch& c, int cfg) {
   if (!c.halo_skip || c.pool || c.up > 0 || c.kh < 2 || conv_cfg_taps_inner(cfg)) return 0;
   // at most (kh - 1) * dil of a map's H output rows can skip anything: below 5 % there is nothing to decide (and no per-tile walk
   // over the thousands of tiles of a large map on the launch path)
   if ((c.kh - 1) * c.dil * 20 < c.in.H) return 0;
-  const int M = c.in.N * c.Ho * c.Wo, tiles_m = (M + BM - 1) / BM;
+  const int BM = tile_of(cfg).bm, M = ConvGeom(c).M, tiles_m = ConvGeom(c).rows(tile_of(cfg));
   long long rows_all = 0, rows_kept = 0;
   for (int t = 0; t < tiles_m; ++t) {
     const int oy_lo = (t * BM / c.in.N) / c.Wo, oy_hi = ((std::min(M, (t + 1) * BM) - 1) / c.in.N) / c.Wo;
@@ -241,9 +274,24 @@ static int pick_pos_major(const ConvLaunch& c, int cfg, int BM) {
   return rows_kept * 100 <= rows_all * 95 ? 1 : 0;
 }
 
+// The K order: taps innermost (consecutive steps re-read almost the same input lines) for stride-1 filters that neither split K nor
+// skip filter rows - only for the stride-1 convolutions it has been measured and tested on (the stride-2 3x3 convolutions of SSD-512's
+// extra blocks keep the tap-major order); with split-K it loses (conv5_1 at batch 4 +10 %).  Centre-tap-only column tiles of such a
+// launch keep the tap-major walk of their one tap.
+// `splits` is an argument because the callers do not mean the same by it.  conv_pick_cfg chooses between a configuration and its
+// taps-innermost twin before any split is applied: it passes the split the PLANNER would choose (none on the 256 x 256 tile, which is
+// picked for grids that fill the chip) and a factor the caller forces does not count - a test or sweep that forces a factor on
+// kCfgIgemm256TapsInner / kCfgIgemm128EarlyTapsInner runs that order split.  plan_member, for the tiles without a twin, passes the
+// split it applied, forced or not.  No reason for the difference is recorded anywhere; both answers are kept as they were.
+// (Both are callables: conv_pick_cfg runs for every launch ron_forward enqueues, and neither is worked out where the cheap clauses decide.)
+template <class S, class R>
+static bool taps_inner_rule(const ConvLaunch& c, S splits, R skips_rows) {
+  return c.kh * c.kw > 1 && c.up == 0 && c.stride == 1 && !splits() && !skips_rows();
+}
+
 // The halo-patch kernel (conv_patch.hip) where it applies and wins (conv_patch_pick), else the row-gather kernel.
 int conv_pick_cfg(const ConvLaunch& c) {
-  const int M = c.in.N * c.Ho * c.Wo;
+  const ConvGeom g(c);
   if (c.split_n == 0 && conv_c64_applicable(c)) return kCfgC64Resident;
   if (c.out2.base == nullptr && conv_patch_applicable(c)) {
     const int cfg = conv_patch_pick(c);
@@ -251,17 +299,17 @@ int conv_pick_cfg(const ConvLaunch& c) {
   }
   // centre-tap-only columns are a ninth of a column's work: the grid that has to fill the chip is the long columns'
   // (split K: not with a fused pool / transposed conv, and a launch with centre-tap-only columns counts those tiles too)
-  const bool may_split = c.center_from == 0 && !c.pool && c.up == 0 && c.splitk < 0;      // (the same answer when the scratch is being sized)
-  const int KT = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
+  const bool may_split = c.center_from == 0 && !c.pool && c.up == 0 && c.splitk < 0;
+  const int t256x128 = g.tiles(tile_of(kCfgIgemm256x128));
   // Cout = 128 (conv2_x) on maps large enough to fill the chip with 256 x 128 tiles: the four-wave assembly loop at 48 KB staged per
   // K step instead of two 128 x 128 workgroups per CU at 64 KB (sweep: profiles/r05/sweep_256x128.txt)
-  if (c.dtype != RON_DTYPE_F32 && c.Npad % 256 == 128 && c.center_from == 0 && c.up == 0 && c.out2.base == nullptr &&
-      ((M + 255) / 256) * (c.Npad / 128) >= 256 && KT <= kAsmLoopMaxStepsHost && asm_loop_ok(KT))
+  if (c.dtype != RON_DTYPE_F32 && c.Npad % 256 == 128 && c.center_from == 0 && c.up == 0 && c.out2.base == nullptr && t256x128 >= 256 &&
+      asm_loop_ok(g.KT))
     return kCfgIgemm256x128;
-  const int cfg = conv_pick_igemm_cfg(M, c.center_from > 0 ? c.center_from : c.Npad, c.kh * c.kw, c.kh * c.kw * c.in.C, may_split);
-  // taps innermost: only for the stride-1 convolutions it has been measured and tested on (the stride-2 3x3 convolutions of SSD-512's
-  // extra blocks keep the tap-major order).  Centre-tap-only column tiles of such a launch keep the tap-major walk of their one tap.
-  if (cfg == kCfgIgemm256TapsInner && (c.stride != 1 || pick_pos_major(c, kCfgIgemm256, 256))) return kCfgIgemm256;
+  const int cfg = conv_pick_igemm_cfg(g.M, g.n_long, g.taps, g.K, may_split);
+  // (taps innermost on 256 x 256 is taken back where skipping halo filter rows is worth more: conv_pick_igemm_cfg)
+  const auto skips_rows = [&](int on) { return [&c, on] { return pick_pos_major(c, on) != 0; }; };
+  if (cfg == kCfgIgemm256TapsInner && !taps_inner_rule(c, [] { return false; }, skips_rows(kCfgIgemm256))) return kCfgIgemm256;
   if (cfg == kCfgIgemm128Early && c.dtype != RON_DTYPE_F32 && c.center_from == 0) {
     // Where 256 x 256 tiles would leave most CUs idle (and K is not long enough to split them, above) the fallback used to be the
     // 128-row tiles: two workgroups per CU, twice the staged bytes per MAC.  Every tile configuration against this function's choice,
@@ -269,91 +317,87 @@ int conv_pick_cfg(const ConvLaunch& c) {
     // the 256 x 128 four-wave tile where it makes the launch about ONE round of the chip (48 .. 287 tiles; below 129 with K split in
     //    two): conv5_x at batch 32 / conv4_x at 8 / conv3_x at 4 75 -> 55 us (200 tiles), fc7 at batch 16 65 -> 51 (224); from 288
     //    (= 144 tiles of 256 x 256) on that tile wins by 13-17 %, below ~48 the launch is latency either way;
-    const int t = ((M + 255) / 256) * (c.Npad / 128);
-    if (c.up == 0 && KT <= kAsmLoopMaxStepsHost && asm_loop_ok(KT) && t >= 48 && t < 288) return kCfgIgemm256x128;
+    if (c.up == 0 && asm_loop_ok(g.KT) && t256x128 >= 48 && t256x128 < 288) return kCfgIgemm256x128;
     // (The 128 x 64 tile for the smallest launches - SSD-512's tail convolutions 13.5 -> 11.5 us stand-alone - was tried as a third
     // rule: SSD-512 batch 1 -0.8 %, RON batch 2 +0.6 %; not kept.)
   }
-  if (cfg == kCfgIgemm128Early && c.kh * c.kw > 1 && c.up == 0 && c.stride == 1) {
-    // taps innermost for the 128 x 128 tile too (consecutive steps re-read almost the same input lines): 3-6 % on launches that do
-    // not split K (with split-K it loses: conv5_1 at batch 4 +10 %), and where no filter rows can be skipped instead
-    const int tiles = ((M + 127) / 128) * (c.Npad / 128);
-    const bool splits = may_split && conv_pick_splitk(tiles, KT, igemm_slots(kCfgIgemm128Early), 128 * 128) > 1;
-    if (!splits && !pick_pos_major(c, kCfgIgemm128Early, 128)) return kCfgIgemm128EarlyTapsInner;
+  if (cfg == kCfgIgemm128Early) {
+    // taps innermost for the 128 x 128 tile too: 3-6 % on launches that do not split K, and where no filter rows can be skipped instead
+    const auto splits = [&] { return may_split && single_splitk(c, kCfgIgemm128Early) > 1; };
+    if (taps_inner_rule(c, splits, skips_rows(kCfgIgemm128Early))) return kCfgIgemm128EarlyTapsInner;
   }
   return cfg;
 }
 
-// Everything launch_conv decides before it launches: the tile configuration, the kernel arguments (split-K, tile order, K order) and
-// the width of the row-gather kernel's column tile (the configuration's own, or 224: conv_takes_224; 0 for the other kernels).
-static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out, int* bn_out);
-
-int conv_describe(const ConvLaunch& c, int out[4], int* n_tile) {
-  int cfg = -1, bn = 0;
-  ConvArgs a = ConvArgs();
-  const int rc = plan_conv(c, &cfg, &a, &bn);
-  if (rc != RON_OK) return rc;
-  if (n_tile != nullptr) *n_tile = bn;
-  out[0] = cfg;
-  const bool gather = !conv_cfg_is_patch(cfg) && cfg != kCfgC64Resident;
-  out[1] = gather ? a.splitk : 1; out[2] = gather ? a.m_fastest : 0; out[3] = gather ? a.taps_inner : 0;
+// ONE convolution on tile configuration `cfg` (a row-gather one): the requirement checks (`who` starts their messages; the caller has
+// run check_conv_fields), the kernel arguments, tile counts, the split into `sk` K slices if `slab` (`slab_bytes`) holds their fp32
+// sums, tile order, pos_major, K order, and *bn: the width of the column tile (the configuration's own, or 224: conv_takes_224).
+// `four_wave`: the launch may go to the four-wave tiles (which decode panel tile orders and have the 224-column form) - a launch of its
+// own always may, a group when every member's K chain fits their step table.
+// `grouped`: a member of a group.  Two rules differ there, both because a group has one kernel per tile and not the twins a launch of
+// its own chooses between: the K order of the 128 x 128 and 256 x 256 tiles comes from taps_inner_rule and not from the configuration;
+// and a split factor the planner chose does not keep a member off the 224-column form.  As before, a transposed member is split when
+// its factor says so (conv_group_scratch_bytes sizes that slab; group_splitks gives such members 1) and may have centre-tap-only columns.
+static int plan_member(const char* who, const ConvLaunch& c, int cfg, int sk, void* slab, int64_t slab_size, bool four_wave, bool grouped,
+                       ConvArgs& a, int* bn) {
+  const Tile& t = tile_of(cfg);
+  const ConvGeom g(c);
+  const int chunk = conv_k_chunk(c.dtype);
+  RON_REQUIRE(c.in.C % chunk == 0, "%s: Cin %d is not a multiple of the K chunk %d", who, c.in.C, chunk);
+  RON_REQUIRE(c.in.pad >= c.cpad, "%s: input halo %d < conv padding %d", who, c.in.pad, c.cpad);
+  RON_REQUIRE(c.in.bytes > 0 && c.in.bytes < (int64_t)1 << 32, "%s: input allocation must be < 4 GiB for buffer addressing", who);
+  RON_REQUIRE(c.wgt_bytes > 0 && c.wgt_bytes < (int64_t)1 << 32, "%s: weight allocation must be < 4 GiB", who);
+  RON_REQUIRE(c.out.pixels() * c.out.cstride < (int64_t)1 << 31, "%s: output too large for 32-bit offsets", who);
+  RON_REQUIRE(c.Npad % t.bn == 0, "%s: Npad %d not a multiple of the N tile %d", who, c.Npad, t.bn);
+  if (c.up > 0) RON_REQUIRE(c.up_cout % t.bn == 0, "transposed conv: channels per tap %d not a multiple of %d", c.up_cout, t.bn);
+  if (c.center_from > 0)
+    RON_REQUIRE(c.center_from % t.bn == 0 && (c.kh & 1) && (c.kw & 1) && (grouped || c.up == 0),
+                "%s: centre-tap-only columns need an odd filter and a boundary on the N tile (%d)", who, t.bn);
+  RON_REQUIRE((int64_t)c.Npad * g.K * (int)dtype_size(c.dtype) == c.wgt_bytes, "%s: packed weight size mismatch", who);
+  fill_conv_args(c, &a);
+  // SAME pool (plan_conv has checked the views): tile rows are the windows' four positions, ceil(Ho / 2) x ceil(Wo / 2) windows per
+  // image (an odd map's last windows hold positions that are no pixel: conv_igemm_tile)
+  if (c.pool) a.M = 4 * c.in.N * c.out.H * c.out.W;
+  a.tiles_n = g.cols(t);
+  a.tiles_total = ((a.M + t.bm - 1) / t.bm) * a.tiles_n;
+  if (sk > 1 && (grouped || (c.up == 0 && !c.pool)) && slab != nullptr && slab_bytes(c, sk) <= slab_size) {
+    a.kt_split = (a.KT + sk - 1) / sk;
+    a.splitk = (a.KT + a.kt_split - 1) / a.kt_split;      // no empty split
+    a.partial = static_cast<float*>(slab);
+    if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
+  }
+  const int tile_order = pick_m_fastest(c, t, a.tiles_total / a.tiles_n, a.splitk, four_wave ? a.kt_split : 0);
+  RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "%s: tile order %d: 0 .. %d", who, tile_order, kConvMaxTileOrder);
+  a.m_fastest = tile_order;
+  a.pos_major = pick_pos_major(c, cfg);
+  // K order: the configuration's where it names one; by the rule on the 256 x 128 tile and, in a group, on the 128 x 128 tile and on the
+  // 256 x 256 tile where the long columns are at most two tiles wide (what conv_pick_igemm_cfg asks of a launch of its own)
+  const bool by_rule = cfg == kCfgIgemm256x128 || (grouped && (cfg == kCfgIgemm128 || (cfg == kCfgIgemm256 && g.n_long <= kTapsInnerMaxN)));
+  const bool by_rule_inner = by_rule && taps_inner_rule(c, [&] { return a.splitk > 1; }, [&] { return a.pos_major != 0; });
+  a.taps_inner = (conv_cfg_taps_inner(cfg) || by_rule_inner) ? 1 : 0;
+  // 193 .. 224 output channels on the four-wave 256 x 256 tile: its 224-column form.  A split factor plan_conv chose itself keeps the
+  // 256 columns: those are the launches of fewer than 129 tiles (block4_cls_pred below batch 24), which nobody has measured on the
+  // narrower tile; a factor the caller forces (single-operator entry points, the sweep) does not stand in the way.
+  const bool split_allows = grouped || a.splitk == 1 || c.splitk >= 0;
+  *bn = (four_wave && igemm_is256(cfg) && split_allows && conv_takes_224(c, a.kt_split)) ? 224 : t.bn;
   return RON_OK;
 }
 
-int launch_conv(const ConvLaunch& c, hipStream_t stream) {
-  int cfg = -1, bn = 0;
-  ConvArgs a = ConvArgs();
-  int rc = plan_conv(c, &cfg, &a, &bn);
-  if (rc != RON_OK) return rc;
-  if (conv_cfg_is_patch(cfg)) return launch_conv_patch(c, cfg, stream);
-  if (cfg == kCfgC64Resident) return launch_conv_c64(c, stream);
-  if (c.dtype == RON_DTYPE_BF16) rc = launch_cfg<TraitsBF16S>(cfg, bn, a, stream);
-  else if (c.dtype == RON_DTYPE_F16) rc = launch_cfg<TraitsF16S>(cfg, bn, a, stream);
-  else if (c.dtype == RON_DTYPE_F32) rc = launch_cfg<TraitsF32S>(cfg, bn, a, stream);
-  else if (c.dtype == RON_DTYPE_F16X3) rc = launch_cfg<TraitsF16X3S>(cfg, bn, a, stream);
-  else { ron::set_error("conv: unknown dtype %d", c.dtype); return RON_ERR_INVALID; }
-  if (rc != RON_OK || a.splitk == 1) return rc;
-  if (c.dtype == RON_DTYPE_BF16) return launch_finalize<TraitsBF16S>(a, stream);
-  if (c.dtype == RON_DTYPE_F16) return launch_finalize<TraitsF16S>(a, stream);
-  if (c.dtype == RON_DTYPE_F16X3) return launch_finalize<TraitsF16X3S>(a, stream);
-  return launch_finalize<TraitsF32S>(a, stream);
-}
-
-static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out, int* bn_out) {
-  ConvArgs& a = *a_out;
-  *bn_out = 0;
-  {
-    const int rc = check_conv_fields(c);      // before the pickers divide by any of it
-    if (rc != RON_OK) return rc;
-  }
-  int cfg = c.cfg >= 0 ? c.cfg : conv_pick_cfg(c);
+// Everything launch_conv decides before it launches: the tile configuration, the kernel arguments (plan_member) and the width of the
+// row-gather kernel's column tile (0 for the other kernels).
+static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a, int* bn) {
+  *bn = 0;
+  if (const int rc = check_conv_fields(c)) return rc;      // before the pickers divide by any of it
+  const int cfg = c.cfg >= 0 ? c.cfg : conv_pick_cfg(c);
   *cfg_out = cfg;
   RON_REQUIRE(cfg >= 0 && cfg < kNumCfgs, "conv: tile config %d out of range [0, %d)", cfg, kNumCfgs);
   if (conv_cfg_is_patch(cfg) || cfg == kCfgC64Resident) return RON_OK;      // kernels of their own: nothing more to plan here
   RON_REQUIRE(!conv_cfg_taps_inner(cfg) || c.up == 0, "conv: the taps-innermost order is for plain convolutions");
-  const int esz = (int)dtype_size(c.dtype);
-  const int chunk = conv_k_chunk(c.dtype);
-  RON_REQUIRE(c.in.C % chunk == 0, "conv: Cin %d is not a multiple of the K chunk %d", c.in.C, chunk);
-  RON_REQUIRE(c.in.pad >= c.cpad, "conv: input halo %d < conv padding %d", c.in.pad, c.cpad);
-  RON_REQUIRE(c.in.bytes > 0 && c.in.bytes < (int64_t)1 << 32, "conv: input allocation must be < 4 GiB for buffer addressing");
-  RON_REQUIRE(c.wgt_bytes > 0 && c.wgt_bytes < (int64_t)1 << 32, "conv: weight allocation must be < 4 GiB");
-  RON_REQUIRE(c.out.pixels() * c.out.cstride < (int64_t)1 << 31, "conv: output too large for 32-bit offsets");
-  const int K = c.kh * c.kw * c.in.C;
-  const int M = c.in.N * c.Ho * c.Wo;
-  const int BN = igemm_bn(cfg), BM = igemm_bm(cfg);
-  RON_REQUIRE(c.Npad % BN == 0, "conv: Npad %d not a multiple of the N tile %d", c.Npad, BN);
-  if (c.up > 0) RON_REQUIRE(c.up_cout % BN == 0, "transposed conv: channels per tap %d not a multiple of %d", c.up_cout, BN);
-  fill_conv_args(c, &a);
-  a.tiles_n = c.Npad / BN;
   if (c.pool) {
-    // SAME pool: tile rows are the windows' four positions, ceil(Ho / 2) x ceil(Wo / 2) windows per image (an odd map's last windows
-    // hold positions that are no pixel: conv_igemm_tile)
     RON_REQUIRE(c.up == 0 && c.res == nullptr && !c.out_f32 && c.stride == 1, "conv + fused pool: plain stride-1 conv only");
     RON_REQUIRE(c.out.H == (c.Ho + 1) / 2 && c.out.W == (c.Wo + 1) / 2, "conv + fused pool: output view must be the pooled map");
-    a.M = 4 * c.in.N * c.out.H * c.out.W;
   }
-  a.tiles_total = ((a.M + BM - 1) / BM) * a.tiles_n;
-  a.splitk = 1; a.kt_split = a.KT; a.partial = nullptr;
+  if (const int rc = plan_member("conv", c, cfg, single_splitk(c, cfg), c.scratch, c.scratch_bytes, true, false, *a, bn)) return rc;
   if (c.split_n > 0) {
     RON_REQUIRE(c.out_f32 && !c.pool && c.up == 0 && c.res == nullptr && c.center_from == 0, "conv: two head outputs from a plain fp32-output convolution only");
     RON_REQUIRE(c.split_n % 8 == 0 && c.split_first > 0 && c.split_first <= c.split_n && c.split_n < c.Cout,
@@ -368,30 +412,45 @@ static int plan_conv(const ConvLaunch& c, int* cfg_out, ConvArgs* a_out, int* bn
                 "conv: a second output is the un-pooled map of a fused-pool launch");
     RON_REQUIRE(c.out2.pixels() * c.out2.cstride < (int64_t)1 << 31, "conv: second output too large for 32-bit offsets");
   }
-  const int sk = c.splitk >= 0 ? c.splitk : conv_pick_splitk(a.tiles_total, a.KT, igemm_slots(cfg), BM * BN);
-  if (sk > 1 && c.up == 0 && !c.pool && c.scratch != nullptr && (int64_t)sk * M * c.Npad * 4 <= c.scratch_bytes) {
-    a.kt_split = (a.KT + sk - 1) / sk;
-    a.splitk = (a.KT + a.kt_split - 1) / a.kt_split;      // no empty split
-    a.partial = (float*)c.scratch;
-    if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
-  }
-  const int tile_order = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, a.KT);
-  RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "conv: tile order %d: 0 .. %d", tile_order, kConvMaxTileOrder);
-  a.m_fastest = tile_order;
-  a.pos_major = pick_pos_major(c, cfg, BM);
-  a.taps_inner = conv_cfg_taps_inner(cfg) ? 1 : 0;
-  // the 256 x 128 tile: taps innermost by the rule of the other tiles (stride-1 filters that neither split K nor skip filter rows)
-  if (cfg == kCfgIgemm256x128 && c.kh * c.kw > 1 && c.stride == 1 && a.splitk == 1 && !a.pos_major) a.taps_inner = 1;
-  if (c.center_from > 0)
-    RON_REQUIRE(c.center_from % BN == 0 && (c.kh & 1) && (c.kw & 1) && c.up == 0,
-                "conv: centre-tap-only columns need an odd filter and a boundary on the N tile (%d)", BN);
-  RON_REQUIRE((int64_t)c.Npad * K * esz == c.wgt_bytes, "conv: packed weight size mismatch");
-  // 193 .. 224 output channels on the four-wave 256 x 256 tile: its 224-column form.  A split factor this function chose itself keeps
-  // the 256 columns: those are the launches of fewer than 129 tiles (block4_cls_pred below batch 24), which nobody has measured on
-  // the narrower tile; a factor the caller forces (single-operator entry points, the sweep) does not stand in the way.
-  *bn_out = BN;
-  if (igemm_is256(cfg) && (a.splitk == 1 || c.splitk >= 0) && conv_takes_224(c, a.kt_split)) *bn_out = 224;
   return RON_OK;
+}
+
+int conv_describe(const ConvLaunch& c, int out[4], int* n_tile) {
+  int cfg = -1, bn = 0;
+  ConvArgs a = ConvArgs();
+  if (const int rc = plan_conv(c, &cfg, &a, &bn)) return rc;
+  if (n_tile != nullptr) *n_tile = bn;
+  out[0] = cfg;
+  const bool gather = !conv_cfg_is_patch(cfg) && cfg != kCfgC64Resident;
+  out[1] = gather ? a.splitk : 1; out[2] = gather ? a.m_fastest : 0; out[3] = gather ? a.taps_inner : 0;
+  return RON_OK;
+}
+
+// f(Tag<Traits>()) for the traits class of `dtype` (`who` starts the message when there is none)
+template <class T> struct Tag { using type = T; };
+template <class F>
+static int with_traits(int dtype, const char* who, F f) {
+  switch (dtype) {
+    case RON_DTYPE_BF16: return f(Tag<TraitsBF16S>());
+    case RON_DTYPE_F16: return f(Tag<TraitsF16S>());
+    case RON_DTYPE_F32: return f(Tag<TraitsF32S>());
+    case RON_DTYPE_F16X3: return f(Tag<TraitsF16X3S>());
+  }
+  ron::set_error("%s: unknown dtype %d", who, dtype);
+  return RON_ERR_INVALID;
+}
+
+int launch_conv(const ConvLaunch& c, hipStream_t stream) {
+  int cfg = -1, bn = 0;
+  ConvArgs a = ConvArgs();
+  if (const int rc = plan_conv(c, &cfg, &a, &bn)) return rc;
+  if (conv_cfg_is_patch(cfg)) return launch_conv_patch(c, cfg, stream);
+  if (cfg == kCfgC64Resident) return launch_conv_c64(c, stream);
+  return with_traits(c.dtype, "conv", [&](auto tag) {
+    using Tr = typename decltype(tag)::type;
+    const int rc = launch_cfg<Tr>(cfg, bn, a, stream);
+    return (rc != RON_OK || a.splitk == 1) ? rc : launch_finalize<Tr>(a, stream);
+  });
 }
 
 // ---- grouped launches ---------------------------------------------------------------------------------------------
@@ -427,17 +486,14 @@ int group_pick_splitk(int KT, int tiles) {
 
 }  // namespace detail
 
-// Split-K factors of the members of a group.  A member's own bound (group_pick_splitk) assumes the group fills the chip; when
-// the whole group is short of that (small batches: every member is a few tiles), K is cut further so that the group's
-// workgroups come to about the chip's slots, each with >= 8 K steps - what conv_pick_splitk does for a launch of its own.
 // tile configuration member `c` of a group launched as `group_cfg` runs on
 static int group_member_cfg(int group_cfg, const ConvLaunch& c) {
   return group_cfg == kGroupMixed ? (c.Npad % 128 == 0 ? kCfgIgemm128 : kCfgIgemm128x64) : group_cfg;
 }
 
 // Split-K factors of a mixed-width group (one dependency level of the heads: a large "carrier" member and latency-bound small
-// ones) from a model of how the launch runs: workgroups are dispatched in blockIdx order onto 512 slots (two per CU for both
-// 128-row tiles), a workgroup takes as long as its K steps.  For a common chunk length T (K steps per workgroup) every member
+// ones) from a model of how the launch runs: workgroups are dispatched in blockIdx order onto the slots of the group's tile (512: two
+// per CU for both 128-row tiles), a workgroup takes as long as its K steps.  For a common chunk length T (K steps per workgroup) every member
 // is cut into ceil(KT / T) slices (>= 8 steps each; transposed convs, fused pools and forced factors stay as they are); the
 // makespan of the resulting list schedule plus what the fp32 slabs cost (written and read once, in K-step units) is evaluated for
 // a ladder of T, the cheapest wins.  What the fixed "<= 24 steps per workgroup" rule missed: {block7_conv_left, block6_conv_left}
@@ -467,26 +523,22 @@ static long long group_makespan(const int* len, const int* cnt, int n, int slots
 }
 
 static void group_splitks_scheduled(const ConvLaunch* ls, int n, int cfg, int* sk) {
-  // workgroup slots of the chip and what a K step of a workgroup costs with the slots full (measured, tools/_tune in HISTORY.md:
-  // 256 x 256: one per CU, 1.4 us; 128 x 128: two per CU, 1.15 us each; 128 x 64: 0.75 us); slab bytes the memory side moves per us
-  const int slots = cfg == kCfgIgemm256 ? 256 : 512;
-  const double kSlabBytesPerUs = 2.0e6;
+  const double kSlabBytesPerUs = 2.0e6;      // slab bytes the memory side moves per us (slots and K-step costs: tile_of)
   int tiles[kMaxConvGroup], KT[kMaxConvGroup];
   double step_us[kMaxConvGroup];
   bool fixed[kMaxConvGroup];
   for (int k = 0; k < n; ++k) {
     const ConvLaunch& c = ls[k];
-    const int M = c.in.N * c.Ho * c.Wo;
-    const int mcfg = group_member_cfg(cfg, c), BM = igemm_bm(mcfg);
-    step_us[k] = mcfg == kCfgIgemm256 ? 1.4 : (mcfg == kCfgIgemm128 ? 1.15 : 0.75);
-    KT[k] = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
+    const int mcfg = group_member_cfg(cfg, c);
+    const Tile& t = tile_of(mcfg);
+    const ConvGeom g(c);
+    KT[k] = g.KT;
     // a member on the 256 x 224 tile: 7/8 of the MFMAs of a step (block4_cls_pred alone measured 0.83 x, profiles/r08).  The plans of
     // RON-320 full at batches 1 .. 64 are the same for any value from 1.15 to 1.4 here: the entry moves no split factor today.
     // (KT, not the slice the plan will give the member: a slice is never longer, so the step-table limit cannot turn out tighter.)
-    if (mcfg == kCfgIgemm256 && conv_takes_224(c, KT[k])) step_us[k] = 1.4 * 7 / 8;
+    step_us[k] = (mcfg == kCfgIgemm256 && conv_takes_224(c, KT[k])) ? t.step_us * 7 / 8 : t.step_us;
     // centre-tap-only column tiles are a ninth of a tile: count them as that
-    const int cols = c.Npad / igemm_bn(mcfg), cols_long = c.center_from > 0 ? c.center_from / igemm_bn(mcfg) : cols;
-    tiles[k] = ((M + BM - 1) / BM) * cols_long + ((M + BM - 1) / BM) * (cols - cols_long) / (c.kh * c.kw);
+    tiles[k] = g.rows(t) * g.long_cols(t) + g.rows(t) * (g.cols(t) - g.long_cols(t)) / g.taps;
     fixed[k] = c.up > 0 || c.pool || c.splitk >= 0 || KT[k] < 16;
     sk[k] = c.splitk >= 0 ? std::max(c.splitk, 1) : 1;
   }
@@ -503,39 +555,36 @@ static void group_splitks_scheduled(const ConvLaunch* ls, int n, int cfg, int* s
       cnt[k] = tiles[k] * cand[k];
       order[k] = k;
       if (cand[k] > 1) {
-        slab_us += 2.0 * cand[k] * (double)ls[k].in.N * ls[k].Ho * ls[k].Wo * ls[k].Npad * 4 / kSlabBytesPerUs;
+        slab_us += 2.0 * (double)slab_bytes(ls[k], cand[k]) / kSlabBytesPerUs;
         any = true;
       }
     }
     std::sort(order, order + n, [&](int a, int b) { return len[a] > len[b]; });
     int l2[kMaxConvGroup], c2[kMaxConvGroup];
     for (int k = 0; k < n; ++k) { l2[k] = len[order[k]]; c2[k] = cnt[order[k]]; }
-    const double us = group_makespan(l2, c2, n, slots) * 0.05 + slab_us + (any ? 6.0 : 0.0);      // + the finalize launch
+    const double us = group_makespan(l2, c2, n, tile_of(cfg).slots) * 0.05 + slab_us + (any ? 6.0 : 0.0);      // + the finalize launch
     if (us < best) { best = us; for (int k = 0; k < n; ++k) best_sk[k] = cand[k]; }
   }
   for (int k = 0; k < n; ++k) sk[k] = best_sk[k];
 }
 
+// Split-K factors of the members of a group.  A member's own bound (group_pick_splitk) assumes the group fills the chip; when
+// the whole group is short of that (small batches: every member is a few tiles), K is cut further so that the group's
+// workgroups come to about the chip's slots, each with >= 8 K steps - what conv_pick_splitk does for a launch of its own.
 static void group_splitks(const ConvLaunch* ls, int n, int cfg, int* sk) {
-  if (cfg == kGroupMixed || cfg == kCfgIgemm256) {
-    // the schedule model assumes a launch that can fill the chip; below that (small batches: every member is a few tiles) the
-    // per-member rule that follows measured better (batch 1, six levels: 271 vs 291 us)
-    long long wg1 = 0;
-    for (int k = 0; k < n; ++k) {
-      const int mcfg = group_member_cfg(cfg, ls[k]);
-      wg1 += (long long)((ls[k].in.N * ls[k].Ho * ls[k].Wo + igemm_bm(mcfg) - 1) / igemm_bm(mcfg)) * (ls[k].Npad / igemm_bn(mcfg));
-    }
-    if (wg1 * 2 >= (cfg == kCfgIgemm256 ? 256 : 512)) return group_splitks_scheduled(ls, n, cfg, sk);
-  }
-  const int slots = cfg == kCfgIgemm256 ? 256 : 512;     // workgroups the chip holds (256 x 256: one per CU, the 128-row tiles: two)
+  const int slots = tile_of(cfg).slots;     // workgroups the chip holds (256 x 256: one per CU, the 128-row tiles: two)
   int tiles[kMaxConvGroup], KT[kMaxConvGroup];
-  long long steps = 0, wgs = 0;
+  long long steps = 0, wgs = 0, wg1 = 0;
+  for (int k = 0; k < n; ++k) {
+    tiles[k] = ConvGeom(ls[k]).tiles(tile_of(group_member_cfg(cfg, ls[k])));
+    KT[k] = ConvGeom(ls[k]).KT;
+    wg1 += tiles[k];
+  }
+  // the schedule model assumes a launch that can fill the chip; below that (small batches: every member is a few tiles) the
+  // per-member rule that follows measured better (batch 1, six levels: 271 vs 291 us)
+  if ((cfg == kGroupMixed || cfg == kCfgIgemm256) && wg1 * 2 >= slots) return group_splitks_scheduled(ls, n, cfg, sk);
   for (int k = 0; k < n; ++k) {
     const ConvLaunch& c = ls[k];
-    const int M = c.in.N * c.Ho * c.Wo;
-    KT[k] = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
-    const int BM = igemm_bm(group_member_cfg(cfg, c)), BN = igemm_bn(group_member_cfg(cfg, c));
-    tiles[k] = ((M + BM - 1) / BM) * (c.Npad / BN);
     sk[k] = (c.up > 0 || c.pool) ? 1 : (c.splitk >= 0 ? std::max(c.splitk, 1) : group_pick_splitk(KT[k], tiles[k]));
     steps += (long long)tiles[k] * KT[k];
     wgs += (long long)tiles[k] * sk[k];
@@ -550,9 +599,7 @@ static void group_splitks(const ConvLaunch* ls, int n, int cfg, int* sk) {
   }
 }
 
-static int64_t group_slab_bytes(const ConvLaunch& c, int sk) {
-  return sk > 1 ? ron::align_up((int64_t)sk * c.in.N * c.Ho * c.Wo * c.Npad * 4, 256) : 0;
-}
+static int64_t group_slab_bytes(const ConvLaunch& c, int sk) { return sk > 1 ? ron::align_up(slab_bytes(c, sk), 256) : 0; }
 
 int64_t conv_group_scratch_bytes(const ConvLaunch* ls, int n, int cfg, const int* sk_plan) {
   int64_t total = 0;
@@ -568,14 +615,14 @@ int64_t conv_group_scratch_bytes(const ConvLaunch* ls, int n, int cfg, const int
   return total;
 }
 
-// `n` mutually independent convolutions as one launch of tile configuration `cfg` (kCfgIgemm128x64, kCfgIgemm128, or kGroupMixed:
-// each member on the 128-row tile of its own width);
-// `scratch`: conv_group_scratch_bytes() for the split-K slabs (each conv gets its own part).
 void conv_group_plan(const ConvLaunch* ls, int n, int cfg, int* sk) {
   if (cfg == kCfgPatch64 || n < 1 || n > kMaxConvGroup) { for (int k = 0; k < n && k < kMaxConvGroup; ++k) sk[k] = 1; return; }
   group_splitks(ls, n, cfg, sk);
 }
 
+// `n` mutually independent convolutions as one launch of tile configuration `cfg` (kCfgIgemm128x64, kCfgIgemm128, kCfgIgemm256, or
+// kGroupMixed: each member on the 128-row tile of its own width);
+// `scratch`: conv_group_scratch_bytes() for the split-K slabs (each conv gets its own part).
 int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, int64_t scratch_bytes, hipStream_t stream, const int* sk_plan,
                       int* n_tiles) {
   RON_REQUIRE(n >= 1 && n <= kMaxGroup, "conv group: %d launches (1..%d)", n, kMaxGroup);
@@ -585,10 +632,8 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
     // otherwise each as the launch it would be on its own
     RON_REQUIRE(n == 2, "conv group: the patch-kernel form takes a pair");
     if (conv_patch_pair_applicable(ls_in[0], ls_in[1])) return launch_conv_patch_pair(ls_in[0], ls_in[1], stream);
-    for (int k = 0; k < n; ++k) {
-      const int rc = launch_conv(ls_in[k], stream);
-      if (rc) return rc;
-    }
+    for (int k = 0; k < n; ++k)
+      if (const int rc = launch_conv(ls_in[k], stream)) return rc;
     return RON_OK;
   }
   RON_REQUIRE(cfg == kCfgIgemm128x64 || cfg == kCfgIgemm128 || cfg == kGroupMixed || cfg == kCfgIgemm256,
@@ -597,74 +642,36 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
   g.n = n;
   int64_t used = 0;
   bool any_split = false;
-  int sks_in[kMaxConvGroup], sks[kMaxConvGroup], order[kMaxConvGroup];
+  int sks_in[kMaxConvGroup], order[kMaxConvGroup], chain[kMaxConvGroup];
   if (sk_plan != nullptr) for (int k = 0; k < n; ++k) sks_in[k] = sk_plan[k];
   else group_splitks(ls_in, n, cfg, sks_in);
   // workgroups are dispatched in blockIdx order: the members with the longest K chains per workgroup go first, the short ones fill
-  // the slots the long ones leave (members are independent: their order is free)
-  for (int k = 0; k < n; ++k) order[k] = k;
-  if (cfg == kGroupMixed || cfg == kCfgIgemm256) {
-    auto chain = [&](int k) {
-      const ConvLaunch& c = ls_in[k];
-      const int KT = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
-      return (KT + sks_in[k] - 1) / sks_in[k];
-    };
-    std::stable_sort(order, order + n, [&](int a, int b) { return chain(a) > chain(b); });
-  }
-  ConvLaunch ls[kMaxConvGroup];
-  for (int k = 0; k < n; ++k) { ls[k] = ls_in[order[k]]; sks[k] = sks_in[order[k]]; }
-  // the 256 x 256 group runs on the four-wave tiles (which decode panel tile orders) when every member's K chain fits their step table
-  bool group_4w = cfg == kCfgIgemm256 && ls[0].dtype != RON_DTYPE_F32;
-  for (int k = 0; k < n && group_4w; ++k) {
-    const int KT = ls[k].kh * ls[k].kw * ls[k].in.C / conv_k_chunk(ls[k].dtype);
-    group_4w = asm_loop_ok((KT + sks[k] - 1) / std::max(sks[k], 1));
-  }
+  // the slots the long ones leave (members are independent: their order is free); the 256 x 256 group runs on the four-wave tiles
+  // (which decode panel tile orders) when every member's K chain fits their step table
+  bool group_4w = cfg == kCfgIgemm256 && ls_in[0].dtype != RON_DTYPE_F32;
   for (int k = 0; k < n; ++k) {
-    const ConvLaunch& c = ls[k];
-    const int esz = (int)dtype_size(c.dtype), chunk = conv_k_chunk(c.dtype);
-    const int mcfg = group_member_cfg(cfg, c), BM = igemm_bm(mcfg), BN = igemm_bn(mcfg);
-    if (mcfg == kCfgIgemm128x64) g.narrow |= 1u << k;
-    // (a four-wave 256 x 256 group: bit k = member k on the 256 x 224 tile, set below once its split factor is known)
-    RON_REQUIRE(c.dtype == ls[0].dtype, "conv group: mixed dtypes");
-    RON_REQUIRE(c.in.C % chunk == 0 && c.in.pad >= c.cpad, "conv group: bad input (Cin %d, halo %d < %d)", c.in.C, c.in.pad, c.cpad);
-    RON_REQUIRE(c.in.bytes > 0 && c.in.bytes < (int64_t)1 << 32 && c.wgt_bytes > 0 && c.wgt_bytes < (int64_t)1 << 32,
-                "conv group: allocations must be < 4 GiB");
-    RON_REQUIRE(c.out.pixels() * c.out.cstride < (int64_t)1 << 31, "conv group: output too large for 32-bit offsets");
-    RON_REQUIRE(c.Npad % BN == 0 && !c.pool, "conv group: Npad %d not a multiple of the N tile %d, or a fused pool", c.Npad, BN);
-    if (c.up > 0) RON_REQUIRE(c.up_cout % BN == 0, "transposed conv: channels per tap %d not a multiple of %d", c.up_cout, BN);
-    ConvArgs& a = g.op[k];
-    {
-      const int rc = check_conv_fields(c);
-      if (rc != RON_OK) return rc;
-    }
-    fill_conv_args(c, &a);
-    RON_REQUIRE((int64_t)c.Npad * a.K * esz == c.wgt_bytes, "conv group: packed weight size mismatch");
-    a.tiles_n = c.Npad / BN;
-    a.tiles_total = ((a.M + BM - 1) / BM) * a.tiles_n;
-    const int64_t need = group_slab_bytes(c, sks[k]);
-    if (need > 0 && scratch != nullptr && used + need <= scratch_bytes) {
-      const int sk = sks[k];
-      a.kt_split = (a.KT + sk - 1) / sk;
-      a.splitk = (a.KT + a.kt_split - 1) / a.kt_split;
-      a.partial = reinterpret_cast<float*>(static_cast<char*>(scratch) + used);
-      if (a.splitk == 1) { a.kt_split = a.KT; a.partial = nullptr; }
-      else { used += need; any_split = true; }
-    }
-    if (group_4w && conv_takes_224(c, a.kt_split)) g.narrow |= 1u << k;
-    const int tile_order = pick_m_fastest(c, BM, BN, a.tiles_total / a.tiles_n, a.tiles_n, a.splitk, group_4w ? a.kt_split : 0);
-    RON_REQUIRE(tile_order >= 0 && tile_order <= kConvMaxTileOrder, "conv group: tile order %d: 0 .. %d", tile_order, kConvMaxTileOrder);
-    a.m_fastest = tile_order;
-    a.pos_major = pick_pos_major(c, mcfg, BM);
-    // K order of the member, by the rules of a launch of its own (conv_pick_cfg): taps innermost for stride-1 filters that neither
-    // split K nor skip filter rows - on the 256 x 256 tile where the long columns are at most two tiles wide, on 128 x 128 always
-    const int n_long = c.center_from > 0 ? c.center_from : c.Npad;
-    a.taps_inner = (c.kh * c.kw > 1 && c.up == 0 && c.stride == 1 && a.splitk == 1 && !a.pos_major &&
-                    (mcfg == kCfgIgemm128 || (mcfg == kCfgIgemm256 && n_long <= kTapsInnerMaxN))) ? 1 : 0;
-    if (c.center_from > 0) RON_REQUIRE(c.center_from % BN == 0 && (c.kh & 1) && (c.kw & 1), "conv group: bad centre-tap-only columns");
+    order[k] = k;
+    chain[k] = (ConvGeom(ls_in[k]).KT + sks_in[k] - 1) / std::max(sks_in[k], 1);
+    group_4w = group_4w && asm_loop_ok(chain[k]);
   }
-  if (n_tiles != nullptr)
-    for (int k = 0; k < n; ++k)
-      n_tiles[order[k]] = (group_4w && ((g.narrow >> k) & 1u)) ? 224 : igemm_bn(group_member_cfg(cfg, ls[k]));
+  if (cfg == kGroupMixed || cfg == kCfgIgemm256) std::stable_sort(order, order + n, [&](int a, int b) { return chain[a] > chain[b]; });
+  for (int k = 0; k < n; ++k) {
+    const ConvLaunch& c = ls_in[order[k]];
+    const int mcfg = group_member_cfg(cfg, c), sk = sks_in[order[k]];
+    int bn = 0;
+    RON_REQUIRE(c.dtype == ls_in[0].dtype, "conv group: mixed dtypes");
+    RON_REQUIRE(c.Npad % tile_of(mcfg).bn == 0 && !c.pool, "conv group: Npad %d not a multiple of the N tile %d, or a fused pool", c.Npad,
+                tile_of(mcfg).bn);
+    if (const int rc = check_conv_fields(c)) return rc;
+    const int64_t need = group_slab_bytes(c, sk);
+    const bool fits = need > 0 && scratch != nullptr && used + need <= scratch_bytes;
+    if (const int rc = plan_member("conv group", c, mcfg, sk, fits ? static_cast<char*>(scratch) + used : nullptr, fits ? need : 0, group_4w, true,
+                                   g.op[k], &bn)) return rc;
+    if (g.op[k].splitk > 1) { used += need; any_split = true; }
+    // ConvGroupArgs::narrow, bit k: member k on the 128 x 64 tile (a mixed group), or on the 256 x 224 tile (a four-wave 256 x 256 group)
+    if (mcfg == kCfgIgemm128x64 || bn == 224) g.narrow |= 1u << k;
+    if (n_tiles != nullptr) n_tiles[order[k]] = bn;
+  }
   // entries, longest K chain first (see ConvGroupArgs)
   struct Ent { int op, bid0, cnt, chain; };
   Ent ents[kMaxEntries];
@@ -673,10 +680,10 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
     const ConvArgs& a = g.op[k];
     const int total = a.tiles_total * a.splitk;
     if (a.center_from_n > 0 && a.splitk == 1) {
-      const int BN = igemm_bn(group_member_cfg(cfg, ls[k]));
+      const int BN = tile_of(group_member_cfg(cfg, ls_in[order[k]])).bn;
       const int n_long = (a.tiles_total / a.tiles_n) * (a.center_from_n / BN);
       ents[ne++] = Ent{k, 0, n_long, a.KT};
-      ents[ne++] = Ent{k, n_long, total - n_long, a.Cin / conv_k_chunk(ls[k].dtype)};
+      ents[ne++] = Ent{k, n_long, total - n_long, a.Cin / conv_k_chunk(ls_in[0].dtype)};
     } else {
       ents[ne++] = Ent{k, 0, total, a.kt_split};
     }
@@ -687,22 +694,15 @@ int launch_conv_group(const ConvLaunch* ls_in, int n, int cfg, void* scratch, in
     g.eop[e] = ents[e].op; g.ebid0[e] = ents[e].bid0; g.enwg[e] = g.op[ents[e].op].tiles_total * g.op[ents[e].op].splitk;
     g.first[e + 1] = g.first[e] + ents[e].cnt;
   }
-  if (ls[0].dtype == RON_DTYPE_BF16) return launch_group_cfg<TraitsBF16S>(cfg, g, any_split, stream);
-  if (ls[0].dtype == RON_DTYPE_F16) return launch_group_cfg<TraitsF16S>(cfg, g, any_split, stream);
-  if (ls[0].dtype == RON_DTYPE_F32) return launch_group_cfg<TraitsF32S>(cfg, g, any_split, stream);
-  if (ls[0].dtype == RON_DTYPE_F16X3) return launch_group_cfg<TraitsF16X3S>(cfg, g, any_split, stream);
-  ron::set_error("conv group: unknown dtype %d", ls[0].dtype);
-  return RON_ERR_INVALID;
+  return with_traits(ls_in[0].dtype, "conv group",
+                     [&](auto tag) { return launch_group_cfg<typename decltype(tag)::type>(cfg, g, any_split, stream); });
 }
 
 int64_t conv_scratch_bytes(const ConvLaunch& c) {
   const int cfg = c.cfg >= 0 ? c.cfg : conv_pick_cfg(c);
   if (conv_cfg_is_patch(cfg) || c.up > 0 || c.pool) return 0;      // the halo-patch kernel never splits K
-  const int M = c.in.N * c.Ho * c.Wo;
-  const int KT = c.kh * c.kw * c.in.C / conv_k_chunk(c.dtype);
-  const int tiles = ((M + igemm_bm(cfg) - 1) / igemm_bm(cfg)) * (c.Npad / igemm_bn(cfg));
-  const int sk = c.splitk >= 0 ? c.splitk : conv_pick_splitk(tiles, KT, igemm_slots(cfg), igemm_bm(cfg) * igemm_bn(cfg));
-  return sk > 1 ? (int64_t)sk * M * c.Npad * 4 : 0;
+  const int sk = single_splitk(c, cfg);
+  return sk > 1 ? slab_bytes(c, sk) : 0;
 }
 
 }  // namespace ron

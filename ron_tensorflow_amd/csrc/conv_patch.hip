@@ -589,7 +589,7 @@ int launch_conv_patch_pair(const ConvLaunch& ca, const ConvLaunch& cb, hipStream
 }
 
 int launch_conv_patch(const ConvLaunch& c, int cfg, hipStream_t stream) {
-  PatchArgs a;
+  PatchArgs a = PatchArgs();
   int grid = 0;
   const int rc0 = patch_args(c, cfg, &a, &grid);
   if (rc0) return rc0;

@@ -364,7 +364,7 @@ int plan_wgrad(const WgradLaunch& c, WgradPlan* p) {
 
 template <bool BF16, int WBM, int WBN>
 int launch_wgrad_t(const WgradLaunch& c, const WgradPlan& p, hipStream_t s) {
-  WgradArgs a;
+  WgradArgs a = WgradArgs();
   a.x = static_cast<const char*>(c.x.base); a.dz = static_cast<const char*>(c.dz.base);
   a.out = p.slices > 1 ? static_cast<float*>(c.scratch) : c.dw;
   a.slab_elems = p.slab_elems;
@@ -477,7 +477,7 @@ int check_backward_call(const char* what, const char* sizer, const ron_conv_desc
 template <bool BF16>
 int launch_pack_halo(const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc, int cdst,
                      int64_t guard, hipStream_t s) {
-  PackArgs a;
+  PackArgs a = PackArgs();
   a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
   a.rows = rows + 2 * guard; a.guard = guard;
   a.N = n; a.H = h; a.W = w; a.pad = pad; a.Csrc = csrc; a.Cdst = cdst;
@@ -492,7 +492,7 @@ int launch_pack_halo(const float* src, const float* mask, void* out, int64_t row
 template <bool BF16>
 int launch_pack_halo_scatter(const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc,
                              int cdst, int hs, int ws, int sstep, int soff, hipStream_t s) {
-  PackArgs a;
+  PackArgs a = PackArgs();
   a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
   a.rows = rows; a.guard = 0;
   a.N = n; a.H = h; a.W = w; a.pad = pad; a.Csrc = csrc; a.Cdst = cdst;
@@ -600,7 +600,7 @@ int run_backward(const ron_conv_desc* d, const BackwardPlan& P, const float* x, 
   else rc = launch_pack_halo_scatter<BF16>(dy, d->relu ? y : nullptr, dzbuf, P.rows, d->n, d->h, d->w, P.pad, d->cout, P.cop, hs, wsrc, sstep, soff, s);
   if (rc) return rc;
   if (dx != nullptr) {
-    WpackArgs wa;
+    WpackArgs wa = WpackArgs();
     wa.w = w; wa.out = reinterpret_cast<unsigned short*>(ws + P.off_w);
     wa.taps = P.taps; wa.cin = d->cin; wa.cout = d->cout; wa.cop = P.cop; wa.npad = P.npad;
     RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
@@ -901,7 +901,7 @@ int plan_k2s2(const ron_conv_desc* d, K2Plan* P) {
 
 template <bool BF16>
 int k2s2_pack_s2d(const float* src, const float* mask, void* out, const K2Plan& P, int n, int c, hipStream_t s) {
-  S2dArgs a;
+  S2dArgs a = S2dArgs();
   a.src = src; a.mask = mask; a.out = static_cast<unsigned short*>(out);
   a.rows = P.rows; a.N = n; a.H = P.H; a.W = P.W; a.C = c;
   RON_LAUNCH(k2s2_pack_s2d_kernel<BF16>, dim3(grid_for(a.rows * (c / 2))), dim3(256), 0, s, a);
@@ -928,7 +928,7 @@ int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const floa
       RON_LAUNCH(k2s2_pack_weights_kn_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, w, wout, P.kconv, d->cin, P.npad);
     } else {
       // HWIO [2,2,cin,cout] = [4 cin][cout]: the rows of the launch as they stand (conv_bwd_pack_weights_kernel with a single tap)
-      WpackArgs wa;
+      WpackArgs wa = WpackArgs();
       wa.w = w; wa.out = wout;
       wa.taps = 1; wa.cin = 4 * d->cin; wa.cout = d->cout; wa.cop = P.cz; wa.npad = P.npad;
       RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
@@ -939,7 +939,7 @@ int run_k2s2(const ron_conv_desc* d, const K2Plan& P, const float* x, const floa
     if (tr) {
       if ((rc = launch_unpack(out, d->dtype, 0, dx, s))) return rc;
     } else {
-      D2sArgs u;
+      D2sArgs u = D2sArgs();
       u.in = reinterpret_cast<const unsigned short*>(ws + P.off_dx); u.dx = dx;
       u.N = d->n; u.H = P.H; u.W = P.W; u.C = d->cin; u.vec_store = ((uintptr_t)dx & 15) == 0;
       RON_LAUNCH(k2s2_unpack_d2s_kernel<BF16>, dim3(grid_for((long long)d->n * d->h * d->w * (d->cin / 8))), dim3(256), 0, s, u);

@@ -89,7 +89,7 @@ struct Op {
   int up = 0, up_cout = 0, pool = 0;
   int center_from = 0;                  // output channels >= this hold a 1x1 branch in the centre tap of the 3x3 filter (0: none)
   int fuse_next_pool = 0;               // the next op is this conv's 2x2 pool and both maps are needed (conv4_3, conv5_3): one launch
-                                        // with two outputs whenever the conv would not split K (decided per batch in ron_forward)
+                                        // with two outputs whenever the conv would not split K (decided per batch by slot_resources)
   int head_kind = -1, head_layer = -1;  // 0 cls, 1 obj, 2 loc
   int head_kind2 = -1;                  // a second head output of the same layer from the same launch (pack_box_pair), or -1
   int Ho = 0, Wo = 0;
@@ -148,12 +148,13 @@ struct ron_ctx {
   std::vector<OpTiming> timing;                       // ops.size() + 1 (last = post-processing)
   std::vector<std::string> labels;                    // ron_profile_get names, one per op, built once (stable until ron_destroy)
   int grouped_launches = 0;                           // grouped launches in the plan (0: one launch per convolution)
-  // split-K factors of the grouped launches, planned once per (first op of the group, batch) - conv_group_plan models the launch's
-  // schedule, which is far too slow for the enqueue path: [op index] -> [batch] -> factors (first = 0: not planned yet)
-  std::map<int, std::vector<std::array<int, kMaxConvGroup>>> group_sk;
-  // conv4_3 / conv5_3 with their pool from the same launch (Op::fuse_next_pool): decided once per (op, batch) - the answer is "the
-  // two-output launch would not split K", which takes a tile-configuration pick: [op index] -> [batch] -> -1 unknown / 0 / 1
-  std::map<int, std::vector<signed char>> fuse_pool_ok;
+  // What each conv launch does at each batch size, [batch 1 .. max_batch][first op of the launch]: decided once by slot_resources (a
+  // clone copies its owner's) and only read by ron_forward - conv_group_plan models a launch's schedule, ~1 ms: too slow to enqueue with.
+  struct LaunchPlan {
+    std::array<int, kMaxConvGroup> sk{};      // a grouped launch: the members' split-K factors
+    bool fuse_pool = false;                   // conv4_3 / conv5_3 (Op::fuse_next_pool): the conv takes its pool along at this batch
+  };
+  std::vector<std::vector<LaunchPlan>> launch_plans;
   std::vector<std::vector<Event>> pending;            // per recorded call: one event per stamp ...
   std::vector<std::vector<int>> pending_ops;          // ... and what it marks: op index or kStamp*
   std::vector<Event> event_pool;
@@ -1030,6 +1031,19 @@ static int describe_conv(const ron_ctx* c, const Op& o, int n, const ron_heads* 
   return RON_OK;
 }
 
+// The members of the launch that starts at op `oi`, at batch n: the op itself, or it and the following ops of its group.
+static int gather_launch(const ron_ctx* c, size_t oi, int n, const ron_heads* heads, ConvLaunch* L, int* members) {
+  const Op& o = c->ops[oi];
+  int m = 0;
+  do {
+    RON_REQUIRE(m < kMaxConvGroup, "conv group %d has more than %d members", o.group, kMaxConvGroup);
+    if (const int rc = describe_conv(c, c->ops[oi + m], n, heads, &L[m])) return rc;
+    ++m;
+  } while (o.group >= 0 && oi + m < c->ops.size() && c->ops[oi + m].group == o.group);
+  *members = m;
+  return RON_OK;
+}
+
 // the context's own head buffers, as ron_detect hands them to the forward pass and the post-processing
 static void own_heads(const ron_ctx* c, ron_heads* hd) {
   for (int i = 0; i < c->n_feat; ++i) {
@@ -1046,38 +1060,43 @@ static int slot_resources(ron_ctx* c) {
       RON_HIP_CHECK(hipEventCreateWithFlags(c->lane_done[l].put(), hipEventDisableTiming));
     }
   }
-  // split-K scratch: the largest slab set any launch (or grouped launch) of a lane can ask for at max_batch
-  for (size_t i = 0; i < c->ops.size();) {
-    const Op& o = c->ops[i];
-    size_t j = i + 1;
-    if (o.kind == OP_CONV && o.group >= 0) while (j < c->ops.size() && c->ops[j].group == o.group) ++j;
-    if (o.kind == OP_CONV && (o.group >= 0 || o.up == 0)) {
-      // a clone takes the plans (and with them the scratch sizes) of the slot it was cloned from: the schedule model of a grouped
-      // launch costs ~1 ms per (group, batch)
-      const ron_ctx* from = c->weights_owner;
-      std::vector<std::array<int, kMaxConvGroup>>* plans = nullptr;
-      if (o.group >= 0) {
-        plans = &c->group_sk[(int)i];
-        if (from != nullptr && from->group_sk.count((int)i)) *plans = from->group_sk.at((int)i);
-        else plans->assign(c->cfg.max_batch + 1, std::array<int, kMaxConvGroup>{});
-      }
-      for (int nb = 1; nb <= c->cfg.max_batch && from == nullptr; ++nb) {
+  // The launch plans of every batch size, and with them the split-K scratch: the largest slab set any launch (or grouped launch) of
+  // a lane can ask for.  A clone takes both from the slot it was cloned from (the schedule model costs ~1 ms per (group, batch)).
+  if (const ron_ctx* from = c->weights_owner) {
+    c->launch_plans = from->launch_plans;
+    for (int l = 0; l < 4; ++l) c->splitk_bytes[l] = from->splitk_bytes[l];
+  } else {
+    c->launch_plans.assign(c->cfg.max_batch + 1, std::vector<ron_ctx::LaunchPlan>(c->ops.size()));
+    int members = 1;
+    for (size_t i = 0; i < c->ops.size(); i += members) {
+      const Op& o = c->ops[i];
+      members = 1;
+      if (o.kind != OP_CONV || (o.group < 0 && o.up > 0)) continue;
+      const bool pool_follows = o.fuse_next_pool && i + 1 < c->ops.size() && c->ops[i + 1].kind == OP_POOL;
+      for (int nb = 1; nb <= c->cfg.max_batch; ++nb) {
         ConvLaunch L[kMaxConvGroup];
-        for (size_t k = i; k < j; ++k) describe_conv(c, c->ops[k], nb, nullptr, &L[k - i]);
+        if (const int rc = gather_launch(c, i, nb, nullptr, L, &members)) return rc;
+        ron_ctx::LaunchPlan& plan = c->launch_plans[nb][i];
         int64_t b;
         if (o.group >= 0) {
           // the plan ron_forward will launch with, and its scratch, from ONE run of the model
-          conv_group_plan(L, (int)(j - i), o.group_cfg, (*plans)[nb].data());
-          b = conv_group_scratch_bytes(L, (int)(j - i), o.group_cfg, (*plans)[nb].data());
+          conv_group_plan(L, members, o.group_cfg, plan.sk.data());
+          b = conv_group_scratch_bytes(L, members, o.group_cfg, plan.sk.data());
         } else {
           b = conv_scratch_bytes(L[0]);
+          if (pool_follows) {
+            // conv4_3 / conv5_3: both the map and its pool are read later.  When the launch does not split K (it does at small
+            // batches: the pool epilogue needs whole sums) the pool comes out of the same accumulators and the pool launch is skipped.
+            // (The pool inside the split-K finalize pass instead was measured at batch 1: conv4_3 30.9 + pool4 8.7 us -> 40.9 us, no gain.)
+            ConvLaunch F = L[0];
+            F.out2 = L[0].out;                           // the kernel choice of a two-output launch (row-gather kernel only) ...
+            plan.fuse_pool = conv_scratch_bytes(F) == 0;      // ... would not split K at this batch
+          }
         }
         if (b > c->splitk_bytes[o.lane]) c->splitk_bytes[o.lane] = b;
       }
     }
-    i = j;
   }
-  if (c->weights_owner != nullptr) for (int l = 0; l < 4; ++l) c->splitk_bytes[l] = c->weights_owner->splitk_bytes[l];
   for (int l = 0; l < 4; ++l)
     if (c->splitk_bytes[l] > 0) RON_HIP_CHECK(ron::dev_malloc(c->splitk[l].put(), (size_t)c->splitk_bytes[l]));
   // ron_detect's head buffers and post-processing workspace, for max_batch: allocated (and the workspace zeroed) here, so that the
@@ -1192,6 +1211,7 @@ static int forward(ron_ctx* c, const float* d_images, int n, ron_heads* out, voi
   const Weights& W = *c->wts;
   const hipStream_t main_stream = (hipStream_t)stream;
   bool lane_started[4] = {false, false, false, false};
+  ConvLaunch L[kMaxConvGroup];      // the members of the launch being enqueued
   for (size_t oi = 0; oi < c->ops.size(); ++oi) {
     const Op& o = c->ops[oi];
     hipStream_t s = main_stream;
@@ -1220,47 +1240,26 @@ static int forward(ron_ctx* c, const float* d_images, int n, ron_heads* out, voi
       if ((rc = launch_maxpool3x3s1(c->view(o.in, n), c->view(o.out, n), c->cfg.dtype, s))) return rc;
     } else if (o.kind == OP_L2NORM) {
       if ((rc = launch_l2norm(c->view(o.in, n), c->view(o.out, n), W.l2_gamma.as<float>(), c->cfg.dtype, s))) return rc;
-    } else if (o.group >= 0) {
-      // this op and the following ones of the same group: one launch (the stamp above times the whole group)
-      ConvLaunch L[kMaxConvGroup];
-      size_t j = oi;
-      for (; j < c->ops.size() && c->ops[j].group == o.group; ++j) {
-        RON_REQUIRE(j - oi < (size_t)kMaxConvGroup, "conv group %d has more than %d members", o.group, kMaxConvGroup);
-        if ((rc = describe_conv(c, c->ops[j], n, out, &L[j - oi]))) return rc;
-      }
-      std::vector<std::array<int, kMaxConvGroup>>& plans = c->group_sk[(int)oi];      // filled by slot_resources
-      if (plans.empty()) plans.assign(c->cfg.max_batch + 1, std::array<int, kMaxConvGroup>{});
-      if (plans[n][0] == 0) conv_group_plan(L, (int)(j - oi), o.group_cfg, plans[n].data());
-      if ((rc = launch_conv_group(L, (int)(j - oi), o.group_cfg, c->splitk[o.lane], c->splitk_bytes[o.lane], s, plans[n].data()))) {
-        std::string msg = ron_last_error();
-        ron::set_error("group of %s: %s", o.name.c_str(), msg.c_str());
-        return rc;
-      }
-      oi = j - 1;
     } else {
-      ConvLaunch L;
-      if ((rc = describe_conv(c, o, n, out, &L))) return rc;
-      if (o.fuse_next_pool && oi + 1 < c->ops.size() && c->ops[oi + 1].kind == OP_POOL) {
-        // conv4_3 / conv5_3: both the map and its pool are read later.  When this launch does not split K (it does at small
-        // batches: the pool epilogue needs whole sums) the pool comes out of the same accumulators and the pool launch is skipped.
-        // (The pool inside the split-K finalize pass instead was measured at batch 1: conv4_3 30.9 + pool4 8.7 us -> 40.9 us, no gain.)
-        ConvLaunch F = L;
-        F.out2 = L.out;                           // the kernel choice of a two-output launch (row-gather kernel only) ...
-        std::vector<signed char>& ok = c->fuse_pool_ok[(int)oi];
-        if (ok.empty()) ok.assign(c->cfg.max_batch + 1, (signed char)-1);
-        if (ok[n] < 0) ok[n] = conv_scratch_bytes(F) == 0 ? 1 : 0;      // ... would not split K at this batch
-        if (ok[n] == 1) {
-          F.out = c->view(c->ops[oi + 1].out, n);
-          F.pool = 1;
-          L = F;
-          ++oi;
+      // a convolution, or this op and the rest of its group as one launch (one stamp for it), as slot_resources planned it for this batch
+      int members = 1;
+      if ((rc = gather_launch(c, oi, n, out, L, &members))) return rc;
+      const ron_ctx::LaunchPlan& plan = c->launch_plans[n][oi];
+      if (o.group >= 0) {
+        rc = launch_conv_group(L, members, o.group_cfg, c->splitk[o.lane], c->splitk_bytes[o.lane], s, plan.sk.data());
+      } else {
+        if (plan.fuse_pool) {                     // the pooled map from the same launch; the pool op that follows is skipped
+          L[0].out2 = L[0].out; L[0].out = c->view(c->ops[oi + 1].out, n); L[0].pool = 1;
+          ++members;
         }
+        rc = launch_conv(L[0], s);
       }
-      if ((rc = launch_conv(L, s))) {
+      if (rc) {
         std::string msg = ron_last_error();
-        ron::set_error("%s: %s", o.name.c_str(), msg.c_str());
+        ron::set_error(o.group >= 0 ? "group of %s: %s" : "%s: %s", o.name.c_str(), msg.c_str());
         return rc;
       }
+      oi += members - 1;
     }
   }
   if (rec) {

@@ -90,7 +90,7 @@ extern "C" int ron_maxpool2x2_backward_nhwc(const float* x, const float* dy, int
   RON_REQUIRE(c >= 8 && c % 8 == 0, "maxpool backward: c %d must be a multiple of 8", c);
   RON_REQUIRE(x != nullptr && dy != nullptr && dx != nullptr, "maxpool backward: NULL tensor");
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "maxpool backward: x, dy and dx must be 16-byte aligned (16 bytes per access)");
-  PoolBwdArgs a;
+  PoolBwdArgs a = PoolBwdArgs();
   a.x = x; a.dy = dy; a.dx = dx;
   a.h = h; a.w = w; a.oh = (h + 1) / 2; a.ow = (w + 1) / 2; a.c = c;
   a.total = (long long)n * a.oh * a.ow * (c / 4);

@@ -170,7 +170,7 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
     RON_HIP_CHECK(dev_upload(&d_bb, b64.data(), 64 * 4));
     if ((rc = launch_stem_conv(x, d->n, d->h, d->w, d->dtype, d_f.p, (const float*)d_bb.p, S.c.out, s, oscale))) return rc;
     if ((rc = launch_unpack(S.c.out, d->dtype, 0, y, s))) return rc;
-    RON_HIP_CHECK(hipStreamSynchronize(s));
+    RON_HIP_CHECK(dev_stream_sync(s));
     return RON_OK;
   }
   if (S.is_c3) {
@@ -185,7 +185,7 @@ extern "C" int ron_conv2d_nhwc(const ron_conv_desc* d, const float* x, const flo
   }
   if ((rc = launch_conv(S.c, s))) return rc;
   if ((rc = launch_unpack(S.c.out, d->dtype, 0, y, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 
@@ -211,7 +211,7 @@ extern "C" int ron_conv2d_pool2_nhwc(const ron_conv_desc* d, const float* x, con
   if ((rc = launch_conv(c, s))) return rc;
   if ((rc = launch_unpack(c.out, d->dtype, 0, y_pooled, s))) return rc;
   if ((rc = launch_unpack(c.out2, d->dtype, 0, y_full, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 
@@ -289,7 +289,7 @@ extern "C" int ron_conv2d_f32out_nhwc(const ron_conv_desc* da, const float* xa, 
   if (!grouped) {
     for (int k = 0; k < n; ++k) {
       int o[4];
-      if ((rc = conv_describe(L[k], o, &widths[k])) || (rc = launch_conv(L[k], s))) { (void)hipStreamSynchronize(s); return rc; }
+      if ((rc = conv_describe(L[k], o, &widths[k])) || (rc = launch_conv(L[k], s))) { (void)dev_stream_sync(s); return rc; }
     }
   } else {
     // split factors: the descriptors' where both give one (>= 1), else the group's own plan
@@ -297,10 +297,10 @@ extern "C" int ron_conv2d_f32out_nhwc(const ron_conv_desc* da, const float* xa, 
     const int* plan = (sk[0] >= 1 && sk[1] >= 1) ? sk : nullptr;
     for (int k = 0; k < 2; ++k) { L[k].scratch = nullptr; L[k].scratch_bytes = 0; L[k].splitk = plan ? sk[k] : -1; }
     const int64_t sb = conv_group_scratch_bytes(L, 2, kCfgIgemm256, plan);
-    if (sb > 0 && (rc = alloc(&scratch, sb, false))) { (void)hipStreamSynchronize(s); return rc; }
-    if ((rc = launch_conv_group(L, 2, kCfgIgemm256, scratch.p, sb, s, plan, widths))) { (void)hipStreamSynchronize(s); return rc; }
+    if (sb > 0 && (rc = alloc(&scratch, sb, false))) { (void)dev_stream_sync(s); return rc; }
+    if ((rc = launch_conv_group(L, 2, kCfgIgemm256, scratch.p, sb, s, plan, widths))) { (void)dev_stream_sync(s); return rc; }
   }
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   if (n_tiles != nullptr) for (int k = 0; k < n; ++k) n_tiles[k] = widths[k];
   return RON_OK;
 }
@@ -344,7 +344,7 @@ extern "C" int ron_conv2d_patch_pair_nhwc(const ron_conv_desc* da, const ron_con
   conv_patch_pair_columns(S[0].c, S[1].c, cols);
   if (columns != nullptr) { columns[0] = cols[0]; columns[1] = cols[1]; }
   rc = launch_conv_patch_pair(S[0].c, S[1].c, s, kCfgPatch64);
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return rc;
 }
 
@@ -397,7 +397,7 @@ extern "C" int ron_conv2d_heads_nhwc(const ron_conv_desc* d, int split_first, co
   }
   if ((rc = launch_pack_input(x, c.in, d->dtype, s))) return rc;
   if ((rc = launch_conv(c, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 
@@ -450,7 +450,7 @@ extern "C" int ron_maxpool2x2_nhwc(const float* x, int n, int h, int w, int c, i
   if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
   if ((rc = launch_maxpool2x2(vin, vout, dtype, s))) return rc;
   if ((rc = launch_unpack(vout, dtype, 0, y, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 
@@ -472,7 +472,7 @@ extern "C" int ron_maxpool3x3s1_nhwc(const float* x, int n, int h, int w, int c,
   if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
   if ((rc = launch_maxpool3x3s1(vin, vout, dtype, s))) return rc;
   if ((rc = launch_unpack(vout, dtype, 0, y, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 
@@ -493,7 +493,7 @@ extern "C" int ron_l2norm_nhwc(const float* x, const float* gamma, int n, int h,
   if ((rc = launch_pack_input(x, vin, dtype, s))) return rc;
   if ((rc = launch_l2norm(vin, vout, gamma, dtype, s))) return rc;
   if ((rc = launch_unpack(vout, dtype, 0, y, s))) return rc;
-  RON_HIP_CHECK(hipStreamSynchronize(s));
+  RON_HIP_CHECK(dev_stream_sync(s));
   return RON_OK;
 }
 

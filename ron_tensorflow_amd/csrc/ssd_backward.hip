@@ -277,7 +277,7 @@ extern "C" int ron_maxpool3x3s1_backward_nhwc(const float* x, const float* dy, i
   RON_REQUIRE(elems_fit(n, h, w, c, &pixels), "maxpool3x3 backward: tensor of %d x %d x %d x %d elements is beyond 64-bit indexing", n, h, w, c);
   RON_REQUIRE(x != nullptr && dy != nullptr && dx != nullptr, "maxpool3x3 backward: NULL tensor");
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx) & 15) == 0, "maxpool3x3 backward: x, dy and dx must be 16-byte aligned (16 bytes per access)");
-  Pool3Args a;
+  Pool3Args a = Pool3Args();
   a.x = x; a.dy = dy; a.dx = dx;
   a.h = h; a.w = w; a.c = c;
   a.total = pixels * (c / 4);
@@ -309,7 +309,7 @@ extern "C" int ron_l2norm_backward_nhwc(const float* x, const float* gamma, cons
               (long long)workspace_bytes, (long long)need);
   RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "l2norm backward: the workspace must be 256-byte aligned");
   if (dx == nullptr && dgamma == nullptr) return RON_OK;
-  L2Args a;
+  L2Args a = L2Args();
   a.x = x; a.gamma = gamma; a.dy = dy; a.dx = dx;
   a.table = dgamma != nullptr ? static_cast<float*>(workspace) : nullptr;
   a.pixels = pixels; a.c = c; a.waves = waves;

@@ -262,7 +262,7 @@ int plan_stem_backward(const ron_conv_desc* d, StemPlan* P) {
 template <bool BF16>
 int run_stem_backward(const ron_conv_desc* d, const StemPlan& P, const float* x, const float* y, const float* dy, float* dw, float* dbias,
                       void* workspace, hipStream_t s) {
-  StemWgradArgs a;
+  StemWgradArgs a = StemWgradArgs();
   a.x = x; a.y = d->relu ? y : nullptr; a.dy = dy;
   a.slabs = static_cast<float*>(workspace);
   a.H = d->h; a.W = d->w; a.pixels = P.pixels;

@@ -6,12 +6,16 @@
 // scratch sizes (conv_pick_cfg, pick_pos_major, conv_group_plan -> group_splitks_scheduled); then ron_detect at a few batch sizes,
 // which walks launch_conv / launch_conv_group up to the launch itself (tile counts, split-K slices, tile order, entry lists, the
 // post-processing's workspace layout) and ron_clone (a second slot taking over the plans).  Index tables overrun or integer
-// overflow in any of it ends the run with a sanitizer report and a non-zero exit code.
+// overflow in any of it ends the run with a sanitizer report and a non-zero exit code.  Then the argument passes of the single-operator
+// entry points.  With RON_PLAN_TRACE=<file> the library writes a line per skipped launch and this program a heading per context and
+// pass: the trace two trees must agree on when a change is meant to leave every plan alone (tests/test_plan_trace_cpu.py).
 #include <math.h>
+#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <time.h>
 
 #include <string>
 #include <vector>
@@ -37,7 +41,21 @@ void __hipRegisterManagedVar(void*, void**, void*, const char*, size_t, unsigned
     }                                                                                      \
   } while (0)
 
+// RON_PLAN_TRACE=<file>: the library appends one line per launch it skips (csrc/common.h); the headings of this program go to the same
+// file, so that every context and argument pass is a section of its own (tests/test_plan_trace_cpu.py digests them one by one).
+static FILE* g_trace = nullptr;
+static void trace_note(const char* fmt, ...) {
+  if (g_trace == nullptr) return;
+  va_list ap;
+  va_start(ap, fmt);
+  vfprintf(g_trace, fmt, ap);
+  va_end(ap);
+  fputc('\n', g_trace);
+  fflush(g_trace);
+}
+
 static int run(int variant, int dtype, uint32_t flags, int max_batch, bool detect) {
+  trace_note("context %d %d 0x%x %d", variant, dtype, flags, max_batch);
   ron_config cfg;
   memset(&cfg, 0, sizeof(cfg));
   cfg.variant = variant; cfg.dtype = dtype;
@@ -558,15 +576,152 @@ static int conv_envelope() {
   return 0;
 }
 
+// plan_conv and launch_conv_group through the single-operator entry points, with what the graphs never set: every tile configuration
+// forced (refusals included: their status and message go into the trace), forced split factors, centre-tap-only columns, the transposed
+// convolution, the fused pool with and without its second output, the two-output heads, the grouped pair and RON_IGEMM224=0.  The
+// weights are host memory (the entry points pack them); activations are fake device addresses nobody dereferences in a dry run.
+static int conv_planner_arguments() {
+  struct Case { int n, h, w, cin, cout, k, stride, dil, transpose, pool, center_from; bool all_cfgs; };
+  const Case cases[] = {
+      {32, 40, 40, 256, 512, 3, 1, 1, 0, 0, 0, true},    // two column tiles of 256, taps innermost
+      {4, 40, 40, 256, 512, 3, 1, 1, 0, 0, 0, true},     // about one round of 256 x 128 tiles
+      {32, 40, 40, 256, 210, 3, 1, 1, 0, 0, 0, true},    // 193 .. 224 output channels: the 256 x 224 form
+      {8, 40, 40, 128, 128, 3, 1, 1, 0, 0, 0, true},     // Cout = 128
+      {32, 160, 160, 128, 128, 3, 1, 1, 0, 0, 0, false}, // ... on a map that fills the chip (conv2_x)
+      {4, 80, 80, 64, 64, 3, 1, 1, 0, 0, 0, true},       // 64 channels: the resident-weight and patch kernels
+      {2, 5, 7, 64, 24, 3, 1, 1, 0, 0, 0, true},         // one tile of 128 x 64
+      {32, 10, 10, 512, 1024, 3, 1, 6, 0, 0, 0, false},  // few fat tiles, long K, dilation 6 on a 10 x 10 map (filter rows to skip)
+      {8, 10, 10, 128, 256, 7, 1, 1, 0, 0, 0, true},     // 7 x 7 on 10 x 10: position-major rows
+      {32, 10, 10, 1024, 1024, 1, 1, 1, 0, 0, 0, false}, // a plain GEMM
+      {32, 40, 40, 128, 768, 3, 1, 1, 0, 0, 512, true},  // centre-tap-only columns behind two long column tiles
+      {8, 20, 20, 128, 384, 3, 1, 1, 0, 0, 128, false},  // ... behind one of 128
+      {32, 10, 10, 256, 256, 2, 2, 1, 1, 0, 0, true},    // transposed, kernel == stride
+      {8, 20, 20, 256, 256, 2, 2, 1, 0, 0, 0, true},     // stride 2
+      {32, 40, 40, 256, 512, 3, 1, 1, 0, 1, 0, true},    // fused pool
+      {3, 19, 19, 128, 256, 3, 1, 1, 0, 1, 0, false},    // ... on an odd map
+  };
+  float* const x = reinterpret_cast<float*>(uintptr_t(1) << 40);          // fake device addresses
+  float* const y = reinterpret_cast<float*>(uintptr_t(2) << 40);
+  float* const y2 = reinterpret_cast<float*>(uintptr_t(3) << 40);
+  const int ncfg = ron_conv_num_tile_cfgs();
+  std::vector<float> w, bias(4096, 0.5f);
+  auto desc = [&](const Case& c, int dtype, int cfg, int splitk) {
+    ron_conv_desc d;
+    memset(&d, 0, sizeof d);
+    d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.cout = c.cout; d.kh = d.kw = c.k; d.stride = c.stride; d.dilation = c.dil;
+    d.relu = 1; d.transpose = c.transpose; d.dtype = dtype; d.tile_cfg = cfg; d.pool = c.pool; d.splitk = splitk; d.center_from = c.center_from;
+    w.assign((size_t)c.k * c.k * c.cin * c.cout, 0.01f);
+    return d;
+  };
+  auto note_rc = [](int rc) { trace_note("-> %d %s", rc, rc != 0 ? ron_last_error() : ""); };
+  int launched = 0;
+  for (const Case& c : cases) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16X3, (int)RON_DTYPE_F32}) {
+      if (dtype != RON_DTYPE_BF16 && !c.all_cfgs) continue;
+      for (int cfg = -1; cfg < (c.all_cfgs ? ncfg + 1 : 0); ++cfg) {         // (ncfg itself: out of range)
+        for (int splitk : {-1, 1, 2, 7}) {
+          // (every call packs the weights again: the other dtypes take the forced configurations with the library's own split factor only)
+          if (cfg >= 0 && (splitk == 1 || (dtype != RON_DTYPE_BF16 && splitk != -1))) continue;
+          if (cfg < 0 && dtype != RON_DTYPE_BF16 && (splitk == 1 || splitk == 7)) continue;
+          const ron_conv_desc d = desc(c, dtype, cfg, splitk);
+          trace_note("conv %d %d %d %d %d k %d stride %d dil %d transpose %d pool %d center_from %d dtype %d cfg %d splitk %d", c.n, c.h, c.w, c.cin,
+                     c.cout, c.k, c.stride, c.dil, c.transpose, c.pool, c.center_from, dtype, cfg, splitk);
+          const int rc = ron_conv2d_nhwc(&d, x, w.data(), bias.data(), c.pool || c.transpose ? nullptr : y2, y, nullptr);
+          note_rc(rc);
+          if (rc != RON_OK && rc != RON_ERR_INVALID) return 1;
+          if (cfg < 0 && rc != RON_OK) return 1;                              // the library's own choice is never refused
+          launched += rc == RON_OK;
+          if (cfg < 0 && splitk < 0) {
+            int32_t plan[4] = {0, 0, 0, 0}, n_tile = 0;
+            CHECK(ron_conv_plan(&d, plan));
+            CHECK(ron_conv_plan_n_tile(&d, &n_tile));
+            trace_note("plan %d %d %d %d n_tile %d", plan[0], plan[1], plan[2], plan[3], n_tile);
+          }
+          if (c.pool && (cfg < 0 || splitk < 0)) {
+            trace_note("... with the un-pooled map as a second output");
+            note_rc(ron_conv2d_pool2_nhwc(&d, x, w.data(), bias.data(), y, y2, nullptr));
+          }
+        }
+      }
+    }
+  }
+  if (launched < 100) return 1;
+  // RON_IGEMM224=0 (read per call): the 256-column tile for 193 .. 224 output channels, chosen and forced, with split factors
+  setenv("RON_IGEMM224", "0", 1);
+  for (int cfg : {-1, 0, 7}) {
+    for (int splitk : {-1, 2}) {
+      const ron_conv_desc d = desc(cases[2], RON_DTYPE_BF16, cfg, splitk);
+      int32_t n_tile = 0;
+      trace_note("RON_IGEMM224=0 cfg %d splitk %d", cfg, splitk);
+      note_rc(ron_conv2d_nhwc(&d, x, w.data(), bias.data(), nullptr, y, nullptr));
+      CHECK(ron_conv_plan_n_tile(&d, &n_tile));
+      trace_note("n_tile %d", n_tile);
+      if (n_tile == 224) return 1;
+    }
+  }
+  unsetenv("RON_IGEMM224");
+  // the two-output heads (an SSD feature layer's class and box convolutions as one launch)
+  const Case heads[] = {{16, 64, 64, 256, 100, 3, 1, 1, 0, 0, 0, true}, {1, 8, 8, 256, 150, 3, 1, 1, 0, 0, 0, true}, {32, 32, 32, 256, 210, 3, 1, 1, 0, 0, 0, true}};
+  for (const Case& c : heads) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F32}) {
+      for (int cfg = -1; cfg < ncfg; ++cfg) {
+        for (int splitk : {-1, 2, 7}) {
+          if (cfg >= 0 && splitk == 7) continue;
+          const ron_conv_desc d = desc(c, dtype, cfg, splitk);
+          trace_note("heads %d %d %d %d %d first %d dtype %d cfg %d splitk %d", c.n, c.h, c.w, c.cin, c.cout, c.cout * 4 / 5 + 4, dtype, cfg, splitk);
+          const int rc = ron_conv2d_heads_nhwc(&d, c.cout * 4 / 5 + 4, x, w.data(), bias.data(), y, y2, nullptr);
+          note_rc(rc);
+          if (cfg < 0 && rc != RON_OK) return 1;
+        }
+      }
+    }
+  }
+  // fp32-output heads: one, two on their own, and the grouped pair of 256 x 256 tiles with its own and with forced split factors
+  const Case pairs[][2] = {{{32, 10, 10, 256, 210, 3, 1, 1, 0, 0, 0, true}, {32, 5, 5, 256, 210, 3, 1, 1, 0, 0, 0, true}},
+                           {{4, 20, 20, 512, 210, 3, 1, 1, 0, 0, 0, true}, {4, 10, 10, 512, 256, 3, 1, 1, 0, 0, 0, true}},
+                           {{32, 40, 40, 128, 210, 3, 1, 1, 0, 0, 0, true}, {32, 20, 20, 128, 512, 1, 1, 1, 0, 0, 0, true}}};
+  std::vector<float> wb;
+  for (const auto& p : pairs) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16, (int)RON_DTYPE_F16X3, (int)RON_DTYPE_F32}) {
+      for (int n224 : {1, 0}) {
+        if (n224) unsetenv("RON_IGEMM224"); else setenv("RON_IGEMM224", "0", 1);
+        const int sks[][2] = {{-1, -1}, {1, 1}, {2, 7}, {7, 2}, {2, -1}};
+        for (const auto& sk : sks) {
+          const ron_conv_desc db = desc(p[1], dtype, -1, sk[1]);
+          wb = w;
+          const ron_conv_desc da = desc(p[0], dtype, -1, sk[0]);
+          for (int grouped : {0, 1}) {
+            int32_t widths[2] = {0, 0};
+            trace_note("f32out pair %d x %d x %d + %d x %d x %d dtype %d n224 %d splitk %d %d grouped %d", p[0].n, p[0].h, p[0].cout, p[1].n, p[1].h,
+                       p[1].cout, dtype, n224, sk[0], sk[1], grouped);
+            CHECK(ron_conv2d_f32out_nhwc(&da, x, w.data(), bias.data(), y, &db, x, wb.data(), bias.data(), y2, grouped, widths, nullptr));
+            trace_note("widths %d %d", widths[0], widths[1]);
+          }
+        }
+      }
+    }
+  }
+  unsetenv("RON_IGEMM224");
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (getenv("RON_PLAN_ONLY") == nullptr) {
     fprintf(stderr, "plan_sweep: run with RON_PLAN_ONLY=1 (a dry run: this binary holds no device code)\n");
     return 2;
   }
   const bool quick = argc > 1 && strcmp(argv[1], "--quick") == 0;
+  if (const char* path = getenv("RON_PLAN_TRACE")) {
+    FILE* f = fopen(path, "w");           // a fresh file; the library appends to it from its first skipped launch on
+    if (f != nullptr) fclose(f);
+    g_trace = fopen(path, "a");
+    if (g_trace == nullptr) { fprintf(stderr, "plan_sweep: cannot write %s\n", path); return 2; }
+  }
   const int batches_all[] = {1, 2, 3, 4, 6, 8, 12, 13, 16, 23, 24, 32, 48, 64};
   const uint32_t plans[] = {0u, RON_CFG_LEVEL_GROUPS, RON_CFG_BATCH_GROUPS, RON_CFG_NO_GROUPS, RON_CFG_NO_HALO_SKIP};
   int runs = 0;
+  timespec t0, t1;
+  clock_gettime(CLOCK_MONOTONIC, &t0);
   // reducedfc and SSD-512: every head plan x every batch size of the ladder (the plan tables change at 12 / 13 and 23 / 24)
   for (int variant : {(int)RON_VARIANT_REDUCEDFC, (int)RON_VARIANT_SSD512}) {
     for (uint32_t plan : plans) {
@@ -607,34 +762,49 @@ int main(int argc, char** argv) {
     if (run(RON_VARIANT_REDUCEDFC, RON_DTYPE_F16, RON_CFG_FUSE_POOLS | RON_CFG_NO_STEM2, 32, true)) return 1;
     runs += 2;
   }
+  clock_gettime(CLOCK_MONOTONIC, &t1);
+  printf("plan_sweep: %d contexts created, planned and run dry in %.1f s\n", runs, (double)(t1.tv_sec - t0.tv_sec) + 1e-9 * (double)(t1.tv_nsec - t0.tv_nsec));
+  trace_note("pass loss_arguments");
   if (loss_arguments()) {
     fprintf(stderr, "plan_sweep: ron_losses / ron_losses_grad argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass conv_backward_arguments");
   if (conv_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_conv2d_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass stem_backward_arguments");
   if (stem_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_conv2d_stem_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass op_backward_arguments");
   if (op_backward_arguments()) {
     fprintf(stderr, "plan_sweep: ron_maxpool2x2_backward_nhwc / ron_conv2d_k2s2_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass batchnorm_arguments");
   if (batchnorm_arguments()) {
     fprintf(stderr, "plan_sweep: ron_batchnorm_train_nhwc / ron_batchnorm_backward_nhwc planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass optimizer_arguments");
   if (optimizer_arguments()) {
     fprintf(stderr, "plan_sweep: ron_optimizer_step planning / argument handling: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass conv_envelope");
   if (conv_envelope()) {
     fprintf(stderr, "plan_sweep: the argument envelope of ron_conv_desc: %s\n", ron_last_error());
     return 1;
   }
+  trace_note("pass conv_planner_arguments");
+  if (conv_planner_arguments()) {
+    fprintf(stderr, "plan_sweep: plan_conv / launch_conv_group through the single-operator entry points: %s\n", ron_last_error());
+    return 1;
+  }
+  if (g_trace != nullptr) fclose(g_trace);
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
   return 0;
 }
