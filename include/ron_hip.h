@@ -680,8 +680,9 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
  * each be NULL (not computed); every element of a non-NULL output is written.  x may be NULL when dw is, w when dx is.
  * x, y and dy must be 16-byte aligned (they are read 16 bytes at a time), the workspace 256-byte aligned.
  *
- * Accepted descriptors: stride 1, kh == kw in {1, 3}, dilation 1 .. 31 (the envelope of ron_conv_desc above: the data
- * gradient is a forward launch), dtype bf16 / fp16, cin a multiple of 64, any cout >= 1; relu 0 or 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1.  d->splitk is the pixel-split
+ * Accepted descriptors: stride 1, kh == kw in {1, 3} at dilation 1 .. 31 (the envelope of ron_conv_desc above: the data
+ * gradient is a forward launch) or 7 x 7 at dilation 1 (fc6 of the `full` variant; 5 x 5 and a dilated 7 x 7 have no user and
+ * are refused), dtype bf16 / fp16, cin a multiple of 64, any cout >= 1; relu 0 or 1; transpose, pool, center_from, in_cstride, in_coff = 0 and tile_cfg = -1.  d->splitk is the pixel-split
  * factor of the weight gradient: -1 = by shape, 1 = off, S = forced (capped at the number of 32-pixel steps and where the
  * fp32 partial sums of the slices would reach 2 GiB).  Anything else - a NULL y with relu set, a misaligned pointer and a
  * workspace that is too small included - is RON_ERR_INVALID with a message, before any HIP call.
@@ -693,6 +694,46 @@ int ron_stem2_workgroups_per_cu(int dtype, int32_t* per_cu);
 int64_t ron_conv2d_backward_workspace_bytes(const ron_conv_desc* d);
 int ron_conv2d_backward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* y, const float* dy,
                              float* dx, float* dw, float* dbias, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Convolution forward for training: ONE convolution from DEVICE weights, the forward that ron_conv2d_backward_nhwc,
+ * ron_conv2d_stem_backward_nhwc and ron_conv2d_k2s2_backward_nhwc differentiate.  Its contract is that of
+ * ron_conv2d_backward_nhwc: a real entry point that enqueues on `stream`, allocates nothing, never synchronises, honours the
+ * dry-run mode and assumes nothing about the workspace's contents; every element of y is written.
+ *
+ * All pointers are DEVICE fp32, w and bias included (the optimizer changes them on the device every step; nothing is cached
+ * between calls): x [n,h,w,cin], w HWIO [kh,kw,cin,cout] ([2,2,cout,cin] when d->transpose), bias [cout] or NULL, y
+ * [n,ho,wo,cout] with (ho, wo) = (h, w) at stride 1, (h/2, w/2) for the strided and (2h, 2w) for the transposed form.  x and y
+ * must be 16-byte aligned (the x of the 3-channel stem: 4-byte), w and bias 4-byte, the workspace 256-byte aligned.
+ *
+ * The arithmetic is ron_conv2d_nhwc's: operands rounded to d->dtype, fp32 accumulation, + fp32 bias, ReLU when d->relu, y
+ * delivered as storage-type values in fp32.  It is the same launch on the same packed operands with the by-shape plan
+ * (tile_cfg = -1, splitk = -1) - only the packing moved from the host to the stream - so for the same inputs y has the same
+ * bytes as ron_conv2d_nhwc's.
+ *
+ * Accepted descriptors (dtype bf16 / fp16; relu 0 or 1; pool, center_from, in_cstride, in_coff = 0; tile_cfg = -1,
+ * splitk = -1):
+ *   - stride 1 SAME, kh == kw in {1, 3} at dilation 1 .. 31, or 7 x 7 at dilation 1; cin a multiple of 64, any cout >= 1;
+ *   - the stem: cin 3, cout 64, 3 x 3, dilation 1, any width (with relu the stem kernel, without it im2col + one GEMM step:
+ *     the routes of ron_conv2d_nhwc);
+ *   - kh = kw = stride = 2, transpose 0: h and w even, cin a multiple of 64;
+ *   - kh = kw = stride = 2, transpose 1: cin a multiple of 64, cout a multiple of 128.
+ * There is no residual argument: a fused relu(y + residual) loses the mask of the inner ReLU that the backward needs, so the
+ * join stays with the caller.  Out of scope: fp32 and f16x3 arithmetic, fused pools, channel slices, forced tile
+ * configurations, the padded convolutions of the SSD extra blocks (ron_conv2d_nhwc runs those).
+ * Anything else - a NULL x, w or y, a misaligned pointer, a workspace that is too small, a packed tensor that would reach
+ * 2 GiB - is RON_ERR_INVALID with a message, before any HIP call.
+ * ron_conv2d_forward_workspace_bytes is host arithmetic only; -1 + ron_last_error() on a descriptor the call would refuse.
+ * ---------------------------------------------------------------------------------------- */
+int64_t ron_conv2d_forward_workspace_bytes(const ron_conv_desc* d);
+int ron_conv2d_forward_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                            void* workspace, int64_t workspace_bytes, void* stream);
+/* Tooling (tools/conv_forward_time.py): the same call restricted to some of its steps, so that each can be timed alone on a
+ * workspace an earlier full call has filled: the pack of x, the packs of w and the bias, the convolution launch, the unpack
+ * into y.  Same checks, same contract; RON_FWD_PART_ALL is ron_conv2d_forward_nhwc. */
+enum { RON_FWD_PART_X = 1, RON_FWD_PART_W = 2, RON_FWD_PART_LAUNCH = 4, RON_FWD_PART_UNPACK = 8, RON_FWD_PART_ALL = 15 };
+int ron_conv2d_forward_parts_nhwc(const ron_conv_desc* d, const float* x, const float* w, const float* bias, float* y,
+                                  void* workspace, int64_t workspace_bytes, int parts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of the 3-channel stem convolution conv1_1 (3 -> 64 channels, 3x3, stride 1, SAME): its weight and bias

@@ -207,6 +207,9 @@ SIGNATURES = {
     'ron_stem2_workgroups_per_cu': (C.c_int, [C.c_int, C.POINTER(C.c_int32)]),
     'ron_conv2d_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_conv2d_forward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
+    'ron_conv2d_forward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, C.c_int64, _P]),
+    'ron_conv2d_forward_parts_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, C.c_int64, C.c_int, _P]),
     'ron_conv2d_stem_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_stem_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_maxpool2x2_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -660,12 +660,49 @@ def conv2d_stem_backward_nhwc(x, dy, y=None, relu=True, dtype='bf16', splitk=-1,
     return dw, db
 
 
+# --------------------------------------------------------------------------- #
+# convolution forward for training (ron_conv2d_forward_nhwc): device weights, the current stream, no synchronisation
+# --------------------------------------------------------------------------- #
+def _forward_desc(n, h, w, cin, cout, k, stride, dilation, relu, transpose, dtype):
+    return _lib.ConvDesc(n, h, w, cin, cout, k, k, stride, dilation, int(relu), int(transpose), _lib.DTYPES[dtype], -1, 0, 0, 0, -1, 0)
+
+
+def conv2d_forward_workspace_bytes(n, h, w, cin, cout, k=3, stride=1, dilation=1, relu=True, transpose=False, dtype='bf16'):
+    """Bytes of workspace conv2d_forward_nhwc needs for this convolution (n, h, w: the input x; host arithmetic; raises on a
+    descriptor the library refuses)."""
+    return _desc_workspace_bytes('conv2d_forward', _forward_desc(n, h, w, cin, cout, k, stride, dilation, relu, transpose, dtype))
+
+
+def conv2d_forward_nhwc(x, w, bias=None, relu=True, dilation=1, stride=1, transpose=False, dtype='bf16', workspace=None):
+    """y = act(conv(x, w) + bias) from DEVICE weights: the training forward.  x [N,H,W,Cin], w HWIO [k,k,Cin,Cout] ([2,2,Cout,Cin] with
+    `transpose`) and bias [Cout] or None are GPU fp32 tensors; nothing is copied to the host, the call enqueues on the current stream
+    and never synchronises.  Stride-1 SAME 1x1 / 3x3 (any dilation) / 7x7, the 3 -> 64 channel stem, and the 2x2 stride-2 convolution
+    (`stride=2`) and transposed convolution (`stride=2, transpose=True`); bf16 / fp16.  The arithmetic and the result's bytes are
+    conv2d_nhwc's.  `workspace`: a uint8 GPU tensor of at least conv2d_forward_workspace_bytes(...) bytes, or None for the cached
+    per-device, per-stream buffer."""
+    for name, t in (('x', x), ('w', w), ('bias', bias)):
+        if t is not None and not (hasattr(t, 'is_cuda') and t.is_cuda and t.dtype == torch.float32):
+            raise _lib.RonError('conv2d_forward_nhwc: %s must be a GPU fp32 tensor (host weights: conv2d_nhwc)' % name)
+    x, w = x.contiguous(), w.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    n, h, wd, cin = x.shape
+    k = w.shape[0]
+    cout = w.shape[2] if transpose else w.shape[3]
+    assert tuple(w.shape) == ((k, k, cout, cin) if transpose else (k, k, cin, cout)), 'w %s does not belong to x %s' % (tuple(w.shape), tuple(x.shape))
+    assert bias is None or tuple(bias.shape) == (cout,)
+    d = _forward_desc(n, h, wd, cin, cout, k, stride, dilation, relu, transpose, dtype)
+    nbytes = _desc_workspace_bytes('conv2d_forward', d)
+    ws = _workspace(x.device, nbytes) if workspace is None else workspace
+    ho, wo = (h * stride, wd * stride) if transpose else (h // stride, wd // stride)
+    y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
+    check(lib().ron_conv2d_forward_nhwc(C.byref(d), ptr(x), ptr(w), ptr(bias), ptr(y), ptr(ws), int(ws.numel()), current_stream()))
+    return y
+
+
 class _Conv2dNhwcFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, relu, dilation, dtype):
-        # ron_conv2d_nhwc takes HOST weights and synchronises: a convenience for tests and small experiments, not the training path
-        b = None if bias is None else bias.detach().cpu().numpy()
-        y = conv2d_nhwc(x.detach(), w.detach().cpu().numpy(), b, dilation=dilation, relu=relu, dtype=dtype)
+        y = conv2d_forward_nhwc(x.detach(), w.detach(), None if bias is None else bias.detach(), relu=relu, dilation=dilation, dtype=dtype)
         ctx.save_for_backward(x, w, y)
         ctx.cfg = (relu, dilation, dtype, bias is not None)
         return y
@@ -690,8 +727,9 @@ class _Conv2dNhwcFn(torch.autograd.Function):
 def conv2d_nhwc_fn(x, w, bias, relu=True, dilation=1, dtype='bf16'):
     """act(conv_SAME(x, w) + bias), stride 1, as a torch.autograd.Function: x [N,H,W,Cin], w HWIO, bias [Cout] or None, GPU fp32 tensors.
 
-    The forward is ron_conv2d_nhwc, which packs the weights on the HOST (a device-to-host copy of w) and synchronises: a
-    convenience for tests and small experiments, not the training path.  The backward is ONE ron_conv2d_backward_nhwc call on the
+    k = 1, 3 (any dilation) or 7 (dilation 1).  The forward is ONE ron_conv2d_forward_nhwc call (conv2d_forward_nhwc): the weights
+    stay on the device and are packed there, on the current stream, without a synchronisation - the training path; its result has the
+    bytes of conv2d_nhwc's.  The backward is ONE ron_conv2d_backward_nhwc call on the
     current stream, computing only the gradients autograd asks for; tensors that do not require grad get None.  A 3-channel x (the
     image in front of conv1_1) has ONE ron_conv2d_stem_backward_nhwc call instead, for dw and db; asking for its dx raises RonError."""
     return _Conv2dNhwcFn.apply(x, w, bias, relu, dilation, dtype)
@@ -759,8 +797,8 @@ def maxpool2x2_nhwc_fn(x, dtype='bf16'):
 class _Conv2dK2s2NhwcFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w, bias, relu, transpose, dtype):
-        b = None if bias is None else bias.detach().cpu().numpy()
-        y = conv2d_nhwc(x.detach(), w.detach().cpu().numpy(), b, stride=2, relu=relu, transpose=transpose, dtype=dtype)
+        y = conv2d_forward_nhwc(x.detach(), w.detach(), None if bias is None else bias.detach(), relu=relu, stride=2, transpose=transpose,
+                                dtype=dtype)
         ctx.save_for_backward(x, w, y)
         ctx.cfg = (relu, transpose, dtype, bias is not None)
         return y
@@ -777,8 +815,8 @@ class _Conv2dK2s2NhwcFn(torch.autograd.Function):
 
 def conv2d_k2s2_nhwc_fn(x, w, bias, relu=True, transpose=False, dtype='bf16'):
     """act(conv(x, w) + bias) for the 2x2 stride-2 convolution (w HWIO) or, with `transpose`, the 2x2 stride-2 transposed
-    convolution (w [2,2,Cout,Cin]) as a torch.autograd.Function on GPU fp32 tensors.  The forward is ron_conv2d_nhwc (host weights,
-    synchronises: tests and small experiments; its transposed form wants Cout a multiple of 128); the backward is ONE
+    convolution (w [2,2,Cout,Cin]) as a torch.autograd.Function on GPU fp32 tensors.  The forward is ONE ron_conv2d_forward_nhwc call
+    (device weights, the current stream, no synchronisation; its transposed form wants Cout a multiple of 128); the backward is ONE
     ron_conv2d_k2s2_backward_nhwc call on the current stream, computing only the gradients autograd asks for."""
     return _Conv2dK2s2NhwcFn.apply(x, w, bias, relu, transpose, dtype)
 

@@ -188,6 +188,85 @@ static int conv_backward_arguments() {
   return 0;
 }
 
+// ron_conv2d_forward_nhwc in the dry run: the descriptor checks, the ConvLaunch of every route (plain, 7 x 7, the stem with and without
+// its kernel, 2 x 2 stride 2, transposed, the resident-weight images), the workspace and the refusals, over the case table of
+// tests/conv_fwd_cases.py plus the layer shapes of tools/conv_forward_time.py; and the 7 x 7 filter through ron_conv2d_backward_nhwc.
+// Part of the FULL sweep only: the launch trace of the quick sweep is pinned section by section (tests/test_plan_trace_cpu.py).
+static int conv_forward_arguments() {
+  struct Case { int n, h, w, cin, cout, k, dil, stride, tr; };
+  const Case cases[] = {{1, 1, 1, 64, 64, 3, 1, 1, 0},     {2, 5, 7, 64, 24, 3, 1, 1, 0},      {3, 3, 3, 128, 126, 3, 1, 1, 0},   {1, 10, 10, 64, 192, 3, 6, 1, 0},
+                        {2, 19, 19, 192, 64, 1, 1, 1, 0},  {1, 38, 38, 320, 256, 3, 1, 1, 0},  {2, 40, 40, 64, 64, 3, 1, 1, 0},   {2, 5, 7, 64, 24, 7, 1, 1, 0},
+                        {1, 10, 10, 128, 192, 7, 1, 1, 0}, {1, 10, 10, 64, 64, 3, 3, 1, 0},    {2, 3, 5, 64, 1, 3, 1, 1, 0},      {2, 4, 6, 128, 65, 1, 1, 1, 0},
+                        {2, 8, 32, 3, 64, 3, 1, 1, 0},     {2, 9, 37, 3, 64, 3, 1, 1, 0},      {2, 6, 8, 64, 24, 2, 1, 2, 0},     {1, 2, 2, 128, 128, 2, 1, 2, 0},
+                        {2, 3, 5, 64, 128, 2, 1, 2, 1},    {1, 1, 1, 128, 256, 2, 1, 2, 1},    {1, 8, 32, 64, 64, 3, 1, 1, 0},
+                        {32, 320, 320, 3, 64, 3, 1, 1, 0}, {32, 320, 320, 64, 64, 3, 1, 1, 0}, {32, 160, 160, 64, 128, 3, 1, 1, 0}, {32, 80, 80, 256, 256, 3, 1, 1, 0},
+                        {32, 40, 40, 512, 512, 3, 1, 1, 0}, {32, 10, 10, 512, 1024, 3, 3, 1, 0}, {32, 10, 10, 512, 4096, 7, 1, 1, 0}, {32, 10, 10, 4096, 4096, 1, 1, 1, 0},
+                        {32, 10, 10, 4096, 512, 2, 1, 2, 0}, {32, 20, 20, 512, 512, 2, 1, 2, 1}, {32, 40, 40, 512, 210, 3, 1, 1, 0}};
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (const Case& c : cases) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      for (int relu : {0, 1}) {
+        ron_conv_desc d;
+        memset(&d, 0, sizeof d);
+        d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.cout = c.cout; d.kh = d.kw = c.k; d.stride = c.stride; d.dilation = c.dil;
+        d.relu = relu; d.transpose = c.tr; d.dtype = dtype; d.tile_cfg = -1; d.splitk = -1;
+        const int64_t bytes = ron_conv2d_forward_workspace_bytes(&d);
+        if (bytes <= 0 || bytes % 256 != 0) return 1;
+        CHECK(ron_conv2d_forward_nhwc(&d, f, f, f, f, ws, bytes, nullptr));
+        CHECK(ron_conv2d_forward_nhwc(&d, f, f + 1, nullptr, f, ws, bytes, nullptr));      // no bias; a w that is only 4-byte aligned
+        CHECK(ron_conv2d_forward_parts_nhwc(&d, f, f, f, f, ws, bytes, RON_FWD_PART_W | RON_FWD_PART_UNPACK, nullptr));
+        if (c.cin == 3) CHECK(ron_conv2d_forward_nhwc(&d, f + 1, f, f, f, ws, bytes, nullptr));
+        else if (ron_conv2d_forward_nhwc(&d, f + 1, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, f, f, f, f + 1, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, f, f, f, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, f, f, f, f, static_cast<char*>(ws) + 128, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, nullptr, f, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, f, nullptr, f, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_nhwc(&d, f, f, f, nullptr, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_parts_nhwc(&d, f, f, f, f, ws, bytes, 0, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv2d_forward_parts_nhwc(&d, f, f, f, f, ws, bytes, 16, nullptr) != RON_ERR_INVALID) return 1;
+        ron_conv_desc bad = d;
+        bad.dtype = RON_DTYPE_F16X3;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.dtype = RON_DTYPE_F32;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.cin = 96;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.kh = bad.kw = 5;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.pool = 1;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.tile_cfg = 1;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.splitk = 2;
+        if (ron_conv2d_forward_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.center_from = 8;
+        if (ron_conv2d_forward_nhwc(&bad, f, f, f, f, ws, (int64_t)1 << 40, nullptr) != RON_ERR_INVALID) return 1;
+        if (c.k == 7 && c.stride == 1) {
+          bad = d; bad.dilation = 2;
+          if (ron_conv2d_forward_workspace_bytes(&bad) != -1 || ron_conv2d_backward_workspace_bytes(&bad) != -1) return 1;
+          for (int splitk : {-1, 1, 3, 1000000}) {
+            ron_conv_desc g = d;
+            g.splitk = splitk;
+            const int64_t gb = ron_conv2d_backward_workspace_bytes(&g);
+            if (gb <= 0 || gb % 256 != 0) return 1;
+            CHECK(ron_conv2d_backward_nhwc(&g, f, f, relu ? f : nullptr, f, f, f, f, ws, gb, nullptr));
+            if (ron_conv2d_backward_nhwc(&g, f, f, relu ? f : nullptr, f, f, f, f, ws, gb - 1, nullptr) != RON_ERR_INVALID) return 1;
+          }
+        }
+      }
+    }
+  }
+  // a packed tensor of 2 GiB: conv1_2 at batch 256 (x: 256 * 321 * 321 * 64 * 2 bytes)
+  ron_conv_desc big;
+  memset(&big, 0, sizeof big);
+  big.n = 256; big.h = big.w = 320; big.cin = big.cout = 64; big.kh = big.kw = 3; big.stride = 1; big.dilation = 1; big.relu = 1;
+  big.dtype = RON_DTYPE_BF16; big.tile_cfg = -1; big.splitk = -1;
+  if (ron_conv2d_forward_workspace_bytes(&big) != -1) return 1;
+  return 0;
+}
+
 // ron_conv2d_stem_backward_nhwc in the dry run: the descriptor checks, the pixel slices and the workspace, over the case table of
 // tests/stem_grad_cases.py plus the layer itself (tools/stem_backward_time.py) and the last accepted pixel count, every dtype and pixel
 // split, and the refusals; pointers are used for arithmetic only.
@@ -803,6 +882,13 @@ int main(int argc, char** argv) {
   if (conv_planner_arguments()) {
     fprintf(stderr, "plan_sweep: plan_conv / launch_conv_group through the single-operator entry points: %s\n", ron_last_error());
     return 1;
+  }
+  if (!quick) {
+    trace_note("pass conv_forward_arguments");
+    if (conv_forward_arguments()) {
+      fprintf(stderr, "plan_sweep: ron_conv2d_forward_nhwc planning / argument handling (and the 7 x 7 backward): %s\n", ron_last_error());
+      return 1;
+    }
   }
   if (g_trace != nullptr) fclose(g_trace);
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
