@@ -736,6 +736,73 @@ int ron_conv2d_forward_parts_nhwc(const ron_conv_desc* d, const float* x, const 
                                   void* workspace, int64_t workspace_bytes, int parts, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Convolution chain: a SEQUENCE of layers - stride-1 SAME convolutions and 2x2 stride-2 SAME max-pools - forward in one call
+ * and backward in one call: conv1_2 .. fc7 of both RON-320 variants, conv1_2 .. conv5_3 of the SSD networks.  Between the
+ * layers, and between the two calls, activations and gradients stay storage-type (bf16 / fp16) halo tensors inside the
+ * caller's workspace; fp32 dense NHWC appears only where data enters or leaves: x, y, the taps, dx, and the weights, biases
+ * and their gradients.  The contract is that of ron_conv2d_forward_nhwc / ron_conv2d_backward_nhwc: both calls enqueue on
+ * `stream`, allocate nothing, never synchronise, honour the dry-run mode; ron_conv_chain_forward assumes nothing about the
+ * workspace's contents; everything refusable is RON_ERR_INVALID with a message, before any HIP call.
+ *
+ * The chain starts from a map [n,h,w,cin], cin a multiple of 64 (the stem's caller feeds its output as x and takes dx into
+ * ron_conv2d_stem_backward_nhwc).  Layers:
+ *   RON_CHAIN_CONV   k in {1, 3} at dilation 1 .. 31, or k = 7 at dilation 1; relu and has_bias 0 or 1; cout >= 1 on the last
+ *                    layer, a multiple of 64 on a layer that feeds another one: what ron_conv2d_forward_nhwc and
+ *                    ron_conv2d_backward_nhwc accept for a stride-1 convolution;
+ *   RON_CHAIN_POOL2  the 2x2 stride-2 SAME max-pool, odd maps included (ron_maxpool2x2_nhwc, ron_maxpool2x2_backward_nhwc);
+ *                    k, dilation, cout, relu, has_bias are ignored.
+ * A convolution layer may be flagged `tap`: the forward also delivers its output as fp32 dense (taps[i]); the backward takes
+ * an fp32 dense gradient for it (dtaps[i], NULL: none; dtaps itself may be NULL), and the gradient that enters the layer's ReLU
+ * mask is float(the next layer's dx) + dtaps[i], added in fp32 before the one rounding - the sum autograd forms when the
+ * operators are chained.  The last layer's output is always delivered (y) and dy is its gradient; a tap flag on it delivers
+ * taps[i] as well and adds dtaps[i] to dy.  A pool layer cannot be tapped.
+ *
+ * Arithmetic: every convolution layer runs the launches ron_conv2d_forward_nhwc / ron_conv2d_backward_nhwc make for it on
+ * its own (the same plan code, csrc/conv_train.h: views, by-shape tile and split, channel padding; only the base pointers
+ * differ), the same weight packs and column sums, and the pools compare and route the same stored values.  y, every tap, dx,
+ * every dw and every dbias therefore have the bytes that the per-operator entry points give when they are chained through
+ * fp32, for any input.
+ *
+ * Pointer arrays (w, bias, taps, dtaps, dw, dbias) are HOST arrays of num_layers DEVICE pointers; entries of pool layers are
+ * ignored.  w[i] is fp32 HWIO [k,k,cin_i,cout_i], packed on the stream at every call (nothing is cached: the optimizer
+ * changes it every step); bias[i] is [cout_i], read when has_bias.  x [n,h,w,cin], y and dy the last layer's output shape
+ * (ron_conv_chain_shape), taps[i] / dtaps[i] layer i's.  x, y, dy, dx, taps and dtaps entries must be 16-byte aligned, the
+ * other pointers 4-byte, the workspace 256-byte.
+ *
+ * ron_conv_chain_backward reads the activations ron_conv_chain_forward left in the SAME workspace (same descriptor) and does not
+ * destroy them: it may be called any number of times after one forward and gives the same bytes each time.  dx, any dw[i],
+ * any dbias[i] (and the arrays dw, dbias themselves) may be NULL: not computed.  Launches whose results nobody asked for are
+ * skipped: without dx the first layer's data gradient is not launched, and layers in front of the first requested gradient do
+ * not run at all.  Every element of a non-NULL output is written.  w[i] of every convolution layer must be given to both calls.
+ *
+ * The workspace is 64-bit sized; each tensor inside it stays below 2 GiB (a larger one is refused).
+ * ron_conv_chain_workspace_bytes is host arithmetic only; -1 + ron_last_error() on a descriptor the calls would refuse.
+ * ron_conv_chain_shape: the output shape of `layer`.
+ * Out of scope: the stem; the 3x3 stride-1 pool, the L2 normalisation and batch normalisation; the 2x2 stride-2
+ * convolutions; fp32 and f16x3 arithmetic; taps on pool layers.
+ * ---------------------------------------------------------------------------------------- */
+enum { RON_CHAIN_CONV = 0, RON_CHAIN_POOL2 = 1 };
+#define RON_CHAIN_MAX_LAYERS 32
+typedef struct {
+  int32_t kind;             /* RON_CHAIN_CONV / RON_CHAIN_POOL2 */
+  int32_t k, dilation, cout, relu, has_bias;
+  int32_t tap;
+} ron_chain_layer;
+typedef struct {
+  int32_t n, h, w, cin;
+  int32_t dtype;            /* ron_dtype: bf16 or fp16 */
+  int32_t num_layers;
+  ron_chain_layer layers[RON_CHAIN_MAX_LAYERS];
+} ron_chain_desc;
+int ron_conv_chain_shape(const ron_chain_desc* d, int layer, int64_t nhwc[4]);
+int64_t ron_conv_chain_workspace_bytes(const ron_chain_desc* d);
+int ron_conv_chain_forward(const ron_chain_desc* d, const float* x, const float* const* w, const float* const* bias,
+                           float* const* taps, float* y, void* workspace, int64_t workspace_bytes, void* stream);
+int ron_conv_chain_backward(const ron_chain_desc* d, const float* dy, const float* const* dtaps, const float* const* w,
+                            float* dx, float* const* dw, float* const* dbias, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Backward of the 3-channel stem convolution conv1_1 (3 -> 64 channels, 3x3, stride 1, SAME): its weight and bias
  * gradients, the two variables ron_conv2d_backward_nhwc cannot reach.  There is no gradient with respect to the image
  * (nothing takes one), hence no w and no dx.  A real entry point like the convolution backward: it enqueues on `stream`,

@@ -114,6 +114,21 @@ class BnDesc(C.Structure):
                 ('eps', C.c_float), ('decay', C.c_float)]
 
 
+RON_CHAIN_CONV = 0
+RON_CHAIN_POOL2 = 1
+RON_CHAIN_MAX_LAYERS = 32
+
+
+class ChainLayer(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('k', C.c_int32), ('dilation', C.c_int32), ('cout', C.c_int32), ('relu', C.c_int32),
+                ('has_bias', C.c_int32), ('tap', C.c_int32)]
+
+
+class ChainDesc(C.Structure):
+    _fields_ = [('n', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('cin', C.c_int32), ('dtype', C.c_int32),
+                ('num_layers', C.c_int32), ('layers', ChainLayer * RON_CHAIN_MAX_LAYERS)]
+
+
 OPT_RULES = {'sgd': 0, 'momentum': 1, 'rmsprop': 2, 'adam': 3}
 
 
@@ -210,6 +225,11 @@ SIGNATURES = {
     'ron_conv2d_forward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_forward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_conv2d_forward_parts_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, C.c_int64, C.c_int, _P]),
+    'ron_conv_chain_shape': (C.c_int, [C.POINTER(ChainDesc), C.c_int, C.POINTER(C.c_int64)]),
+    'ron_conv_chain_workspace_bytes': (C.c_int64, [C.POINTER(ChainDesc)]),
+    'ron_conv_chain_forward': (C.c_int, [C.POINTER(ChainDesc), _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, C.c_int64, _P]),
+    'ron_conv_chain_backward': (C.c_int, [C.POINTER(ChainDesc), _P, C.POINTER(_P), C.POINTER(_P), _P, C.POINTER(_P), C.POINTER(_P), _P,
+                                          C.c_int64, _P]),
     'ron_conv2d_stem_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_stem_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_maxpool2x2_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

@@ -34,12 +34,13 @@
 #include <algorithm>
 
 #include "conv_mfma.h"
+#include "conv_train.h"
 #include "wgrad_device.h"
 
 namespace ron {
 namespace {
 
-constexpr int kWgTile = 128;        // channels per tile side
+constexpr int kWgTile = 128;       // channels per tile side
 constexpr int kWgStep = 32;         // pixels per K step
 constexpr int kWgImage = kWgStep * kWgTile * 2;     // bytes of one staged operand image
 constexpr int kWgLds = 4 * kWgImage;                // two operands, double buffered: 32 KB, inside the default limit
@@ -413,19 +414,7 @@ int launch_conv_wgrad(const WgradLaunch& c, hipStream_t stream) {
 // ---- what the two backward entry points share: the tail of the plan, the checks of a call, the three launch steps ----------------------
 namespace {
 
-// What both operators decide on the host behind their own descriptor checks (offsets and sizes in bytes).  The operator fills rows,
-// sum_cols, conv and wg and carves its own operand buffers; finish_plan does the rest.
-struct BackwardCore {
-  int64_t rows = 0;         // rows of the packed operands: the pixels rounded up to the K step
-  int sum_cols = 0;         // columns of the tensor the bias gradient sums
-  int chunks = 0;
-  int64_t chunk_rows = 0;
-  int64_t off_w = 0, off_bias = 0, off_dx = 0, off_sk = 0, off_slab = 0, off_part = 0, total = 0;
-  int64_t w_bytes = 0, dx_bytes = 0, sk_bytes = 0, slab_bytes = 0;
-  ConvLaunch conv;          // the data gradient (pointers unset)
-  WgradLaunch wg;           // the weight gradient (pointers unset)
-};
-
+// (BackwardCore, what both operators decide on the host behind their own descriptor checks: conv_train.h)
 int64_t carve(BackwardCore* P, int64_t bytes) {
   const int64_t o = P->total;
   P->total += align_up(bytes, 256);
@@ -534,13 +523,7 @@ int launch_colsum(const BackwardCore& P, const void* dzbuf, char* ws, hipStream_
 }
 
 // ---- ron_conv2d_backward_nhwc ------------------------------------------------------------------------------------------------------------
-// Everything the entry point decides on the host: the descriptor's checks and the carving of the workspace.
-struct BackwardPlan : BackwardCore {
-  int pad = 0, cop = 0, npad = 0, taps = 0;
-  int64_t pixels = 0, guard = 0;                // halo pixels; guard pixels of x on each side
-  int64_t off_dz = 0, off_x = 0;
-};
-
+// Everything the entry point decides on the host: the descriptor's checks and the carving of the workspace (BackwardPlan, conv_train.h).
 int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
   if (int rc0 = check_conv_desc(d)) return rc0;       // sizes, filter, stride, dilation inside the envelope of the forward; flags 0 or 1
   RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv backward: dtype %d: bf16 or fp16 only (fp32 and f16x3 have no backward)", d->dtype);
@@ -589,6 +572,18 @@ int plan_backward(const ron_conv_desc* d, BackwardPlan* P) {
   P->off_dz = carve(P, dz_bytes);
   P->off_x = carve(P, x_bytes);
   return finish_plan(P);
+}
+
+// the data gradient's weights: w (device fp32 HWIO) -> the blocked rows at ws + P.off_w.  The launch run_backward makes in line, as a
+// step of its own for conv_train.h (run_backward keeps its text: the dry run's launch trace of the entry point is pinned).
+template <bool BF16>
+int backward_pack_w(const ron_conv_desc* d, const BackwardPlan& P, const float* w, char* ws, hipStream_t s) {
+  WpackArgs wa = WpackArgs();
+  wa.w = w; wa.out = reinterpret_cast<unsigned short*>(ws + P.off_w);
+  wa.taps = P.taps; wa.cin = d->cin; wa.cout = d->cout; wa.cop = P.cop; wa.npad = P.npad;
+  RON_LAUNCH(conv_bwd_pack_weights_kernel<BF16>, dim3(grid_for(P.w_bytes / 16)), dim3(256), 0, s, wa);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
 }
 
 // sstep = 0: y and dy are [n,h,w,cout] (ron_conv2d_backward_nhwc); else they are [n,hs,ws,cout] and dz is their scatter to pixels
@@ -1124,15 +1119,8 @@ __global__ void conv_fwd_pad_bias_kernel(const float* bias, float* out, int cout
 enum { kFwdPlain = 0, kFwdStrided, kFwdTransposed, kFwdStem, kFwdStemIm2col };
 
 // Everything the entry point decides on the host: the descriptor's checks, the ConvLaunch of setup_conv, the carving of the workspace
-struct ForwardPlan {
-  int kind = kFwdPlain;
-  int pad = 0, K = 0;
-  int bias_live = 0, bias_total = 0;
-  bool c64 = false;             // the launch also gets the resident-weight images (ConvLaunch::wgt_c64), as setup_conv provides them
-  int64_t x_bytes = 0, w_bytes = 0, c64_bytes = 0, out_bytes = 0, sk_bytes = 0;
-  int64_t off_x = 0, off_w = 0, off_c64 = 0, off_bias = 0, off_out = 0, off_sk = 0, total = 0;
-  ConvLaunch conv;              // pointers unset
-};
+// (ForwardPlan, conv_train.h)
+static_assert(kFwdPlain == 0, "ForwardPlan::kind defaults to the plain convolution");
 
 TensorView dense_view(int n, int h, int w, int c, int pad) {
   TensorView v;
@@ -1289,6 +1277,41 @@ int run_forward(const ron_conv_desc* d, const ForwardPlan& P, const float* x, co
 }
 
 }  // namespace
+
+// ---- conv_train.h: the plans and steps above, for the network-level chain (conv_chain.hip) ---------------------------------------------
+int train_plan_forward(const ron_conv_desc* d, ForwardPlan* P) { return plan_forward(d, P); }
+int train_plan_backward(const ron_conv_desc* d, BackwardPlan* P) { return plan_backward(d, P); }
+ConvLaunch train_forward_launch(const ForwardPlan& P, char* ws) { return forward_launch(P, ws); }
+
+int train_pack_halo(int dtype, const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc,
+                    int cdst, int64_t guard, hipStream_t s) {
+  return dtype == RON_DTYPE_BF16 ? launch_pack_halo<true>(src, mask, out, rows, n, h, w, pad, csrc, cdst, guard, s)
+                                 : launch_pack_halo<false>(src, mask, out, rows, n, h, w, pad, csrc, cdst, guard, s);
+}
+
+int train_forward_pack_w(const ron_conv_desc* d, const ForwardPlan& P, const ConvLaunch& c, const float* w, const float* bias, char* ws,
+                         hipStream_t s) {
+  return d->dtype == RON_DTYPE_BF16 ? forward_pack_w<true>(d, P, c, w, bias, ws, s) : forward_pack_w<false>(d, P, c, w, bias, ws, s);
+}
+
+int train_backward_pack_w(const ron_conv_desc* d, const BackwardPlan& P, const float* w, char* ws, hipStream_t s) {
+  return d->dtype == RON_DTYPE_BF16 ? backward_pack_w<true>(d, P, w, ws, s) : backward_pack_w<false>(d, P, w, ws, s);
+}
+
+int train_data_grad(const BackwardCore& P, void* dzbuf, char* ws, hipStream_t s, TensorView* out) { return launch_data_grad(P, dzbuf, ws, s, out); }
+
+int train_weight_grad(const BackwardCore& P, void* xbase, void* dzbase, float* dw, char* ws, hipStream_t s) {
+  return launch_weight_grad(P, xbase, dzbase, dw, ws, s);
+}
+
+int train_bias_grad(int dtype, const BackwardPlan& P, const void* dzbuf, char* ws, int cout, float* dbias, hipStream_t s) {
+  const float* part;
+  if (int rc = dtype == RON_DTYPE_BF16 ? launch_colsum<true>(P, dzbuf, ws, s, &part) : launch_colsum<false>(P, dzbuf, ws, s, &part)) return rc;
+  RON_LAUNCH(conv_bwd_colsum_final_kernel, dim3(cout), dim3(64), 0, s, part, P.chunks, P.cop, dbias);
+  RON_HIP_CHECK(ron::launch_error());
+  return RON_OK;
+}
+
 }  // namespace ron
 
 extern "C" int64_t ron_conv2d_forward_workspace_bytes(const ron_conv_desc* d) {

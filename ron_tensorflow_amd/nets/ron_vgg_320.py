@@ -24,6 +24,38 @@ RONParams = namedtuple('SSDParameters', ['img_shape', 'num_classes', 'no_annotat
                                          'anchor_steps', 'anchor_offset', 'prior_scaling'])
 
 
+def vgg_body_chain(variant='reducedfc', scope='ron_320_vgg'):
+    """The VGG body behind the stem as the layer list of ops.conv_chain_fn: conv1_2 .. conv5_3 with pool1 .. pool5, fc6, fc7, taps at
+    conv4_3, conv5_3, fc6 and fc7 (the four feature layers the reverse connections read; fc7, the last layer, is the chain's y).
+
+    Returns (layers, names): layers[i] is ops.chain_conv(...) / ops.chain_pool(); names[i] is (weights name, biases name) of a
+    convolution layer - the variable names of weights.variable_shapes(variant), the ones optim.Optimizer knows - and None for a
+    pool.  The chain's input is conv1_1's output (the stem: ops.conv2d_nhwc_fn on the image); with y, *taps = conv_chain_fn(...)
+    the taps come in the order conv4_3, conv5_3, fc6 and y is fc7 (its tap flag stays clear: y is always delivered)."""
+    if variant not in ('reducedfc', 'full'):
+        raise ValueError('Unknown RON variant %s' % variant)
+    c6 = {'full': 4096, 'reducedfc': 1024}[variant]
+    layers, names = [], []
+
+    def conv(name, cout, k=3, dilation=1, tap=False):
+        layers.append(ops.chain_conv(cout, k=k, dilation=dilation, relu=True, bias=True, tap=tap, name=name))
+        names.append(('%s/%s/weights' % (scope, name), '%s/%s/biases' % (scope, name)))
+
+    for b, (reps, width) in enumerate([(2, 64), (2, 128), (3, 256), (3, 512), (3, 512)]):
+        for r in range(reps):
+            if (b, r) == (0, 0):
+                continue            # conv1_1: the 3-channel stem, in front of the chain
+            conv('conv%d/conv%d_%d' % (b + 1, b + 1, r + 1), width, tap=b >= 3 and r == reps - 1)
+        layers.append(ops.chain_pool(name='pool%d' % (b + 1)))
+        names.append(None)
+    if variant == 'full':
+        conv('fc6', c6, k=7, tap=True)
+    else:
+        conv('fc6', c6, k=3, dilation=3, tap=True)
+    conv('fc7', c6, k=1)
+    return layers, names
+
+
 class _DataFormatScope(object):
     """What `arg_scope(data_format=...)` returns: inside the `with`, the networks it was made for take / return that layout."""
 

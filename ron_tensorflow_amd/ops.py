@@ -736,6 +736,160 @@ def conv2d_nhwc_fn(x, w, bias, relu=True, dilation=1, dtype='bf16'):
 
 
 # --------------------------------------------------------------------------- #
+# convolution chain (ron_conv_chain_forward / ron_conv_chain_backward): a sequence of stride-1 convolutions and 2x2 pools, forward in
+# one call and backward in one call, activations and gradients kept as storage-type halo tensors in one workspace in between
+# --------------------------------------------------------------------------- #
+def chain_conv(cout, k=3, dilation=1, relu=True, bias=True, tap=False, name=None):
+    """One convolution layer of a chain's layer list (`name`: the variable scope, for callers that map layers to variables)."""
+    return {'kind': 'conv', 'k': int(k), 'dilation': int(dilation), 'cout': int(cout), 'relu': bool(relu), 'bias': bool(bias),
+            'tap': bool(tap), 'name': name}
+
+
+def chain_pool(name=None):
+    """One 2x2 stride-2 SAME max-pool layer of a chain's layer list."""
+    return {'kind': 'pool', 'tap': False, 'name': name}
+
+
+def _chain_desc(n, h, w, cin, layers, dtype):
+    d = _lib.ChainDesc()
+    d.n, d.h, d.w, d.cin, d.dtype, d.num_layers = int(n), int(h), int(w), int(cin), _lib.DTYPES[dtype], len(layers)
+    if len(layers) > _lib.RON_CHAIN_MAX_LAYERS:
+        raise _lib.RonError('conv chain: %d layers, at most %d' % (len(layers), _lib.RON_CHAIN_MAX_LAYERS))
+    for i, l in enumerate(layers):
+        if l['kind'] == 'pool':
+            d.layers[i] = _lib.ChainLayer(_lib.RON_CHAIN_POOL2, 0, 0, 0, 0, 0, int(bool(l.get('tap', False))))
+        elif l['kind'] == 'conv':
+            d.layers[i] = _lib.ChainLayer(_lib.RON_CHAIN_CONV, l['k'], l.get('dilation', 1), l['cout'], int(l.get('relu', True)),
+                                          int(l.get('bias', True)), int(bool(l.get('tap', False))))
+        else:
+            raise _lib.RonError('conv chain: layer %d: unknown kind %r' % (i, l['kind']))
+    return d
+
+
+def conv_chain_shapes(n, h, w, cin, layers, dtype='bf16'):
+    """The output shape (n, h, w, c) of every layer of the chain (ron_conv_chain_shape); raises on a descriptor the library refuses."""
+    d = _chain_desc(n, h, w, cin, layers, dtype)
+    out = []
+    for i in range(len(layers)):
+        s = (C.c_int64 * 4)()
+        check(lib().ron_conv_chain_shape(C.byref(d), i, s))
+        out.append(tuple(int(v) for v in s))
+    return out
+
+
+def conv_chain_workspace_bytes(n, h, w, cin, layers, dtype='bf16'):
+    """Bytes of the workspace conv_chain_forward and conv_chain_backward share for this chain (host arithmetic; raises on a descriptor
+    the library refuses)."""
+    return _desc_workspace_bytes('conv_chain', _chain_desc(n, h, w, cin, layers, dtype))
+
+
+def _chain_ptrs(tensors, count):
+    """A host array of `count` device pointers (None entries: NULL), or NULL for None."""
+    if tensors is None:
+        return None
+    assert len(tensors) == count, '%d entries for %d layers' % (len(tensors), count)
+    return (C.c_void_p * count)(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _chain_check(what, tensors):
+    for t in tensors:
+        if t is not None and not (hasattr(t, 'is_cuda') and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()):
+            raise _lib.RonError('%s: every tensor must be a contiguous GPU fp32 tensor' % what)
+
+
+def conv_chain_forward(x, layers, weights, biases, dtype='bf16', workspace=None):
+    """The chain's forward: x [N,H,W,Cin] GPU fp32, `layers` a list of chain_conv(...) / chain_pool() entries, `weights` / `biases`
+    lists with one GPU fp32 tensor per layer (None for pools; biases None where a layer has none).  Returns (y, taps, workspace): y
+    the last layer's output, taps a list with the fp32 output of every tapped layer (None elsewhere), and the workspace that now
+    holds the activations conv_chain_backward reads (`workspace`: a uint8 GPU tensor of at least conv_chain_workspace_bytes(...)
+    bytes, or None to allocate one).  ONE ron_conv_chain_forward call on the current stream, no synchronisation."""
+    assert x.dim() == 4
+    x = x.contiguous()
+    _chain_check('conv_chain_forward', [x] + list(weights) + list(biases))
+    n, h, w, cin = x.shape
+    d = _chain_desc(n, h, w, cin, layers, dtype)
+    nbytes = _desc_workspace_bytes('conv_chain', d)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if workspace is None else workspace
+    shapes = conv_chain_shapes(n, h, w, cin, layers, dtype)
+    taps = [torch.empty(shapes[i], dtype=torch.float32, device=x.device) if l.get('tap') else None for i, l in enumerate(layers)]
+    y = torch.empty(shapes[-1], dtype=torch.float32, device=x.device)
+    L = len(layers)
+    check(lib().ron_conv_chain_forward(C.byref(d), ptr(x), _chain_ptrs(weights, L), _chain_ptrs(biases, L), _chain_ptrs(taps, L), ptr(y),
+                                       ptr(ws), int(ws.numel()), current_stream()))
+    return y, taps, ws
+
+
+def conv_chain_backward(x_shape, layers, weights, dy, dtaps, workspace, dtype='bf16', need_dx=True, need_dw=None, need_db=None):
+    """The chain's backward from the workspace conv_chain_forward filled: x_shape the forward's x.shape, dy the gradient of y, dtaps a
+    list with the gradient of every tap (None: none) or None.  need_dx, need_dw[i], need_db[i] say what is computed (default: dx,
+    every dw, and db of every layer with a bias).  Returns (dx, dws, dbs) with None for what was not asked for.  ONE
+    ron_conv_chain_backward call on the current stream; it may be repeated and gives the same bytes."""
+    n, h, w, cin = x_shape
+    L = len(layers)
+    dy = dy.contiguous()
+    dtaps = None if dtaps is None else [None if t is None else t.contiguous() for t in dtaps]
+    _chain_check('conv_chain_backward', [dy] + list(weights) + list(dtaps or []))
+    d = _chain_desc(n, h, w, cin, layers, dtype)
+    shapes = conv_chain_shapes(n, h, w, cin, layers, dtype)
+    assert tuple(dy.shape) == shapes[-1], 'dy %s, the chain ends in %s' % (tuple(dy.shape), shapes[-1])
+    for i, t in enumerate(dtaps or []):
+        assert t is None or (layers[i].get('tap') and tuple(t.shape) == shapes[i]), 'dtaps[%d]' % i
+    dev = dy.device
+    conv = [l['kind'] == 'conv' for l in layers]
+    need_dw = [conv[i] for i in range(L)] if need_dw is None else [bool(v) and conv[i] for i, v in enumerate(need_dw)]
+    need_db = [conv[i] and layers[i].get('bias', True) for i in range(L)] if need_db is None else [bool(v) and conv[i] for i, v in enumerate(need_db)]
+    dx = torch.empty((n, h, w, cin), dtype=torch.float32, device=dev) if need_dx else None
+    dws = [torch.empty(tuple(weights[i].shape), dtype=torch.float32, device=dev) if need_dw[i] else None for i in range(L)]
+    dbs = [torch.empty((layers[i]['cout'],), dtype=torch.float32, device=dev) if need_db[i] else None for i in range(L)]
+    check(lib().ron_conv_chain_backward(C.byref(d), ptr(dy), _chain_ptrs(dtaps, L), _chain_ptrs(weights, L), ptr(dx), _chain_ptrs(dws, L),
+                                        _chain_ptrs(dbs, L), ptr(workspace), int(workspace.numel()), current_stream()))
+    return dx, dws, dbs
+
+
+class _ConvChainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, layers, dtype, nw, *params):
+        weights, biases = list(params[:nw]), list(params[nw:])
+        det = lambda ts: [None if t is None else t.detach().contiguous() for t in ts]
+        y, taps, ws = conv_chain_forward(x.detach(), layers, det(weights), det(biases), dtype=dtype)
+        ctx.save_for_backward(*[t for t in weights if t is not None])
+        ctx.cfg = (tuple(x.shape), layers, dtype, nw, [t is not None for t in weights], ws)
+        ctx.tapped = [i for i, l in enumerate(layers) if l.get('tap')]
+        ctx.y_shape = tuple(y.shape)
+        ctx.set_materialize_grads(False)        # an output nobody used has no gradient: dtaps[i] stays NULL
+        return (y,) + tuple(taps[i] for i in ctx.tapped)
+
+    @staticmethod
+    def backward(ctx, dy, *dtap_list):
+        x_shape, layers, dtype, nw, has_w, ws = ctx.cfg
+        saved = iter(ctx.saved_tensors)
+        weights = [next(saved).detach().contiguous() if h else None for h in has_w]
+        L = len(layers)
+        dtaps = [None] * L
+        for i, g in zip(ctx.tapped, dtap_list):
+            dtaps[i] = g
+        need = ctx.needs_input_grad
+        need_dw = [bool(need[4 + i]) for i in range(L)]
+        need_db = [bool(need[4 + nw + i]) for i in range(L)]
+        if dy is None:          # only the taps carry gradients
+            dy = torch.zeros(ctx.y_shape, dtype=torch.float32, device=ws.device)
+        dx, dws, dbs = conv_chain_backward(x_shape, layers, weights, dy, dtaps, ws, dtype=dtype, need_dx=bool(need[0]), need_dw=need_dw,
+                                           need_db=need_db)
+        return (dx, None, None, None) + tuple(dws) + tuple(dbs)
+
+
+def conv_chain_fn(x, layers, weights, biases, dtype='bf16'):
+    """The chain as a torch.autograd.Function: returns (y, *taps), the taps in layer order.  x [N,H,W,Cin], weights[i] HWIO and
+    biases[i] [Cout] GPU fp32 tensors (None for pools and for layers without a bias).  The forward is ONE ron_conv_chain_forward
+    call into a workspace of its own, the backward ONE ron_conv_chain_backward call reading that workspace; it computes dx, dw[i] and
+    db[i] only where autograd asks (needs_input_grad).  The results have the bytes of conv2d_nhwc_fn / maxpool2x2_nhwc_fn chained layer
+    by layer."""
+    L = len(layers)
+    assert len(weights) == L and len(biases) == L
+    return _ConvChainFn.apply(x, layers, dtype, L, *(list(weights) + list(biases)))
+
+
+# --------------------------------------------------------------------------- #
 # backward of the 2x2 pool and of the 2x2 stride-2 convolutions (ron_maxpool2x2_backward_nhwc, ron_conv2d_k2s2_backward_nhwc):
 # real entry points like the convolution backward - they enqueue on the current stream and never synchronise
 # --------------------------------------------------------------------------- #

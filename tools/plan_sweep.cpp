@@ -188,6 +188,104 @@ static int conv_backward_arguments() {
   return 0;
 }
 
+// ron_conv_chain_forward / ron_conv_chain_backward in the dry run: the descriptor checks, every layer's plans, the carving of the
+// workspace and the refusals, over the chains of tests/conv_chain_cases.py and the VGG body of both RON-320 variants at batch 1 and
+// 32, with full and with NULL output sets.  Part of the FULL sweep only, like conv_forward_arguments below.
+static int conv_chain_arguments() {
+  struct Layer { int kind, k, dil, cout, relu, tap; };
+  struct Chain { int n, h, w, cin; std::vector<Layer> layers; };
+  const Layer P = {RON_CHAIN_POOL2, 0, 0, 0, 0, 0};
+  auto c3 = [](int cout, int tap = 0) { return Layer{RON_CHAIN_CONV, 3, 1, cout, 1, tap}; };
+  auto body = [&](int n, bool full) {
+    const int c6 = full ? 4096 : 1024;
+    return Chain{n, 320, 320, 64, {c3(64), P, c3(128), c3(128), P, c3(256), c3(256), c3(256), P, c3(512), c3(512), c3(512, 1), P, c3(512), c3(512),
+                                   c3(512, 1), P, full ? Layer{RON_CHAIN_CONV, 7, 1, c6, 1, 1} : Layer{RON_CHAIN_CONV, 3, 3, c6, 1, 1},
+                                   Layer{RON_CHAIN_CONV, 1, 1, c6, 1, 0}}};
+  };
+  const std::vector<Chain> chains = {
+      {2, 12, 20, 64, {c3(64), c3(64, 1), P, c3(128), P, Layer{RON_CHAIN_CONV, 3, 3, 192, 1, 1}, Layer{RON_CHAIN_CONV, 1, 1, 65, 0, 0}}},
+      {3, 5, 7, 64, {c3(64), P, Layer{RON_CHAIN_CONV, 7, 1, 64, 1, 1}, P, Layer{RON_CHAIN_CONV, 1, 1, 24, 1, 0}}},
+      {2, 9, 6, 128, {P, P, Layer{RON_CHAIN_CONV, 3, 1, 64, 0, 0}, P}},
+      {1, 1, 1, 64, {c3(64)}},
+      {1, 38, 38, 320, {c3(256, 1)}},
+      body(1, false), body(32, false), body(1, true), body(32, true)};
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (const Chain& c : chains) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      ron_chain_desc d;
+      memset(&d, 0, sizeof d);
+      d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.dtype = dtype; d.num_layers = (int)c.layers.size();
+      const float* in[RON_CHAIN_MAX_LAYERS];
+      float* out[RON_CHAIN_MAX_LAYERS];
+      float* none[RON_CHAIN_MAX_LAYERS];
+      int first_conv = -1, tapped = -1;
+      for (int i = 0; i < d.num_layers; ++i) {
+        const Layer& l = c.layers[i];
+        d.layers[i].kind = l.kind; d.layers[i].k = l.k; d.layers[i].dilation = l.dil; d.layers[i].cout = l.cout;
+        d.layers[i].relu = l.relu; d.layers[i].has_bias = l.kind == RON_CHAIN_CONV; d.layers[i].tap = l.tap;
+        in[i] = f + 64 * i; out[i] = f + 64 * i; none[i] = nullptr;
+        if (l.kind == RON_CHAIN_CONV && first_conv < 0) first_conv = i;
+        if (l.tap && tapped < 0) tapped = i;
+      }
+      const int64_t bytes = ron_conv_chain_workspace_bytes(&d);
+      if (bytes <= 0 || bytes % 256 != 0) return 1;
+      int64_t shape[4];
+      CHECK(ron_conv_chain_shape(&d, d.num_layers - 1, shape));
+      if (shape[0] != c.n || ron_conv_chain_shape(&d, d.num_layers, shape) != RON_ERR_INVALID) return 1;
+      CHECK(ron_conv_chain_forward(&d, f, in, in, out, f, ws, bytes, nullptr));
+      CHECK(ron_conv_chain_backward(&d, f, in, in, f, out, out, ws, bytes, nullptr));
+      CHECK(ron_conv_chain_backward(&d, f, nullptr, in, nullptr, out, nullptr, ws, bytes, nullptr));
+      CHECK(ron_conv_chain_backward(&d, f, in, in, f, nullptr, nullptr, ws, bytes, nullptr));
+      CHECK(ron_conv_chain_backward(&d, f, in, in, nullptr, none, none, ws, bytes, nullptr));
+      if (ron_conv_chain_forward(&d, nullptr, in, in, out, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_forward(&d, f, in, in, out, nullptr, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_forward(&d, f + 1, in, in, out, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_forward(&d, f, in, in, out, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_forward(&d, f, in, in, out, f, static_cast<char*>(ws) + 128, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_backward(&d, nullptr, in, in, f, out, out, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_conv_chain_backward(&d, f, in, in, f, out, out, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+      if (first_conv >= 0) {
+        in[first_conv] = nullptr;
+        if (ron_conv_chain_forward(&d, f, in, in, out, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_conv_chain_backward(&d, f, in, in, f, out, out, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        in[first_conv] = f;
+      }
+      if (tapped >= 0) {
+        out[tapped] = nullptr;
+        if (ron_conv_chain_forward(&d, f, in, in, out, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        out[tapped] = f;
+      }
+      ron_chain_desc bad = d;
+      bad.num_layers = 0;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad.num_layers = RON_CHAIN_MAX_LAYERS + 1;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.dtype = RON_DTYPE_F32;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.dtype = RON_DTYPE_F16X3;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.cin = 96;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.layers[0].kind = 2;
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.n = 1 << 26;          // an activation of 2 GiB or more
+      if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+      if (first_conv >= 0) {
+        bad = d; bad.layers[first_conv].k = 5;
+        if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.layers[first_conv].k = 7; bad.layers[first_conv].dilation = 2;
+        if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+        if (first_conv < d.num_layers - 1) {
+          bad = d; bad.layers[first_conv].cout = 24;
+          if (ron_conv_chain_workspace_bytes(&bad) != -1) return 1;
+        }
+      }
+    }
+  }
+  return 0;
+}
+
 // ron_conv2d_forward_nhwc in the dry run: the descriptor checks, the ConvLaunch of every route (plain, 7 x 7, the stem with and without
 // its kernel, 2 x 2 stride 2, transposed, the resident-weight images), the workspace and the refusals, over the case table of
 // tests/conv_fwd_cases.py plus the layer shapes of tools/conv_forward_time.py; and the 7 x 7 filter through ron_conv2d_backward_nhwc.
@@ -887,6 +985,11 @@ int main(int argc, char** argv) {
     trace_note("pass conv_forward_arguments");
     if (conv_forward_arguments()) {
       fprintf(stderr, "plan_sweep: ron_conv2d_forward_nhwc planning / argument handling (and the 7 x 7 backward): %s\n", ron_last_error());
+      return 1;
+    }
+    trace_note("pass conv_chain_arguments");
+    if (conv_chain_arguments()) {
+      fprintf(stderr, "plan_sweep: ron_conv_chain_forward / ron_conv_chain_backward planning / argument handling: %s\n", ron_last_error());
       return 1;
     }
   }
