@@ -42,6 +42,7 @@ __device__ __forceinline__ float bn_round_bf16(float f) {
 template <bool BF16> __device__ __forceinline__ float bn_round(float f) { return BF16 ? bn_round_bf16(f) : (float)(_Float16)f; }
 
 // the geometry every kernel of an operator call shares
+RON_KERNEL_ARGS_BEGIN
 struct BnGeom {
   long long rows;           // M
   long long slice_rows;
@@ -49,7 +50,9 @@ struct BnGeom {
   int lpr, lpr_log2;        // lanes per row of a channel tile (a power of two <= 64)
   int rpb;                  // rows a workgroup covers at a time: 256 / lpr
   int slices, tiles;
+  int fill_ = 0;
 };
+RON_KERNEL_ARGS_END(BnGeom)
 
 struct BnPlan : BnGeom {
   int64_t off_part = 0, off_fin = 0, total = 0;

@@ -7,6 +7,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
+#include <type_traits>
 
 #include "../../include/ron_hip.h"
 
@@ -74,14 +75,35 @@ using Event = Owned<hipEvent_t, hipEventDestroy>;
 hipError_t dev_upload(DevBuf* b, const void* host, size_t bytes);      // a new allocation of `bytes` bytes holding the host data
 hipError_t dev_stream_sync(hipStream_t s);
 
+// A struct that reaches a kernel by value is defined between these two:
+//
+//   RON_KERNEL_ARGS_BEGIN
+//   struct FooArgs { const float* p; int n; int fill_ = 0; };
+//   RON_KERNEL_ARGS_END(FooArgs)
+//
+// In between, implicit padding - a hole or the tail - is a compile error (-Wpadded, raised where the struct's layout is first used,
+// in the host and the device pass): what the compiler would pad becomes a named filler member where the padding was, so sizeof and
+// every offset stay as they are.  A filler is 0: by its initialiser, or - ConvArgs and PatchArgs, which device code declares and
+// which hold a bit-field filler - because every host object starts as T().  END declares the struct to trace_launch, which takes no
+// other class type (found by argument-dependent lookup, so it works in any namespace; one BEGIN / END pair per struct).
+#define RON_KERNEL_ARGS_BEGIN _Pragma("clang diagnostic push") _Pragma("clang diagnostic error \"-Wpadded\"")
+#define RON_KERNEL_ARGS_END(T) \
+  _Pragma("clang diagnostic pop") [[maybe_unused]] constexpr bool ron_kernel_args_declared(const T*) { return true; }
+constexpr bool ron_kernel_args_declared(const volatile void*) { return false; }
+
 // Launch trace of the dry run (RON_PLAN_TRACE=<file> beside RON_PLAN_ONLY=1): one line per skipped launch - the kernel as spelled at
-// the RON_LAUNCH site, grid, block, dynamic LDS bytes and, per by-value argument, its size and the CRC32C of its bytes - and one per
-// dev_memset_async.  Two trees whose traces are equal launch the same kernels with the same arguments (tools/plan_sweep.cpp,
-// tests/test_plan_trace_cpu.py).  Nothing is evaluated outside the dry run.
+// the RON_LAUNCH site, grid, block, dynamic LDS bytes and, per by-value argument, its size and the CRC32C of its sizeof bytes - and
+// one per dev_memset_async.  Every hashed byte is the value of a member: scalars and pointers have no padding, and a class type has
+// none because it was declared with RON_KERNEL_ARGS (anything else does not compile).  So the digest is a function of the argument
+// VALUES alone - not of the compiler, its flags, or the copies and returns an argument went through on the way to the launch - and
+// two trees whose traces are equal launch the same kernels with the same arguments wherever a launch is written
+// (tools/plan_sweep.cpp, tests/test_plan_trace_cpu.py).  Nothing is evaluated outside the dry run.
 FILE* plan_trace();      // the open trace file (appended to, line-buffered), or null
 void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t lds, int nargs, const size_t* sizes, const uint32_t* crcs);
 template <class... A>
 void trace_launch(const char* kernel, dim3 grid, dim3 block, size_t lds, hipStream_t, const A&... args) {
+  static_assert(((!std::is_class<A>::value || ron_kernel_args_declared(static_cast<const A*>(nullptr))) && ...),
+                "a struct passed to a kernel by value is defined between RON_KERNEL_ARGS_BEGIN and RON_KERNEL_ARGS_END (no padding)");
   const size_t sizes[] = {sizeof(A)..., 0};
   const uint32_t crcs[] = {ron_crc32c(&args, sizeof(A), 0)..., 0};
   trace_launch(kernel, grid, block, lds, (int)sizeof...(A), sizes, crcs);

@@ -38,6 +38,7 @@ constexpr int kC6PatchBytes = kC6Pieces * 1024;                                 
 constexpr int kC6WBytes = 9 * 64 * 128;                                          // 72 KB
 constexpr int kC6Lds = kC6WBytes + 2 * kC6PatchBytes;                            // 161 792 of 163 840
 
+RON_KERNEL_ARGS_BEGIN
 struct C64Args {
   const void* in;
   unsigned in_bytes;
@@ -50,6 +51,7 @@ struct C64Args {
   int n_img, H, W, halves, relu;
   int n_slots;                // tile sequences (a multiple of 8): grid = n_slots * halves
 };
+RON_KERNEL_ARGS_END(C64Args)
 
 typedef __attribute__((ext_vector_type(2))) float f32x2_c64;
 typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_c64;

@@ -39,6 +39,7 @@ using namespace wgrad;      // round_bits, bits_to_f
 // g and mask are halo tensors of the map (their own halo and pixel stride), add1 / add2 dense fp32 [N,H,W,Csrc]; each may be null.
 // Interior pixels get the value in channels < Csrc; every other element of the buffer - pad channels, halos, guards, tail - zero.
 // With g alone it is a copy into another halo geometry.
+RON_KERNEL_ARGS_BEGIN
 struct JoinArgs {
   const unsigned short* g;
   const float* add1;
@@ -49,6 +50,7 @@ struct JoinArgs {
   int N, H, W, pad, Csrc, Cdst;
   int gpad, gcs, mpad, mcs;
 };
+RON_KERNEL_ARGS_END(JoinArgs)
 
 __device__ __forceinline__ long long halo_off(long long img, int y, int x, int H, int W, int pad, int cs) {
   return ((img * (H + pad) + y + pad) * (W + pad) + x + pad) * cs;
@@ -133,11 +135,14 @@ __global__ __launch_bounds__(256) void chain_join_kernel(JoinArgs a) {
 }
 
 // ---- zero everything of a buffer that is not an interior pixel: halos, guards, tail (the producer wrote the interior) ---------------------
+RON_KERNEL_ARGS_BEGIN
 struct ZeroArgs {
   unsigned short* out;
   long long rows, guard;      // pixels of the buffer; halo pixel 0 is pixel `guard`
   int N, H, W, pad, C;
+  int fill_ = 0;
 };
+RON_KERNEL_ARGS_END(ZeroArgs)
 
 __global__ __launch_bounds__(256) void chain_zero_kernel(ZeroArgs a) {
   const unsigned vecs = a.C / 8;
@@ -163,6 +168,7 @@ __global__ __launch_bounds__(256) void chain_zero_kernel(ZeroArgs a) {
 // The order is (0,0) (0,1) (1,0) (1,1) and a later position takes over only when it is greater (op_backward.hip: TensorFlow's
 // MaxPoolGrad); positions an odd map does not have are neither read nor written.  One lane = one window x 8 channels: four 16-byte
 // loads of x, one of g, four 16-byte stores; every interior element of dx is written exactly once, its halo is left alone.
+RON_KERNEL_ARGS_BEGIN
 struct PoolBwdViewArgs {
   const unsigned short* x;
   const unsigned short* g;
@@ -171,6 +177,7 @@ struct PoolBwdViewArgs {
   int H, W, OH, OW, C;
   int xpad, gpad, dpad;
 };
+RON_KERNEL_ARGS_END(PoolBwdViewArgs)
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void chain_pool_bwd_kernel(PoolBwdViewArgs a) {
@@ -217,8 +224,6 @@ __global__ __launch_bounds__(256) void chain_pool_bwd_kernel(PoolBwdViewArgs a) 
     if (has_r && has_c) *reinterpret_cast<uint4*>(a.dx + d00 + drow + a.C) = make_uint4(o[3][0], o[3][1], o[3][2], o[3][3]);
   }
 }
-
-int grid_for(long long total) { return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16)); }
 
 // ---- plan_chain ---------------------------------------------------------------------------------------------------------------------------
 // Activation j (0: the chain's input, j: the output of layer j - 1) in the geometry of its consumer, layer j.  The buffer is
@@ -277,11 +282,6 @@ int plan_chain(const ron_chain_desc* d, ChainPlan* P) {
   const int L = d->num_layers;
   const int64_t lim = (int64_t)1 << 31;
   P->L = L; P->dtype = d->dtype; P->n = d->n;
-  auto carve = [P](int64_t bytes) {
-    const int64_t o = P->total;
-    P->total += align_up(bytes, 256);
-    return o;
-  };
   int h = d->h, w = d->w, c = d->cin;
   int64_t fwd_scratch = 0, bwd_scratch = 0;
   for (int j = 0; j <= L; ++j) {
@@ -312,7 +312,7 @@ int plan_chain(const ron_chain_desc* d, ChainPlan* P) {
       if (j < L) { h = (h + 1) / 2; w = (w + 1) / 2; }
     }
     RON_REQUIRE(a.bytes() < lim, "conv chain: activation %d (%d x %d x %d x %d) would reach 2 GiB", j, d->n, a.h, a.w, a.c);
-    a.off = carve(a.bytes());
+    a.off = carve(&P->total, a.bytes());
     P->g_bytes = std::max(P->g_bytes, TensorView::halo_pixels(d->n, a.h, a.w, 1) * (int64_t)a.c * 2);
   }
   RON_REQUIRE(P->g_bytes < lim, "conv chain: a gradient tensor would reach 2 GiB");
@@ -340,10 +340,10 @@ int plan_chain(const ron_chain_desc* d, ChainPlan* P) {
     y.bp.off_part = take((int64_t)y.bp.chunks * y.bp.sum_cols * 4);
     bwd_scratch = std::max(bwd_scratch, t);
   }
-  P->off_g[0] = carve(P->g_bytes);
-  P->off_g[1] = carve(P->g_bytes);
+  P->off_g[0] = carve(&P->total, P->g_bytes);
+  P->off_g[1] = carve(&P->total, P->g_bytes);
   P->scratch_bytes = std::max(fwd_scratch, bwd_scratch);
-  P->off_scratch = carve(P->scratch_bytes);
+  P->off_scratch = carve(&P->total, P->scratch_bytes);
   // every layer offset becomes an offset from the workspace's base
   for (int i = 0; i < L; ++i) {
     if (d->layers[i].kind != RON_CHAIN_CONV) continue;

@@ -29,11 +29,14 @@ template <int N> __device__ __forceinline__ void store_f32_vec(float* p, const f
 }
 template <class E, int N> struct alignas(sizeof(E) * vec_align_elems(N)) EVec { E v[N]; };
 
+RON_KERNEL_ARGS_BEGIN
 struct ConvArgs {
   const void* in;
   unsigned in_bytes;
-  const void* wgt;
+  unsigned fill0_;                          // fill*_: where the compiler would pad; no initialisers (the kernels declare a ConvArgs
+  const void* wgt;                          // and copy into it), every host object starts as ConvArgs(), which zeroes them
   unsigned wgt_bytes;
+  unsigned fill1_;
   const float* bias;
   void* out;
   const void* res;
@@ -78,6 +81,7 @@ struct ConvArgs {
   // 1 = M fastest (the row tiles that re-read one weight slice do: fc6's 205 MB of weights are then fetched once, not once per XCD),
   // P >= 2 = panels of P column tiles walked row by row (four-wave tiles only; conv_mfma.hip, pick_m_fastest)
   unsigned m_fastest : 6;
+  unsigned fill_bits_ : 15;
   // fused pool + the full-resolution map too (conv4_3 / conv5_3 feed both their pool and a reverse-connection conv): `out2` is the
   // un-pooled output view, written from the same accumulators; nullptr = pooled map only
   void* out2;
@@ -92,7 +96,9 @@ struct ConvArgs {
   // Column tiles at or beyond output channel center_from_n (0: none) hold a 1x1 branch whose weights sit in the centre tap of the
   // kh x kw filter, zeros elsewhere: they run the K steps of that tap only.
   int center_from_n;
+  int fill2_;
 };
+RON_KERNEL_ARGS_END(ConvArgs)
 
 // MFMA shape of a traits class: kMT x kMT output tile per instruction (32: v_mfma_f32_32x32x16, 16 accumulator registers;
 // 16: v_mfma_f32_16x16x32, 4 registers).  One u32x4 fragment per lane feeds one instruction either way: lane l holds

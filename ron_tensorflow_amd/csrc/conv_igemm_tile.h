@@ -545,6 +545,7 @@ constexpr int kMaxGroup = kMaxConvGroup;
 // steps) are separate entries, so that the host can order ALL long work of the launch before ANY short work - workgroups are
 // dispatched in blockIdx order, and 400 short tiles in front of another member's long ones delayed those by a third of the launch.
 constexpr int kMaxEntries = 2 * kMaxGroup;
+RON_KERNEL_ARGS_BEGIN
 struct ConvGroupArgs {
   ConvArgs op[kMaxGroup];
   int first[kMaxEntries + 1];
@@ -556,6 +557,7 @@ struct ConvGroupArgs {
   unsigned narrow;            // kGroupMixed: bit k set = member k runs on 128 x 64 tiles, else on 128 x 128;
                               // the four-wave 256 x 256 group: bit k set = member k runs on 256 x 224 tiles
 };
+RON_KERNEL_ARGS_END(ConvGroupArgs)
 // tile forms whose grouped kernel also holds the 256 x 224 tile: the four-wave 256 x 256 tile of bf16 / f16
 template <class Tr, int BM, int BN, int WM, int WN, int S>
 constexpr bool kHas224 = AsmLoop<Tr>::value && !IsSplit<Tr>::value && BM == 256 && BN == 256 && WM == 2 && WN == 2 && S == 2;

@@ -143,7 +143,7 @@ inline bool dtype_is_half(int dtype) { return dtype == RON_DTYPE_BF16 || dtype =
 // channels padded to 64: x.C = cin, dz.C >= Cout with zero pad channels).  The kernel walks the flat halo-pixel index without a bounds
 // test, so the caller guarantees: dz's halo is zero; both tensors are zero from pixels() up to the next multiple of 32; x has `guard`
 // >= pad * Wp + pad pixels of finite data (zeros) in front of base and behind its last padded pixel.  ron_conv2d_backward_nhwc packs
-// its fp32 operands that way; a network-level backward calls this on its own halo tensors without the fp32 boundary conversions.
+// its fp32 operands that way (conv_backward.hip); a network-level backward calls this on its own halo tensors without the fp32 boundary conversions.
 struct WgradLaunch {
   int dtype = RON_DTYPE_BF16;
   TensorView x, dz;              // base = halo pixel 0

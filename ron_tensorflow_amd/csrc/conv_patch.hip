@@ -52,6 +52,7 @@ __device__ __forceinline__ void pin_patch_ksteps() {
   }
 }
 
+RON_KERNEL_ARGS_BEGIN
 struct PatchArgs {
   ConvArgs c;
   int flat;                   // 1: runs of 256 positions; 0: TH x TW pixel tiles
@@ -62,7 +63,9 @@ struct PatchArgs {
   int P0;                     // flat: first position (pixel index in the input tensor) of tile 0
   int n_img;
   unsigned max_pixel;         // last pixel index of the input allocation (patch addresses are clamped to it)
+  int fill_;                  // (no initialiser, like ConvArgs: PatchArgs() zeroes it)
 };
+RON_KERNEL_ARGS_END(PatchArgs)
 
 // SB weight stages: SB-1 steps of lead for the per-tap weight tiles.
 // One tile of convolution `p` (geometry `pa`): workgroup `bid` of the `nwg` that convolution's launch -- or its share of a pair

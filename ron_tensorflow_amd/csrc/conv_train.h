@@ -1,16 +1,31 @@
-// What the training entry points of conv_wgrad.hip share with the network-level chain (conv_chain.hip): the host plans of ONE
-// convolution, forward and backward, and the launch steps behind them.  The chain builds every layer's launches through these, so
-// there is one copy of the plan: the same views, by-shape tile and split, Npad and channel padding as ron_conv2d_forward_nhwc and
-// ron_conv2d_backward_nhwc give that layer on its own.  Only the places differ: every off_* is a byte offset from the `ws` pointer a
-// step is given, and the caller may set them afresh behind the plan (the chain points them into its own workspace).
+// The interface between the training convolution's translation units - conv_forward_train.hip (ron_conv2d_forward_nhwc),
+// conv_backward.hip (ron_conv2d_backward_nhwc and its two relatives), conv_wgrad.hip (the weight-gradient kernel) - and to the
+// network-level chain (conv_chain.hip): the host plans of ONE convolution, forward and backward, and the launch steps behind them.
+// The entry points and the chain call the same functions, so there is one copy of the plan and of every step: the same views,
+// by-shape tile and split, Npad and channel padding whether a layer runs on its own or in the chain.  Only the places differ: every
+// off_* is a byte offset from the `ws` pointer a step is given, and the caller may set them afresh behind the plan (the chain points
+// them into its own workspace).
 #pragma once
+#include <algorithm>
+
 #include "conv_mfma.h"
 
 namespace ron {
 
+constexpr int kWgStep = 32;      // pixels per K step of the weight gradient: its packed operands are zero up to the next multiple
+
+// workgroups of 256 lanes for the packs and sums, which stride over `total` items
+inline int grid_for(long long total) { return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16)); }
+// the offset of the next piece of a workspace that holds *total bytes so far; pieces are 256-byte aligned
+inline int64_t carve(int64_t* total, int64_t bytes) {
+  const int64_t o = *total;
+  *total += align_up(bytes, 256);
+  return o;
+}
+
 // ron_conv2d_forward_nhwc: the descriptor's checks, the ConvLaunch of setup_conv, the carving of the operator's own workspace
 struct ForwardPlan {
-  int kind = 0;                 // kFwd* of conv_wgrad.hip (0: a plain stride-1 SAME convolution)
+  int kind = 0;                 // kFwd* of conv_forward_train.hip (0: a plain stride-1 SAME convolution)
   int pad = 0, K = 0;
   int bias_live = 0, bias_total = 0;
   bool c64 = false;             // the launch also gets the resident-weight images (ConvLaunch::wgt_c64), as setup_conv provides them
@@ -44,9 +59,10 @@ int train_plan_backward(const ron_conv_desc* d, BackwardPlan* P);
 // the launch of a forward plan over `ws` (every off_* applied)
 ConvLaunch train_forward_launch(const ForwardPlan& P, char* ws);
 // dense fp32 [n,h,w,csrc] -> `rows` + 2 `guard` pixels of cdst channels of `dtype` in the halo geometry of `pad`, every pixel of the
-// buffer written (conv_bwd_pack_halo_kernel): zero where mask <= 0 (mask may be null), in channels >= csrc, halos, guards and tail
+// buffer written (conv_bwd_pack_halo_kernel): zero where mask <= 0 (mask may be null), in channels >= csrc, halos, guards and tail.
+// sstep > 0: src and mask are the coarser [n,hs,ws,csrc], scattered to pixels (soff + sstep * sy, soff + sstep * sx) of the h x w map
 int train_pack_halo(int dtype, const float* src, const float* mask, void* out, int64_t rows, int n, int h, int w, int pad, int csrc,
-                    int cdst, int64_t guard, hipStream_t s);
+                    int cdst, int64_t guard, hipStream_t s, int hs = 0, int ws = 0, int sstep = 0, int soff = 0);
 // the forward's packs of w and bias (device fp32) to ws + P.off_w / off_c64 / off_bias
 int train_forward_pack_w(const ron_conv_desc* d, const ForwardPlan& P, const ConvLaunch& c, const float* w, const float* bias, char* ws,
                          hipStream_t s);

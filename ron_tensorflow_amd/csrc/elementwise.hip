@@ -116,10 +116,13 @@ __global__ void im2col_c3_kernel(const float* __restrict__ x, int n, int h, int 
   }
 }
 
+RON_KERNEL_ARGS_BEGIN
 struct ViewDev {
   char* base;
   int N, H, W, C, pad, cstride, coff, Hp, Wp;
+  int fill_ = 0;
 };
+RON_KERNEL_ARGS_END(ViewDev)
 ViewDev to_dev(const TensorView& v) {
   return ViewDev{(char*)v.base, v.N, v.H, v.W, v.C, v.pad, v.cstride, v.coff, v.Hp(), v.Wp()};
 }

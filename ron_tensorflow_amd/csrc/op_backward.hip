@@ -29,13 +29,16 @@ __device__ __forceinline__ float round_bf16_f(float f) {
 }
 template <bool BF16> __device__ __forceinline__ float round_storage(float f) { return BF16 ? round_bf16_f(f) : (float)(_Float16)f; }
 
+RON_KERNEL_ARGS_BEGIN
 struct PoolBwdArgs {
   const float* x;
   const float* dy;
   float* dx;
   long long total;          // windows x groups of 4 channels
   int h, w, oh, ow, c;
+  int fill_ = 0;
 };
+RON_KERNEL_ARGS_END(PoolBwdArgs)
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void maxpool2x2_backward_kernel(PoolBwdArgs a) {

@@ -49,6 +49,7 @@ constexpr int kOptMaxTensors = 4096;
 constexpr int64_t kOptMaxCount = (int64_t)1 << 40;
 constexpr int64_t kOptMaxUnits = (int64_t)1 << 22;            // per list: 2^34 elements, and a grid far inside every limit
 
+RON_KERNEL_ARGS_BEGIN      // (a member of OptArgs)
 struct OptEntry {
   float* var;
   const float* grad;
@@ -58,8 +59,10 @@ struct OptEntry {
   float weight_decay;
   unsigned first_unit;          // of this entry, within the launch
 };
+RON_KERNEL_ARGS_END(OptEntry)
 static_assert(sizeof(OptEntry) == 48, "the table is laid out for 48-byte entries");
 
+RON_KERNEL_ARGS_BEGIN
 struct OptArgs {
   OptEntry t[kOptEntries];
   float* partial;               // workspace: one float per unit of the whole list (WANT_REG only)
@@ -71,6 +74,7 @@ struct OptArgs {
   unsigned unit_base;           // the launch's first unit within the list
   unsigned units;               // of the launch
 };
+RON_KERNEL_ARGS_END(OptArgs)
 static_assert(sizeof(OptArgs) <= 4096 - 256, "the kernel arguments must stay under 4 KiB with the hidden ones");
 
 // the rule on one element; g is g'

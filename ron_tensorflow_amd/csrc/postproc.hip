@@ -33,6 +33,7 @@ static_assert(kPartChunks * kMaxTopK <= kSortCap, "the survivors of the partial 
 
 typedef unsigned long long u64;
 
+RON_KERNEL_ARGS_BEGIN
 struct HeadsDev {
   int num_layers;
   int num_classes;
@@ -48,34 +49,46 @@ struct HeadsDev {
   const float* ah[RON_MAX_LAYERS];
   const float* aw[RON_MAX_LAYERS];
 };
+RON_KERNEL_ARGS_END(HeadsDev)
 
 // What the three post-processing forms share of their configuration; a form's own struct adds only what is its own.
+RON_KERNEL_ARGS_BEGIN
 struct PostCore {
   float obj_thr, sel_thr, nms_thr;
   float ref[4];                     // bbox_img / clipping_bbox
   float ps[4];
   unsigned flags;
 };
+RON_KERNEL_ARGS_END(PostCore)
+RON_KERNEL_ARGS_BEGIN
 struct PostDev : PostCore {         // np_methods form: ron_post_np, ron_detect
   int top_k;
 };
+RON_KERNEL_ARGS_END(PostDev)
+RON_KERNEL_ARGS_BEGIN
 struct TfeDev : PostCore {          // TF-evaluation form: ron_post_tfe, ron_detect_tfe
   int top_k, keep_top_k, nms_mode, clip;
   float min_size;
 };
+RON_KERNEL_ARGS_END(TfeDev)
+RON_KERNEL_ARGS_BEGIN
 struct EvalDev : PostCore {         // ron_eval.py form: ron_post_eval
   int keep_top_k, nms_mode;
   const float* min_size;            // [n] filter_boxes' min_size per image
 };
+RON_KERNEL_ARGS_END(EvalDev)
 
+RON_KERNEL_ARGS_BEGIN
 struct DetDev {
   int capacity;
+  int fill_ = 0;
   int* classes;
   float* scores;
   float* bboxes;
   int* anchor_index;
   int* count;
 };
+RON_KERNEL_ARGS_END(DetDev)
 
 // score >= 0 (probabilities): the float's bit pattern is already monotone
 __device__ __forceinline__ u64 make_key(float score, unsigned p) {
@@ -950,12 +963,11 @@ int build_heads_dev(const ron_heads* h, HeadsDev* d, bool need_anchors) {
 int to_det_dev(const ron_detections* d, DetDev* out, int top_k, const char* what, bool optional) {
   if (d == nullptr || d->classes == nullptr) {
     if (!optional) { ron::set_error("%s is NULL", what); return RON_ERR_INVALID; }
-    memset(out, 0, sizeof *out);
+    *out = DetDev();
     return RON_OK;
   }
   RON_REQUIRE(d->capacity >= top_k, "%s: capacity %d < top_k %d", what, d->capacity, top_k);
   RON_REQUIRE(d->scores && d->bboxes && d->anchor_index && d->count, "%s: NULL member", what);
-  memset(out, 0, sizeof *out);      // (padding too: the dry run's launch trace checksums the argument's bytes)
   out->capacity = d->capacity; out->classes = d->classes; out->scores = d->scores; out->bboxes = d->bboxes;
   out->anchor_index = d->anchor_index; out->count = d->count;
   return RON_OK;
@@ -1135,7 +1147,7 @@ __global__ void pack_records_kernel(DetDev d, float* __restrict__ rec) {
 extern "C" int ron_pack_records(const ron_detections* det, int n, float* records, void* stream) {
   RON_REQUIRE(det != nullptr && records != nullptr && n > 0, "bad argument");
   RON_REQUIRE(det->capacity >= 1, "ron_pack_records: empty detection buffers");
-  DetDev d{det->capacity, det->classes, det->scores, det->bboxes, det->anchor_index, det->count};
+  DetDev d{det->capacity, 0, det->classes, det->scores, det->bboxes, det->anchor_index, det->count};
   RON_REQUIRE(d.classes && d.scores && d.bboxes && d.anchor_index && d.count, "ron_pack_records: every detection array is needed");
   RON_LAUNCH(pack_records_kernel, dim3(n), dim3(256), 0, (hipStream_t)stream, d, records);
   RON_HIP_CHECK(ron::launch_error());

@@ -13,7 +13,9 @@
 namespace ron {
 namespace {
 
+RON_KERNEL_ARGS_BEGIN
 struct Means { float m[3]; };
+RON_KERNEL_ARGS_END(Means)
 
 // geom (optional, 8 ints per image): the source window [cy, cy+ch) x [cx, cx+cw) of the whitened image is bilinearly resized
 // to rh x rw and placed at (py, px) of the output, zeros elsewhere.  WARP_RESIZE: the whole image onto the whole output (the

@@ -47,13 +47,16 @@ bool elems_fit(int n, int h, int w, int c, int64_t* pixels) {
   return true;
 }
 
+RON_KERNEL_ARGS_BEGIN
 struct Pool3Args {
   const float* x;
   const float* dy;
   float* dx;
   long long total;          // positions x groups of 4 channels
   int h, w, c;
+  int fill_ = 0;
 };
+RON_KERNEL_ARGS_END(Pool3Args)
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void maxpool3x3s1_backward_kernel(Pool3Args a) {
@@ -132,6 +135,7 @@ constexpr int kL2MaxWaves = 2048;       // rows of the dgamma table at most: eig
 constexpr int kL2MaxC = 2048;           // channels: IT <= 8 passes of 256 per wave, everything in registers
 constexpr int kL2Runs = 8;              // contiguous runs of table rows the second kernel adds side by side
 
+RON_KERNEL_ARGS_BEGIN
 struct L2Args {
   const float* x;
   const float* gamma;
@@ -141,6 +145,7 @@ struct L2Args {
   long long pixels;
   int c, waves;
 };
+RON_KERNEL_ARGS_END(L2Args)
 
 template <bool BF16, int IT>
 __global__ __launch_bounds__(256) void l2norm_backward_kernel(L2Args a) {

@@ -35,6 +35,7 @@ constexpr int64_t kCountBytes = 128;       // int32 n_pos[kSegs], n_cand[kSegs]
 constexpr int64_t kHistBytes = (int64_t)kDigits * kSegs * 256 * (int64_t)sizeof(unsigned);
 constexpr int64_t kZeroBytes = kCountBytes + kHistBytes;
 
+RON_KERNEL_ARGS_BEGIN
 struct SsdDev {
   int num_layers, num_classes, num_segs, batch, mining;
   float match_threshold, negative_ratio, alpha;
@@ -46,11 +47,14 @@ struct SsdDev {
   const float* gloc[RON_MAX_LAYERS];
   const float* gscores[RON_MAX_LAYERS];
 };
+RON_KERNEL_ARGS_END(SsdDev)
 
+RON_KERNEL_ARGS_BEGIN
 struct SsdGradDev {
   float* d_cls[RON_MAX_LAYERS];
   float* d_loc[RON_MAX_LAYERS];
 };
+RON_KERNEL_ARGS_END(SsdGradDev)
 
 __device__ inline int segment_of(const SsdDev& p, long long r) {
   int s = 0;

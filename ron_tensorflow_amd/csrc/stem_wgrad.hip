@@ -69,6 +69,7 @@ template <bool BF16> __device__ __forceinline__ unsigned round_pair(float lo, fl
 __device__ __forceinline__ int z_off(int row, int blk) { return 128 * row + 32 * (blk ^ (((row >> 1) & 1) | (((row >> 3) & 1) << 1))); }
 __device__ __forceinline__ int x_off(int row, int blk) { return 64 * row + 32 * (blk ^ ((row >> 3) & 1)); }
 
+RON_KERNEL_ARGS_BEGIN
 struct StemWgradArgs {
   const float* x;           // [pixels][3]; not read when want_dw == 0
   const float* y;           // [pixels][64], or null: no mask
@@ -78,6 +79,7 @@ struct StemWgradArgs {
   int steps, slices;        // K steps in all; workgroup s owns steps s, s + slices, ... (slices <= steps: no empty slice)
   int want_dw;
 };
+RON_KERNEL_ARGS_END(StemWgradArgs)
 
 template <bool BF16>
 __global__ __launch_bounds__(256) void stem_wgrad_kernel(StemWgradArgs a) {

@@ -25,11 +25,13 @@ namespace {
 
 typedef unsigned long long u64;
 
+RON_KERNEL_ARGS_BEGIN
 struct EncodeDev {
   int num_layers;
   int total;                              // anchors per image
   int off[RON_MAX_LAYERS + 1];            // first flat anchor index of a layer
   int na[RON_MAX_LAYERS];                 // anchors per cell
+  int fill_ = 0;
   const float* ay[RON_MAX_LAYERS];
   const float* ax[RON_MAX_LAYERS];
   const float* ah[RON_MAX_LAYERS];
@@ -42,6 +44,7 @@ struct EncodeDev {
   float low, high;
   float ps[4];
 };
+RON_KERNEL_ARGS_END(EncodeDev)
 
 struct Anchor {
   int layer, local;                       // layer and index inside the layer's [H, W, A]
@@ -188,6 +191,7 @@ __global__ __launch_bounds__(kThreads) void encode_write_kernel(EncodeDev p, con
 }
 
 // ----------------------------------------------------------------------------------------------------------------- losses
+RON_KERNEL_ARGS_BEGIN
 struct LossDev {
   int num_layers, num_classes;
   long long row_off[RON_MAX_LAYERS + 1];  // first flattened row of a layer (batch included)
@@ -199,6 +203,7 @@ struct LossDev {
   const float* gloc[RON_MAX_LAYERS];
   float objness_threshold, negative_ratio;
 };
+RON_KERNEL_ARGS_END(LossDev)
 
 // counters of the workspace (int32): 0 n_pos, 1 n_neg, 2 n_cls_pos, 3 n_cls_neg, 4 objectness set, 5 class set
 constexpr int kNumCounts = 6;
@@ -310,11 +315,13 @@ __global__ __launch_bounds__(kThreads) void loss_final_kernel(const double* __re
 }
 
 // ----------------------------------------------------------------------------------------------------------------- loss gradients
+RON_KERNEL_ARGS_BEGIN
 struct GradDev {
   float* d_cls[RON_MAX_LAYERS];
   float* d_obj[RON_MAX_LAYERS];
   float* d_loc[RON_MAX_LAYERS];
 };
+RON_KERNEL_ARGS_END(GradDev)
 
 // d modified_smooth_l1 / d pred, one coordinate: 9 d in the square branch, sign(d) in the linear one; the branch test is the forward's
 __device__ inline float smooth_l1_grad(float pred, float target, float s) {

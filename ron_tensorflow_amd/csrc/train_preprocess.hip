@@ -27,7 +27,9 @@ constexpr int kSlabs = RON_MAX_GT / kWave;        // boxes per lane
 static_assert(RON_MAX_GT % kWave == 0, "the geometry kernel spreads RON_MAX_GT boxes over one wave");
 static_assert(RON_TRAIN_DRAWS == 5 + 10 * 10 * 12, "draw slots: 5 + outer x inner x 12");
 
+RON_KERNEL_ARGS_BEGIN
 struct Means { float m[3]; };
+RON_KERNEL_ARGS_END(Means)
 
 // tf.random_uniform([1], minval=0, maxval=m, dtype=tf.int32) from a uniform float in [0, 1)
 __device__ inline int int_draw(float u, int m) { return min((int)(u * (float)m), m - 1); }

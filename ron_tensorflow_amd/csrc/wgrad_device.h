@@ -1,5 +1,5 @@
-// Device helpers the weight-gradient kernels share (conv_wgrad.hip, stem_wgrad.hip): the roundings to the storage type, the
-// v_mfma_f32_16x16x32 wrapper and the transposed LDS read that feeds it.
+// Device helpers the weight-gradient kernels and the training packs share (conv_wgrad.hip, stem_wgrad.hip, conv_backward.hip,
+// conv_forward_train.hip): the roundings to the storage type, the v_mfma_f32_16x16x32 wrapper and the transposed LDS read that feeds it.
 #pragma once
 #include <hip/hip_runtime.h>
 

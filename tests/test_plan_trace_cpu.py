@@ -4,13 +4,20 @@ In a dry run the library makes every host decision and skips every HIP call; wit
 launch - kernel, grid, block, dynamic LDS bytes, size and CRC32C of every by-value argument - and one per asynchronous memset.
 Device addresses come from a counter, so two runs give the same bytes, and two TREES that write the same trace launch the same
 kernels with the same arguments.  tools/plan_sweep.cpp puts a `context variant dtype flags max_batch` line in front of each context
-and a `pass <name>` line in front of each argument pass (the last one, conv_planner_arguments, drives plan_conv / launch_conv_group
-through the single-operator entry points with forced tile configurations and split factors, refusals and their messages included).
+and a `pass <name>` line in front of each argument pass (conv_planner_arguments drives plan_conv / launch_conv_group through the
+single-operator entry points with forced tile configurations and split factors, refusals and their messages included; the last two,
+conv_forward_arguments and conv_chain_arguments, drive the training forward and the network-level chain).
 
-EXPECTED holds the digest of every section of the `--quick` sweep: literals recorded from the tree before the conv planner was
-gathered into one member plan (conv_mfma.hip plan_member), so a failure names the context or pass whose launches changed.  After an
-INTENDED plan change, re-record them (the sweep must have been built: tests/test_asan_plan_sweep.py, or `make -C
-ron_tensorflow_amd/csrc asan ASAN_ARGS=--quick`):
+What is hashed is well defined: every struct that reaches a kernel by value is declared without padding (RON_KERNEL_ARGS_BEGIN / _END,
+csrc/common.h; the compiler refuses a padded one, and trace_launch refuses a struct that was not declared so), so a digest depends on
+the argument values alone - not on the compiler, its flags, or the function a launch is written in.
+
+EXPECTED holds the digest of every section of the `--quick` sweep, so a failure names the context or pass whose launches changed.
+The literals were recorded when the argument structs lost their padding: against the trace of the tree before, 154 of 36090 lines
+differ, each only in the CRC of a 48-byte ViewDev argument (elementwise.hip: pack_kernel, unpack_kernel, l2norm_kernel), whose 4
+bytes of tail padding used to be hashed as they lay on the stack; every other line is byte for byte the one recorded before the conv
+planner was gathered into one member plan (conv_mfma.hip plan_member).  After an INTENDED plan change, re-record them (the sweep
+must have been built: tests/test_asan_plan_sweep.py, or `make -C ron_tensorflow_amd/csrc asan ASAN_ARGS=--quick`):
 
     python tests/test_plan_trace_cpu.py          # prints the EXPECTED table to paste below
 
@@ -46,29 +53,31 @@ EXPECTED = {
     'context 0 1 0x11 1': '5af93f8dad65971b',
     'context 0 1 0x11 13': '52bbd249c8b60c18',
     'context 0 1 0x11 32': 'f2cd7a106dd2265c',
-    'context 2 1 0x1 1': '94419925d34ffc86',
-    'context 2 3 0x1 1': '3f4cdc8b5ee595b0',
+    'context 2 1 0x1 1': '65b9184be8bdf71f',
+    'context 2 3 0x1 1': 'c88ef6f97c17c0ad',
     'context 2 1 0x1 13': '092b4e7d8867f460',
-    'context 2 1 0x1 32': 'd0746abaa274c629',
+    'context 2 1 0x1 32': '7f5a1be38eccef82',
     'context 2 3 0x1 32': 'ae7674ffa1729c57',
-    'context 2 1 0x9 1': '3ddfed487253c97c',
-    'context 2 1 0x9 13': 'bede07a668538d70',
-    'context 2 1 0x9 32': '89ad9b22e0bb936b',
-    'context 2 1 0x11 1': '7e66a25fade69658',
+    'context 2 1 0x9 1': '3f10d3786a5b9ee6',
+    'context 2 1 0x9 13': 'bbdb7186d3eb97e5',
+    'context 2 1 0x9 32': 'f353865656809873',
+    'context 2 1 0x11 1': '01d54e5a7a634170',
     'context 2 1 0x11 13': 'f3f7179a191c1107',
-    'context 2 1 0x11 32': '895d6d0ca31c07e5',
+    'context 2 1 0x11 32': '1e687dc78f7d8ec2',
     'context 1 1 0x1 32': 'c27552c23754eea7',
-    'context 3 1 0x1 1': '2c739194627eb10d',
+    'context 3 1 0x1 1': '8eab1af8df90498e',
     'context 3 1 0x1 32': '3d6de168ea5667da',
-    'context 3 0 0x0 1': '0c7e602a5108a202',
+    'context 3 0 0x0 1': '3e0ed1a499bb3c0f',
     'pass loss_arguments': 'cce9b8771b7e8bfd',
-    'pass conv_backward_arguments': 'df561f2056b80934',
+    'pass conv_backward_arguments': 'a16ea092513d601d',
     'pass stem_backward_arguments': 'f680e656aebe47ef',
     'pass op_backward_arguments': '472486200c7e1f34',
     'pass batchnorm_arguments': '63e474dfa231c86b',
     'pass optimizer_arguments': '82b7de58c71f575d',
     'pass conv_envelope': '213341073940a95a',
-    'pass conv_planner_arguments': 'af5972347d3ebe29',
+    'pass conv_planner_arguments': '0af9347b816153b3',
+    'pass conv_forward_arguments': '2c88547b28d13a56',
+    'pass conv_chain_arguments': '2737d407926c80bb',
 }
 
 

@@ -190,7 +190,7 @@ static int conv_backward_arguments() {
 
 // ron_conv_chain_forward / ron_conv_chain_backward in the dry run: the descriptor checks, every layer's plans, the carving of the
 // workspace and the refusals, over the chains of tests/conv_chain_cases.py and the VGG body of both RON-320 variants at batch 1 and
-// 32, with full and with NULL output sets.  Part of the FULL sweep only, like conv_forward_arguments below.
+// 32, with full and with NULL output sets.
 static int conv_chain_arguments() {
   struct Layer { int kind, k, dil, cout, relu, tap; };
   struct Chain { int n, h, w, cin; std::vector<Layer> layers; };
@@ -289,7 +289,6 @@ static int conv_chain_arguments() {
 // ron_conv2d_forward_nhwc in the dry run: the descriptor checks, the ConvLaunch of every route (plain, 7 x 7, the stem with and without
 // its kernel, 2 x 2 stride 2, transposed, the resident-weight images), the workspace and the refusals, over the case table of
 // tests/conv_fwd_cases.py plus the layer shapes of tools/conv_forward_time.py; and the 7 x 7 filter through ron_conv2d_backward_nhwc.
-// Part of the FULL sweep only: the launch trace of the quick sweep is pinned section by section (tests/test_plan_trace_cpu.py).
 static int conv_forward_arguments() {
   struct Case { int n, h, w, cin, cout, k, dil, stride, tr; };
   const Case cases[] = {{1, 1, 1, 64, 64, 3, 1, 1, 0},     {2, 5, 7, 64, 24, 3, 1, 1, 0},      {3, 3, 3, 128, 126, 3, 1, 1, 0},   {1, 10, 10, 64, 192, 3, 6, 1, 0},
@@ -981,17 +980,15 @@ int main(int argc, char** argv) {
     fprintf(stderr, "plan_sweep: plan_conv / launch_conv_group through the single-operator entry points: %s\n", ron_last_error());
     return 1;
   }
-  if (!quick) {
-    trace_note("pass conv_forward_arguments");
-    if (conv_forward_arguments()) {
-      fprintf(stderr, "plan_sweep: ron_conv2d_forward_nhwc planning / argument handling (and the 7 x 7 backward): %s\n", ron_last_error());
-      return 1;
-    }
-    trace_note("pass conv_chain_arguments");
-    if (conv_chain_arguments()) {
-      fprintf(stderr, "plan_sweep: ron_conv_chain_forward / ron_conv_chain_backward planning / argument handling: %s\n", ron_last_error());
-      return 1;
-    }
+  trace_note("pass conv_forward_arguments");
+  if (conv_forward_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_conv2d_forward_nhwc planning / argument handling (and the 7 x 7 backward): %s\n", ron_last_error());
+    return 1;
+  }
+  trace_note("pass conv_chain_arguments");
+  if (conv_chain_arguments()) {
+    fprintf(stderr, "plan_sweep: ron_conv_chain_forward / ron_conv_chain_backward planning / argument handling: %s\n", ron_last_error());
+    return 1;
   }
   if (g_trace != nullptr) fclose(g_trace);
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
