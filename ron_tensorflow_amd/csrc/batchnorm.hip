@@ -26,6 +26,7 @@
 #include <cmath>
 
 #include "common.h"
+#include "storage_device.h"      // round_storage
 
 namespace ron {
 namespace {
@@ -33,13 +34,6 @@ namespace {
 constexpr int kBnThreads = 256;
 constexpr int kBnMaxSlices = 1024;      // 4 per thread of the merge kernels
 constexpr int64_t kBnMaxRows = (int64_t)1 << 24;      // counts stay exact in fp32
-
-__device__ __forceinline__ float bn_round_bf16(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return f;
-  return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
-}
-template <bool BF16> __device__ __forceinline__ float bn_round(float f) { return BF16 ? bn_round_bf16(f) : (float)(_Float16)f; }
 
 // the geometry every kernel of an operator call shares
 RON_KERNEL_ARGS_BEGIN
@@ -108,14 +102,14 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(BnGeom g, const fl
     float k[4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
     load4(p, k);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) k[e] = bn_round<BF16>(k[e]);
+    for (int e = 0; e < 4; ++e) k[e] = round_storage<BF16>(k[e]);
 #pragma unroll 4
     for (int i = 1; i < mine; ++i) {
       float v[4];
       load4(p + i * step, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float d = bn_round<BF16>(v[e]) - k[e];
+        const float d = round_storage<BF16>(v[e]) - k[e];
         s1[e] += d;
         s2[e] += d * d;
       }
@@ -234,10 +228,10 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, const fl
     load4(x + base + i * step, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
+      const float xhat = (round_storage<BF16>(v[e]) - mu[e]) * rstd[e];
       float t = ga[e] * xhat + be[e];
       if (RELU) t = t > 0.f ? t : (t == t ? 0.f : t);          // NaN stays NaN
-      o[e] = bn_round<BF16>(t);
+      o[e] = round_storage<BF16>(t);
     }
     store4(y + base + i * step, o);
   }
@@ -271,8 +265,8 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_kernel(BnGeom g, const
       if (RELU) load4(y + base + i * step, m);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
-        const float dz = bn_round<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
-        const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
+        const float dz = round_storage<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
+        const float xhat = (round_storage<BF16>(v[e]) - mu[e]) * rstd[e];
         sb[e] += dz;
         sg[e] += dz * xhat;
       }
@@ -381,9 +375,9 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(BnGeom g, const f
     if (RELU) load4(y + base + i * step, m);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const float dz = bn_round<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
-      const float xhat = (bn_round<BF16>(v[e]) - mu[e]) * rstd[e];
-      o[e] = bn_round<BF16>(scale[e] * ((dz - mb[e]) - xhat * mg[e]));
+      const float dz = round_storage<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
+      const float xhat = (round_storage<BF16>(v[e]) - mu[e]) * rstd[e];
+      o[e] = round_storage<BF16>(scale[e] * ((dz - mb[e]) - xhat * mg[e]));
     }
     store4(dx + base + i * step, o);
   }
@@ -420,13 +414,6 @@ int plan_bn(const char* what, const ron_bn_desc* d, BnPlan* P) {
   P->off_part = 0;
   P->off_fin = align_up((int64_t)P->slices * 2 * d->c * 4, 256);
   P->total = P->off_fin + align_up((int64_t)2 * d->c * 4, 256);
-  return RON_OK;
-}
-
-int check_workspace(const char* what, const BnPlan& P, void* workspace, int64_t workspace_bytes) {
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (ron_batchnorm_workspace_bytes)",
-              what, (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
   return RON_OK;
 }
 
@@ -479,7 +466,7 @@ extern "C" int ron_batchnorm_train_nhwc(const ron_bn_desc* d, const float* x, co
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)y | (uintptr_t)mean | (uintptr_t)var |
                 (uintptr_t)moving_mean | (uintptr_t)moving_var) & 15) == 0,
               "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
-  if (int rc = check_workspace(what, P, workspace, workspace_bytes)) return rc;
+  if (int rc = check_workspace(what, "ron_batchnorm_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   if (d->dtype == RON_DTYPE_BF16)
@@ -502,7 +489,7 @@ extern "C" int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x,
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)(d->relu ? y : nullptr) | (uintptr_t)dy | (uintptr_t)gamma | (uintptr_t)mean | (uintptr_t)var |
                 (uintptr_t)dx | (uintptr_t)dgamma | (uintptr_t)dbeta) & 15) == 0,
               "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
-  if (int rc = check_workspace(what, P, workspace, workspace_bytes)) return rc;
+  if (int rc = check_workspace(what, "ron_batchnorm_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   hipStream_t s = (hipStream_t)stream;
   char* ws = static_cast<char*>(workspace);
   if (d->dtype == RON_DTYPE_BF16)

@@ -1,7 +1,8 @@
-// Shared host-side helpers of libron_hip.so (error reporting, HIP checks).
+// Shared host-side helpers of libron_hip.so (error reporting, HIP checks, the grid of a striding kernel, the workspace check).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <stdint.h>
@@ -35,6 +36,16 @@ void set_error(const char* fmt, ...);
   } while (0)
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
+// workgroups of 256 lanes for a kernel that strides over `total` items: at least one, at most `cap` (the training side's packs, sums
+// and elementwise backwards: 4096; the forward boundary of elementwise.hip: 2048)
+inline int grid_for(long long total, int cap = 256 * 16) { return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, cap)); }
+// The workspace of a call: there, as large as `sizer` (the entry point that gives its size) says, 256-byte aligned.  `what` starts
+// the messages.
+inline int check_workspace(const char* what, const char* sizer, const void* workspace, int64_t bytes, int64_t needed) {
+  RON_REQUIRE(workspace != nullptr && bytes >= needed, "%s: workspace of %lld bytes, %lld needed (%s)", what, (long long)bytes, (long long)needed, sizer);
+  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
+  return RON_OK;
+}
 
 // Dry run (RON_PLAN_ONLY=1 in the environment, read once): every host-side decision of the library is made - launch plans, tile
 // choices, split-K factors, kernel arguments, workspace sizes - but no HIP call: device "allocations" are distinct fake addresses

@@ -16,12 +16,10 @@
 
 #include "conv_mfma.h"
 #include "conv_train.h"
-#include "wgrad_device.h"
+#include "storage_device.h"      // the roundings to the storage type and back, pack8 / unpack8, the halo walk
 
 namespace ron {
 namespace {
-
-using namespace wgrad;      // wgrad_device.h: the roundings to the storage type and back
 
 // ---- pack: dense fp32 [N,H,W,Csrc] -> halo tensor of the storage type, EVERY pixel of the buffer written ---------------------------
 // The buffer holds `rows` pixels of Cdst channels; pixel `guard` is halo pixel 0 of the view.  Interior pixels get the rounded
@@ -44,54 +42,41 @@ __global__ void conv_bwd_pack_halo_kernel(PackArgs a) {
   // (every buffer of the entry point is below 2 GiB, plan_backward: the 16-byte pieces and the pixels fit 32-bit arithmetic)
   const unsigned vecs = a.Cdst / 8;
   const unsigned total = (unsigned)a.rows * vecs;
-  const unsigned Wp = a.W + a.pad, Hp = a.H + a.pad;
   const bool vec_ok = a.Csrc % 4 == 0;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const unsigned b = i / vecs;
     const int v = (int)(i - b * vecs);
     float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (b >= (unsigned)a.guard) {
-      const unsigned q = b - (unsigned)a.guard;
-      const unsigned r = q / Wp;
-      const int col = (int)(q - r * Wp);
-      const unsigned img = r / Hp;
-      const int row = (int)(r - img * Hp);
-      bool inside = col >= a.pad && row >= a.pad && img < (unsigned)a.N;
-      int sy = row - a.pad, sx = col - a.pad, sh = a.H, sw = a.W;
-      if (SCATTER && inside) {
-        sy -= a.soff; sx -= a.soff;
-        inside = sy >= 0 && sx >= 0 && sy % a.sstep == 0 && sx % a.sstep == 0;
-        sy /= a.sstep; sx /= a.sstep; sh = a.Hs; sw = a.Ws;
-        inside = inside && sy < sh && sx < sw;
-      }
-      if (inside) {
-        const long long s0 = (((long long)img * sh + sy) * sw + sx) * a.Csrc + v * 8;
-        if (vec_ok && v * 8 + 8 <= a.Csrc) {
-          const float4 lo = *reinterpret_cast<const float4*>(a.src + s0), hi = *reinterpret_cast<const float4*>(a.src + s0 + 4);
-          f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
-          if (a.mask != nullptr) {
-            const float4 ml = *reinterpret_cast<const float4*>(a.mask + s0), mh = *reinterpret_cast<const float4*>(a.mask + s0 + 4);
-            const float m[8] = {ml.x, ml.y, ml.z, ml.w, mh.x, mh.y, mh.z, mh.w};
+    const HaloPixel p = halo_pixel(b, a.guard, a.N, a.H, a.W, a.pad);
+    const unsigned img = p.img;
+    bool inside = p.inside;
+    int sy = p.y, sx = p.x, sh = a.H, sw = a.W;
+    if (SCATTER && inside) {
+      sy -= a.soff; sx -= a.soff;
+      inside = sy >= 0 && sx >= 0 && sy % a.sstep == 0 && sx % a.sstep == 0;
+      sy /= a.sstep; sx /= a.sstep; sh = a.Hs; sw = a.Ws;
+      inside = inside && sy < sh && sx < sw;
+    }
+    if (inside) {
+      const long long s0 = (((long long)img * sh + sy) * sw + sx) * a.Csrc + v * 8;
+      if (vec_ok && v * 8 + 8 <= a.Csrc) {
+        load8(a.src + s0, f);
+        if (a.mask != nullptr) {
+          float m[8];
+          load8(a.mask + s0, m);
+          keep_positive(f, m);
+        }
+      } else {
 #pragma unroll
-            for (int e = 0; e < 8; ++e) f[e] = m[e] > 0.f ? f[e] : 0.f;
-          }
-        } else {
-#pragma unroll
-          for (int e = 0; e < 8; ++e) {
-            if (v * 8 + e < a.Csrc) {
-              const float val = a.src[s0 + e];
-              f[e] = (a.mask == nullptr || a.mask[s0 + e] > 0.f) ? val : 0.f;
-            }
+        for (int e = 0; e < 8; ++e) {
+          if (v * 8 + e < a.Csrc) {
+            const float val = a.src[s0 + e];
+            f[e] = (a.mask == nullptr || a.mask[s0 + e] > 0.f) ? val : 0.f;
           }
         }
       }
     }
-    uint4 o;
-    o.x = round_bits<BF16>(f[0]) | ((unsigned)round_bits<BF16>(f[1]) << 16);
-    o.y = round_bits<BF16>(f[2]) | ((unsigned)round_bits<BF16>(f[3]) << 16);
-    o.z = round_bits<BF16>(f[4]) | ((unsigned)round_bits<BF16>(f[5]) << 16);
-    o.w = round_bits<BF16>(f[6]) | ((unsigned)round_bits<BF16>(f[7]) << 16);
-    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = o;
+    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = pack8<BF16>(f);
   }
 }
 
@@ -127,10 +112,7 @@ __global__ void conv_bwd_pack_weights_kernel(WpackArgs a) {
       if (n < a.cin && co + e < a.cout) v = a.w[((long long)ts * a.cin + n) * a.cout + co + e];
       h[e] = round_bits<BF16>(v);
     }
-    uint4 o;
-    o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
-    o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
-    *reinterpret_cast<uint4*>(a.out + i * 8) = o;
+    *reinterpret_cast<uint4*>(a.out + i * 8) = pack8_bits(h);
   }
 }
 
@@ -145,13 +127,10 @@ __global__ __launch_bounds__(256) void conv_bwd_colsum_kernel(const unsigned sho
   const long long r0 = (long long)blockIdx.x * chunk_rows, r1 = r0 + chunk_rows < rows ? r0 + chunk_rows : rows;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   for (long long r = r0 + rl; r < r1; r += 32) {
-    const uint4 d = *reinterpret_cast<const uint4*>(dz + r * cop + c0 + v * 8);
-    const unsigned u[4] = {d.x, d.y, d.z, d.w};
+    float f[8];
+    unpack8<BF16>(*reinterpret_cast<const uint4*>(dz + r * cop + c0 + v * 8), f);
 #pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      acc[2 * e] += bits_to_f<BF16>((unsigned short)(u[e] & 0xFFFFu));
-      acc[2 * e + 1] += bits_to_f<BF16>((unsigned short)(u[e] >> 16));
-    }
+    for (int e = 0; e < 8; ++e) acc[e] += f[e];
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) sums[rl][v * 8 + e] = acc[e];
@@ -202,9 +181,7 @@ int check_backward_call(const char* what, const char* sizer, const ron_conv_desc
   RON_REQUIRE(!d->relu || y != nullptr, "%s: relu is set and y is NULL (the mask is y > 0)", what);
   RON_REQUIRE(dx == nullptr || w != nullptr, "%s: dx needs w", what);
   RON_REQUIRE(dw == nullptr || x != nullptr, "%s: dw needs x", what);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (%s)", what,
-              (long long)workspace_bytes, (long long)P.total, sizer);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
+  if (int rc = check_workspace(what, sizer, workspace, workspace_bytes, P.total)) return rc;
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)y | (uintptr_t)dy) & 15) == 0, "%s: x, y and dy must be 16-byte aligned (they are read 16 bytes at a time)", what);
   if (dx != nullptr) {
     // what launch_conv would refuse is refused here, before anything is enqueued
@@ -496,21 +473,14 @@ __global__ void k2s2_pack_s2d_kernel(S2dArgs a) {
       const unsigned img = r / a.H;
       const int row = (int)(r - img * a.H);
       const long long s0 = (((long long)img * 2 * a.H + 2 * row + (t >> 1)) * 2 * a.W + 2 * col + (t & 1)) * a.C + c;
-      const float4 lo = *reinterpret_cast<const float4*>(a.src + s0), hi = *reinterpret_cast<const float4*>(a.src + s0 + 4);
-      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+      load8(a.src + s0, f);
       if (a.mask != nullptr) {
-        const float4 ml = *reinterpret_cast<const float4*>(a.mask + s0), mh = *reinterpret_cast<const float4*>(a.mask + s0 + 4);
-        const float m[8] = {ml.x, ml.y, ml.z, ml.w, mh.x, mh.y, mh.z, mh.w};
-#pragma unroll
-        for (int e = 0; e < 8; ++e) f[e] = m[e] > 0.f ? f[e] : 0.f;
+        float m[8];
+        load8(a.mask + s0, m);
+        keep_positive(f, m);
       }
     }
-    uint4 o;
-    o.x = round_bits<BF16>(f[0]) | ((unsigned)round_bits<BF16>(f[1]) << 16);
-    o.y = round_bits<BF16>(f[2]) | ((unsigned)round_bits<BF16>(f[3]) << 16);
-    o.z = round_bits<BF16>(f[4]) | ((unsigned)round_bits<BF16>(f[5]) << 16);
-    o.w = round_bits<BF16>(f[6]) | ((unsigned)round_bits<BF16>(f[7]) << 16);
-    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = o;
+    *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = pack8<BF16>(f);
   }
 }
 
@@ -529,10 +499,7 @@ __global__ void k2s2_pack_weights_kn_kernel(const float* w, unsigned short* out,
     unsigned short h[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) h[e] = round_bits<BF16>(n < cin ? w[(long long)(k + e) * cin + n] : 0.f);
-    uint4 o;
-    o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
-    o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
-    *reinterpret_cast<uint4*>(out + i * 8) = o;
+    *reinterpret_cast<uint4*>(out + i * 8) = pack8_bits(h);
   }
 }
 
@@ -557,15 +524,9 @@ __global__ void k2s2_unpack_d2s_kernel(D2sArgs a) {
     const int ox = (int)(pix % (2 * a.W));
     const int oy = (int)((pix / (2 * a.W)) % (2 * a.H));
     const long long img = pix / ((long long)4 * a.W * a.H);
-    const long long q = (img * (a.H + 1) + 1 + (oy >> 1)) * (a.W + 1) + 1 + (ox >> 1);
-    const uint4 d = *reinterpret_cast<const uint4*>(a.in + q * 4 * a.C + ((oy & 1) * 2 + (ox & 1)) * a.C + g * 8);
-    const unsigned u[4] = {d.x, d.y, d.z, d.w};
+    const long long q = halo_off(img, oy >> 1, ox >> 1, a.H, a.W, 1, 4 * a.C);
     float f[8];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      f[2 * e] = bits_to_f<BF16>((unsigned short)(u[e] & 0xFFFFu));
-      f[2 * e + 1] = bits_to_f<BF16>((unsigned short)(u[e] >> 16));
-    }
+    unpack8<BF16>(*reinterpret_cast<const uint4*>(a.in + q + ((oy & 1) * 2 + (ox & 1)) * a.C + g * 8), f);
     float* o = a.dx + i * 8;
     if (a.vec_store) {
       *reinterpret_cast<float4*>(o) = make_float4(f[0], f[1], f[2], f[3]);

@@ -28,12 +28,10 @@
 
 #include "conv_mfma.h"
 #include "conv_train.h"
-#include "wgrad_device.h"
+#include "storage_device.h"      // the roundings, pack8 / unpack8, the halo walk, the pool's first maximum
 
 namespace ron {
 namespace {
-
-using namespace wgrad;      // round_bits, bits_to_f
 
 // ---- the join: out(buffer of `rows` pixels, halo pixel 0 at pixel `guard`) = round((float(g) + add1 + add2) * (mask > 0)) ----------------
 // g and mask are halo tensors of the map (their own halo and pixel stride), add1 / add2 dense fp32 [N,H,W,Csrc]; each may be null.
@@ -52,82 +50,58 @@ struct JoinArgs {
 };
 RON_KERNEL_ARGS_END(JoinArgs)
 
-__device__ __forceinline__ long long halo_off(long long img, int y, int x, int H, int W, int pad, int cs) {
-  return ((img * (H + pad) + y + pad) * (W + pad) + x + pad) * cs;
-}
-
 template <bool BF16>
 __global__ __launch_bounds__(256) void chain_join_kernel(JoinArgs a) {
   // (every buffer of the chain is below 2 GiB, plan_chain: the 16-byte pieces and the pixels fit 32-bit arithmetic)
   const unsigned vecs = a.Cdst / 8;
   const unsigned total = (unsigned)a.rows * vecs;
-  const unsigned Wp = a.W + a.pad, Hp = a.H + a.pad;
   const bool vec_ok = a.Csrc % 8 == 0;
   const bool copy = a.add1 == nullptr && a.add2 == nullptr && a.mask == nullptr;
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
     const unsigned b = i / vecs;
     const int c0 = (int)(i - b * vecs) * 8;
     uint4 o = {0u, 0u, 0u, 0u};
-    if (b >= (unsigned)a.guard && c0 < a.Csrc) {
-      const unsigned q = b - (unsigned)a.guard;
-      const unsigned r = q / Wp;
-      const int col = (int)(q - r * Wp);
-      const unsigned img = r / Hp;
-      const int row = (int)(r - img * Hp);
-      if (col >= a.pad && row >= a.pad && img < (unsigned)a.N) {
-        const int y = row - a.pad, x = col - a.pad;
-        const long long dense = (((long long)img * a.H + y) * a.W + x) * a.Csrc + c0;
-        const long long go = a.g != nullptr ? halo_off(img, y, x, a.H, a.W, a.gpad, a.gcs) + c0 : 0;
-        const long long mo = a.mask != nullptr ? halo_off(img, y, x, a.H, a.W, a.mpad, a.mcs) + c0 : 0;
-        if (vec_ok && copy) {
-          o = *reinterpret_cast<const uint4*>(a.g + go);
+    HaloPixel p = {false, 0u, 0, 0};
+    if (c0 < a.Csrc) p = halo_pixel(b, a.guard, a.N, a.H, a.W, a.pad);
+    if (p.inside) {
+      const long long img = p.img;
+      const int y = p.y, x = p.x;
+      const long long dense = (((long long)img * a.H + y) * a.W + x) * a.Csrc + c0;
+      const long long go = a.g != nullptr ? halo_off(img, y, x, a.H, a.W, a.gpad, a.gcs) + c0 : 0;
+      const long long mo = a.mask != nullptr ? halo_off(img, y, x, a.H, a.W, a.mpad, a.mcs) + c0 : 0;
+      if (vec_ok && copy) {
+        o = *reinterpret_cast<const uint4*>(a.g + go);
+      } else {
+        float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (vec_ok) {
+          float t[8];
+          if (a.g != nullptr) unpack8<BF16>(*reinterpret_cast<const uint4*>(a.g + go), f);
+          if (a.add1 != nullptr) {
+            load8(a.add1 + dense, t);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] = a.g != nullptr ? f[e] + t[e] : t[e];
+          }
+          if (a.add2 != nullptr) {
+            load8(a.add2 + dense, t);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) f[e] += t[e];
+          }
+          if (a.mask != nullptr) {
+            unpack8<BF16>(*reinterpret_cast<const uint4*>(a.mask + mo), t);
+            keep_positive(f, t);
+          }
         } else {
-          float f[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-          bool keep[8] = {true, true, true, true, true, true, true, true};
-          if (vec_ok) {
-            if (a.g != nullptr) {
-              const uint4 gv = *reinterpret_cast<const uint4*>(a.g + go);
-              const unsigned u[4] = {gv.x, gv.y, gv.z, gv.w};
 #pragma unroll
-              for (int e = 0; e < 8; ++e) f[e] = bits_to_f<BF16>((unsigned short)(u[e >> 1] >> (16 * (e & 1))));
-            }
-            if (a.add1 != nullptr) {
-              const float4 lo = *reinterpret_cast<const float4*>(a.add1 + dense), hi = *reinterpret_cast<const float4*>(a.add1 + dense + 4);
-              const float t[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-              for (int e = 0; e < 8; ++e) f[e] = a.g != nullptr ? f[e] + t[e] : t[e];
-            }
-            if (a.add2 != nullptr) {
-              const float4 lo = *reinterpret_cast<const float4*>(a.add2 + dense), hi = *reinterpret_cast<const float4*>(a.add2 + dense + 4);
-              const float t[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-#pragma unroll
-              for (int e = 0; e < 8; ++e) f[e] += t[e];
-            }
-            if (a.mask != nullptr) {
-              const uint4 mv = *reinterpret_cast<const uint4*>(a.mask + mo);
-              const unsigned u[4] = {mv.x, mv.y, mv.z, mv.w};
-#pragma unroll
-              for (int e = 0; e < 8; ++e) keep[e] = bits_to_f<BF16>((unsigned short)(u[e >> 1] >> (16 * (e & 1)))) > 0.f;
-            }
-          } else {
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-              keep[e] = false;
-              if (c0 + e < a.Csrc) {
-                float t = a.g != nullptr ? bits_to_f<BF16>(a.g[go + e]) : 0.f;
-                if (a.add1 != nullptr) t = a.g != nullptr ? t + a.add1[dense + e] : a.add1[dense + e];
-                if (a.add2 != nullptr) t += a.add2[dense + e];
-                f[e] = t;
-                keep[e] = a.mask == nullptr || bits_to_f<BF16>(a.mask[mo + e]) > 0.f;
-              }
+          for (int e = 0; e < 8; ++e) {
+            if (c0 + e < a.Csrc) {
+              float t = a.g != nullptr ? bits_to_f<BF16>(a.g[go + e]) : 0.f;
+              if (a.add1 != nullptr) t = a.g != nullptr ? t + a.add1[dense + e] : a.add1[dense + e];
+              if (a.add2 != nullptr) t += a.add2[dense + e];
+              f[e] = (a.mask == nullptr || bits_to_f<BF16>(a.mask[mo + e]) > 0.f) ? t : 0.f;
             }
           }
-          unsigned short h[8];
-#pragma unroll
-          for (int e = 0; e < 8; ++e) h[e] = round_bits<BF16>(keep[e] ? f[e] : 0.f);
-          o.x = h[0] | ((unsigned)h[1] << 16); o.y = h[2] | ((unsigned)h[3] << 16);
-          o.z = h[4] | ((unsigned)h[5] << 16); o.w = h[6] | ((unsigned)h[7] << 16);
         }
+        o = pack8<BF16>(f);
       }
     }
     *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = o;
@@ -147,26 +121,14 @@ RON_KERNEL_ARGS_END(ZeroArgs)
 __global__ __launch_bounds__(256) void chain_zero_kernel(ZeroArgs a) {
   const unsigned vecs = a.C / 8;
   const unsigned total = (unsigned)a.rows * vecs;
-  const unsigned Wp = a.W + a.pad, Hp = a.H + a.pad;
   const uint4 zero4 = {0u, 0u, 0u, 0u};
   for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-    const unsigned b = i / vecs;
-    bool inside = false;
-    if (b >= (unsigned)a.guard) {
-      const unsigned q = b - (unsigned)a.guard;
-      const unsigned r = q / Wp;
-      const int col = (int)(q - r * Wp);
-      const unsigned img = r / Hp;
-      const int row = (int)(r - img * Hp);
-      inside = col >= a.pad && row >= a.pad && img < (unsigned)a.N;
-    }
-    if (!inside) *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = zero4;
+    if (!halo_pixel(i / vecs, a.guard, a.N, a.H, a.W, a.pad).inside) *reinterpret_cast<uint4*>(a.out + (long long)i * 8) = zero4;
   }
 }
 
 // ---- pool backward on views: dx(window position) = g(window) at the FIRST maximum of the stored x, 0 at the others -------------------------
-// The order is (0,0) (0,1) (1,0) (1,1) and a later position takes over only when it is greater (op_backward.hip: TensorFlow's
-// MaxPoolGrad); positions an odd map does not have are neither read nor written.  One lane = one window x 8 channels: four 16-byte
+// The rule is first_max_2x2 (storage_device.h), the one of ron_maxpool2x2_backward_nhwc; positions an odd map does not have are neither read nor written.  One lane = one window x 8 channels: four 16-byte
 // loads of x, one of g, four 16-byte stores; every interior element of dx is written exactly once, its halo is left alone.
 RON_KERNEL_ARGS_BEGIN
 struct PoolBwdViewArgs {
@@ -199,21 +161,14 @@ __global__ __launch_bounds__(256) void chain_pool_bwd_kernel(PoolBwdViewArgs a) 
     if (has_r) v10 = *reinterpret_cast<const uint4*>(a.x + x00 + xrow);
     if (has_r && has_c) v11 = *reinterpret_cast<const uint4*>(a.x + x00 + xrow + a.C);
     const uint4 gv = *reinterpret_cast<const uint4*>(a.g + halo_off(img, oy, ox, a.OH, a.OW, a.gpad, a.C) + c0);
-    const unsigned u00[4] = {v00.x, v00.y, v00.z, v00.w}, u01[4] = {v01.x, v01.y, v01.z, v01.w};
-    const unsigned u10[4] = {v10.x, v10.y, v10.z, v10.w}, u11[4] = {v11.x, v11.y, v11.z, v11.w};
+    float f00[8], f01[8], f10[8], f11[8];
+    unpack8<BF16>(v00, f00); unpack8<BF16>(v01, f01); unpack8<BF16>(v10, f10); unpack8<BF16>(v11, f11);
     const unsigned ug[4] = {gv.x, gv.y, gv.z, gv.w};
     unsigned o[4][4] = {{0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}, {0u, 0u, 0u, 0u}};
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
       const int wd = e >> 1, sh = 16 * (e & 1);
-      float best = bits_to_f<BF16>((unsigned short)(u00[wd] >> sh));
-      int at = 0;
-      float v = bits_to_f<BF16>((unsigned short)(u01[wd] >> sh));
-      if (has_c && v > best) { best = v; at = 1; }
-      v = bits_to_f<BF16>((unsigned short)(u10[wd] >> sh));
-      if (has_r && v > best) { best = v; at = 2; }
-      v = bits_to_f<BF16>((unsigned short)(u11[wd] >> sh));
-      if (has_r && has_c && v > best) { best = v; at = 3; }
+      const int at = first_max_2x2(f00[e], f01[e], f10[e], f11[e], has_c, has_r);
       const unsigned grad = ((ug[wd] >> sh) & 0xFFFFu) << sh;
 #pragma unroll
       for (int p = 0; p < 4; ++p) o[p][wd] |= at == p ? grad : 0u;
@@ -413,13 +368,6 @@ int launch_pool_bwd(int dtype, const TensorView& x, const TensorView& g, const T
 
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
-int check_workspace(const char* what, const ChainPlan& P, const void* workspace, int64_t workspace_bytes) {
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (ron_conv_chain_workspace_bytes)", what,
-              (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
-  return RON_OK;
-}
-
 // what launch_conv would refuse is refused before anything is enqueued
 int describe(ConvLaunch c, char* ws) {
   if (c.bias == nullptr) c.bias = reinterpret_cast<const float*>(ws);
@@ -475,7 +423,7 @@ extern "C" int ron_conv_chain_forward(const ron_chain_desc* d, const float* x, c
     RON_REQUIRE(!l.tap || (taps != nullptr && taps[i] != nullptr), "conv chain forward: layer %d is tapped and taps[%d] is NULL", i, i);
     RON_REQUIRE(!l.tap || aligned16(taps[i]), "conv chain forward: taps[%d] must be 16-byte aligned", i);
   }
-  if (int rc = check_workspace("conv chain forward", P, workspace, workspace_bytes)) return rc;
+  if (int rc = check_workspace("conv chain forward", "ron_conv_chain_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   for (int i = 0; i < L; ++i)
     if (d->layers[i].kind == RON_CHAIN_CONV)
@@ -539,7 +487,7 @@ extern "C" int ron_conv_chain_backward(const ron_chain_desc* d, const float* dy,
     RON_REQUIRE(dw == nullptr || ((uintptr_t)dw[i] & 3) == 0, "conv chain backward: dw[%d] must be 4-byte aligned", i);
     RON_REQUIRE(dbias == nullptr || ((uintptr_t)dbias[i] & 3) == 0, "conv chain backward: dbias[%d] must be 4-byte aligned", i);
   }
-  if (int rc = check_workspace("conv chain backward", P, workspace, workspace_bytes)) return rc;
+  if (int rc = check_workspace("conv chain backward", "ron_conv_chain_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   char* ws = static_cast<char*>(workspace);
   // need[j]: somebody wants the gradient of activation j - the caller (dx), or a convolution in front of it (its dw, dbias or dx)
   bool need[RON_CHAIN_MAX_LAYERS + 1];

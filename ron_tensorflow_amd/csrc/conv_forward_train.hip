@@ -21,12 +21,10 @@
 
 #include "conv_mfma.h"
 #include "conv_train.h"
-#include "wgrad_device.h"
+#include "storage_device.h"      // the roundings to the storage type, pack8
 
 namespace ron {
 namespace {
-
-using namespace wgrad;      // wgrad_device.h: the roundings to the storage type
 
 RON_KERNEL_ARGS_BEGIN
 struct FwdWpackArgs {
@@ -98,18 +96,12 @@ __global__ void conv_fwd_pack_rows_kernel(const float* w, unsigned short* out, i
     const float* src = w + ((long long)nb * 64 + nl) * K + kt * 64 + piece * 8;
     float f[8];
     if (vec) {
-      const float4 lo = *reinterpret_cast<const float4*>(src), hi = *reinterpret_cast<const float4*>(src + 4);
-      f[0] = lo.x; f[1] = lo.y; f[2] = lo.z; f[3] = lo.w; f[4] = hi.x; f[5] = hi.y; f[6] = hi.z; f[7] = hi.w;
+      load8(src, f);
     } else {
 #pragma unroll
       for (int e = 0; e < 8; ++e) f[e] = src[e];
     }
-    uint4 o;
-    o.x = round_bits<BF16>(f[0]) | ((unsigned)round_bits<BF16>(f[1]) << 16);
-    o.y = round_bits<BF16>(f[2]) | ((unsigned)round_bits<BF16>(f[3]) << 16);
-    o.z = round_bits<BF16>(f[4]) | ((unsigned)round_bits<BF16>(f[5]) << 16);
-    o.w = round_bits<BF16>(f[6]) | ((unsigned)round_bits<BF16>(f[7]) << 16);
-    *reinterpret_cast<uint4*>(out + i * 8) = o;
+    *reinterpret_cast<uint4*>(out + i * 8) = pack8<BF16>(f);
   }
 }
 
@@ -187,7 +179,8 @@ int forward_pack_w(const ron_conv_desc* d, const ForwardPlan& P, const ConvLaunc
 }  // namespace
 
 // ---- conv_train.h: the plan and the steps of the forward ----------------------------------------------------------------------------
-// Everything the entry point decides on the host: the descriptor's checks, the ConvLaunch of setup_conv, the carving of the workspace
+// Everything the entry point decides on the host: the descriptor's checks, the ConvLaunch of setup_conv (conv_launch_geometry gives
+// both their geometry), the carving of the workspace
 int train_plan_forward(const ron_conv_desc* d, ForwardPlan* P) {
   if (int rc0 = check_conv_desc(d)) return rc0;       // sizes, filter, stride, dilation inside the envelope; flags 0 or 1
   RON_REQUIRE(d->dtype == RON_DTYPE_BF16 || d->dtype == RON_DTYPE_F16, "conv forward: dtype %d: bf16 or fp16 only (fp32 and f16x3 run through ron_conv2d_nhwc)", d->dtype);
@@ -195,18 +188,11 @@ int train_plan_forward(const ron_conv_desc* d, ForwardPlan* P) {
               "conv forward: a plain operator planned by shape (pool, center_from, in_cstride, in_coff = 0, tile_cfg = -1, splitk = -1)");
   RON_REQUIRE(d->kh == d->kw, "conv forward: filter %d x %d: square filters only", d->kh, d->kw);
   const bool k2s2 = d->kh == 2 && d->stride == 2 && d->dilation == 1;
-  int ho = d->h, wo = d->w;
-  ConvLaunch& c = P->conv;
   if (d->transpose) {
     RON_REQUIRE(k2s2, "conv forward: transposed: filter %d x %d, stride %d, dilation %d: 2 x 2 stride 2 only", d->kh, d->kw, d->stride, d->dilation);
     RON_REQUIRE(d->cin % 64 == 0, "conv forward: cin %d must be a multiple of 64", d->cin);
     RON_REQUIRE(d->cout % 128 == 0, "conv forward: transposed: cout %d must be a multiple of 128", d->cout);
     P->kind = kFwdTransposed;
-    ho = 2 * d->h; wo = 2 * d->w;
-    c.Cout = c.Npad = 4 * d->cout;
-    c.up = 2; c.up_cout = d->cout;
-    c.kh = c.kw = 1; c.stride = 1; c.dil = 1; c.cpad = 0;
-    c.Ho = d->h; c.Wo = d->w;
     P->K = d->cin;
   } else if (d->stride != 1) {
     RON_REQUIRE(k2s2, "conv forward: stride %d with a %d x %d filter at dilation %d: the only strided convolution is 2 x 2 at stride 2", d->stride, d->kh,
@@ -214,31 +200,23 @@ int train_plan_forward(const ron_conv_desc* d, ForwardPlan* P) {
     RON_REQUIRE(d->h % 2 == 0 && d->w % 2 == 0, "conv forward: map %d x %d: the strided convolution needs even sides", d->h, d->w);
     RON_REQUIRE(d->cin % 64 == 0, "conv forward: cin %d must be a multiple of 64", d->cin);
     P->kind = kFwdStrided;
-    ho = d->h / 2; wo = d->w / 2;
-    c.kh = c.kw = 2; c.stride = 2; c.dil = 1; c.cpad = 0;
     P->K = 4 * d->cin;
   } else if (d->cin == 3) {
     RON_REQUIRE(d->kh == 3 && d->dilation == 1 && d->cout == 64, "conv forward: a 3-channel input: the 3 x 3, 3 -> 64 stem at dilation 1 only (%d x %d, cout %d, dilation %d)",
                 d->kh, d->kw, d->cout, d->dilation);
     // the routes of ron_conv2d_nhwc: with the ReLU the stem kernel, without it (the kernel has it built in) im2col + one GEMM step
     P->kind = d->relu ? kFwdStem : kFwdStemIm2col;
-    c.kh = c.kw = 1; c.stride = 1; c.dil = 1; c.cpad = 0;
     P->K = 64;
   } else {
     RON_REQUIRE(d->kh == 1 || d->kh == 3 || (d->kh == 7 && d->dilation == 1),
                 "conv forward: filter %d x %d at dilation %d: 1 x 1, 3 x 3, or 7 x 7 at dilation 1 only", d->kh, d->kw, d->dilation);
     RON_REQUIRE(d->cin % 64 == 0, "conv forward: cin %d must be a multiple of 64 (or the 3-channel stem)", d->cin);
-    P->pad = (d->kh - 1) * d->dilation / 2;
-    c.kh = d->kh; c.kw = d->kw; c.stride = 1; c.dil = d->dilation; c.cpad = P->pad;
     P->K = d->kh * d->kw * d->cin;
   }
-  if (P->kind != kFwdTransposed) {
-    c.Cout = d->cout;
-    c.Npad = (int)align_up(d->cout, conv_n_tile(d->cout));
-    c.Ho = ho; c.Wo = wo;
-  }
-  c.dtype = d->dtype;
-  c.relu = d->relu;
+  int ho, wo;
+  ConvLaunch& c = P->conv;
+  conv_launch_geometry(d, &c, &ho, &wo);
+  P->pad = c.cpad;
   c.cfg = -1; c.splitk = -1;
   const bool stem = P->kind == kFwdStem || P->kind == kFwdStemIm2col;
   c.in = dense_view(d->n, d->h, d->w, stem ? 64 : d->cin, P->pad);
@@ -249,7 +227,7 @@ int train_plan_forward(const ron_conv_desc* d, ForwardPlan* P) {
   P->out_bytes = c.out.bytes;
   RON_REQUIRE(P->x_bytes < lim && P->w_bytes < lim && P->out_bytes < lim, "conv forward: a packed tensor would reach 2 GiB");
   c.wgt_bytes = P->w_bytes;
-  P->c64 = P->kind == kFwdPlain && d->kh == 3 && d->cin == 64 && c.Npad == d->cout;
+  P->c64 = conv_c64_wants_images(d->dtype, d->kh, d->kw, d->cin, d->cout, c.Npad);      // (a plain convolution: the others have no 3 x 3)
   if (P->c64) P->c64_bytes = (int64_t)(c.Npad / 64) * 9 * 64 * 64 * 2;
   P->bias_total = P->kind == kFwdStem ? 64 : c.Npad;
   P->bias_live = P->kind == kFwdTransposed ? c.Npad : d->cout;
@@ -320,9 +298,7 @@ extern "C" int ron_conv2d_forward_parts_nhwc(const ron_conv_desc* d, const float
   ForwardPlan P;
   if (int rc = train_plan_forward(d, &P)) return rc;
   RON_REQUIRE(x != nullptr && w != nullptr && y != nullptr, "conv forward: x, w or y is NULL");
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "conv forward: workspace of %lld bytes, %lld needed (ron_conv2d_forward_workspace_bytes)",
-              (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "conv forward: the workspace must be 256-byte aligned");
+  if (int rc = check_workspace("conv forward", "ron_conv2d_forward_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   const bool stem = P.kind == kFwdStem || P.kind == kFwdStemIm2col;
   RON_REQUIRE(((uintptr_t)x & (stem ? 3 : 15)) == 0 && ((uintptr_t)y & 15) == 0,
               "conv forward: x and y must be 16-byte aligned (x of the 3-channel stem: 4-byte)");

@@ -97,6 +97,11 @@ constexpr int kConvMaxTileOrder = 63;    // ConvArgs::m_fastest
 // The descriptor of a single-operator entry point, before any arithmetic on it: sizes, filter, stride and dilation >= 1 and inside
 // the envelope, the flags 0 or 1.  RON_OK, or RON_ERR_INVALID with the message set.
 int check_conv_desc(const ron_conv_desc* d);
+// The geometry of the launch that computes the convolution of a descriptor (ops.cpp), behind the caller's own checks (setup_conv and
+// train_plan_forward accept different envelopes): dtype, relu, kh / kw / stride / dil / cpad, up / up_cout, Cout, Npad, Ho / Wo and
+// *ho x *wo, the output map.  Plain: SAME at stride 1.  Strided: kernel == stride, no padding.  Transposed: kernel == stride, a 1x1
+// launch on the input grid with the pixel-shuffle epilogue.  The 3-channel 3x3 stem: one K step of im2col rows, a 1x1 launch.
+void conv_launch_geometry(const ron_conv_desc* d, ConvLaunch* c, int* ho, int* wo);
 
 int launch_conv(const ConvLaunch& c, hipStream_t stream);
 // what launch_conv would do with `c`: out = {tile configuration (kCfg*), split-K factor, tile order (ConvArgs::m_fastest), K order (taps_inner)};
@@ -105,6 +110,10 @@ int launch_conv(const ConvLaunch& c, hipStream_t stream);
 int conv_describe(const ConvLaunch& c, int out[4], int* n_tile = nullptr);
 // 3x3 / stride 1 / pad 1 on a 64-channel map, weights resident in LDS (conv_c64.hip); pack_conv_c64_weights builds wgt_c64
 bool conv_c64_applicable(const ConvLaunch& c);
+// a layer whose packed weights get those images beside the rows (graph.cpp, ops.cpp, conv_forward_train.hip): the launch decides later
+inline bool conv_c64_wants_images(int dtype, int kh, int kw, int cin, int cout, int npad) {
+  return (dtype == RON_DTYPE_BF16 || dtype == RON_DTYPE_F16) && kh == 3 && kw == 3 && cin == 64 && npad == cout && cout % 64 == 0;
+}
 int launch_conv_c64(const ConvLaunch& c, hipStream_t stream);
 std::vector<uint8_t> pack_conv_c64_weights(const std::vector<float>& rows, int npad, int dtype);
 // 3x3 / stride 1 / pad 1 with the input halo patch staged once per channel chunk (conv_patch.hip)

@@ -14,8 +14,6 @@ namespace ron {
 
 constexpr int kWgStep = 32;      // pixels per K step of the weight gradient: its packed operands are zero up to the next multiple
 
-// workgroups of 256 lanes for the packs and sums, which stride over `total` items
-inline int grid_for(long long total) { return (int)std::max<long long>(1, std::min<long long>((total + 255) / 256, 256 * 16)); }
 // the offset of the next piece of a workspace that holds *total bytes so far; pieces are 256-byte aligned
 inline int64_t carve(int64_t* total, int64_t bytes) {
   const int64_t o = *total;
@@ -23,7 +21,7 @@ inline int64_t carve(int64_t* total, int64_t bytes) {
   return o;
 }
 
-// ron_conv2d_forward_nhwc: the descriptor's checks, the ConvLaunch of setup_conv, the carving of the operator's own workspace
+// ron_conv2d_forward_nhwc: the descriptor's checks, the ConvLaunch of setup_conv (conv_launch_geometry), the carving of the operator's own workspace
 struct ForwardPlan {
   int kind = 0;                 // kFwd* of conv_forward_train.hip (0: a plain stride-1 SAME convolution)
   int pad = 0, K = 0;

@@ -30,7 +30,7 @@
 
 #include "conv_mfma.h"
 #include "conv_train.h"
-#include "wgrad_device.h"
+#include "storage_device.h"      // the MFMA and its transposed operand read (shared with stem_wgrad.hip)
 
 namespace ron {
 namespace {
@@ -38,8 +38,6 @@ namespace {
 constexpr int kWgTile = 128;       // channels per tile side
 constexpr int kWgImage = kWgStep * kWgTile * 2;     // bytes of one staged operand image
 constexpr int kWgLds = 4 * kWgImage;                // two operands, double buffered: 32 KB, inside the default limit
-
-using namespace wgrad;      // wgrad_device.h: the MFMA and its transposed operand read (shared with stem_wgrad.hip)
 
 // byte offset of 16-byte chunk `ch` (0..15) of pixel row `row` (0..31) in a staged image
 __device__ __forceinline__ int image_off(int row, int ch) { return 256 * row + 16 * (ch ^ (((row & 3) << 2) | ((row >> 2) & 3))); }

@@ -270,7 +270,7 @@ __global__ void fill_random_kernel(ViewDev out, unsigned seed) {
   }
 }
 
-int grid_for(long long total) { return (int)std::min<long long>((total + 255) / 256, 256 * 8); }
+constexpr int kGridCap = 256 * 8;      // workgroups of a launch at most (grid_for, common.h)
 int vec_elems(int dtype) { return dtype == RON_DTYPE_F16X3 ? 8 : 16 / (int)dtype_size(dtype); }   // IO<T>::V of the dtype
 
 // launches KERNEL<T> for the element type of `dtype`
@@ -286,7 +286,7 @@ int vec_elems(int dtype) { return dtype == RON_DTYPE_F16X3 ? 8 : 16 / (int)dtype
 
 int launch_im2col_c3(const float* x, int n, int h, int w, int dtype, void* out, int kchunk, hipStream_t s) {
   const long long total = (long long)n * h * w * (kchunk / vec_elems(dtype));
-  const int g = grid_for(total);
+  const int g = grid_for(total, kGridCap);
   RON_DISPATCH_DTYPE(dtype, im2col_c3_kernel, g, s, x, n, h, w, kchunk, out);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -298,7 +298,7 @@ int launch_maxpool2x2(const TensorView& in, const TensorView& out, int dtype, hi
   RON_REQUIRE(out.C % V == 0 && in.cstride % V == 0 && out.cstride % V == 0 && in.coff % V == 0 && out.coff % V == 0,
               "maxpool: channels must be a multiple of %d", V);
   const long long total = (long long)out.N * out.H * out.W * (out.C / V);
-  const int g = grid_for(total);
+  const int g = grid_for(total, kGridCap);
   RON_DISPATCH_DTYPE(dtype, maxpool2x2_kernel, g, s, to_dev(in), to_dev(out));
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -308,7 +308,7 @@ int launch_maxpool3x3s1(const TensorView& in, const TensorView& out, int dtype, 
   const int V = vec_elems(dtype);
   RON_REQUIRE(in.H == out.H && in.W == out.W && in.C == out.C && in.N == out.N && in.pad >= 1, "maxpool3x3: shape / halo mismatch");
   RON_REQUIRE(out.C % V == 0 && in.cstride % V == 0 && out.cstride % V == 0, "maxpool3x3: channels must be a multiple of %d", V);
-  const int g = grid_for((long long)out.N * out.H * out.W * (out.C / V));
+  const int g = grid_for((long long)out.N * out.H * out.W * (out.C / V), kGridCap);
   RON_DISPATCH_DTYPE(dtype, maxpool3x3s1_kernel, g, s, to_dev(in), to_dev(out));
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -333,7 +333,7 @@ static int check_split_view(const TensorView& v, int dtype) {
 int launch_pack_input(const float* x, const TensorView& out, int dtype, hipStream_t s) {
   int rc = check_split_view(out, dtype);
   if (rc) return rc;
-  const int g = grid_for((long long)out.N * out.H * out.W * out.C);
+  const int g = grid_for((long long)out.N * out.H * out.W * out.C, kGridCap);
   RON_DISPATCH_DTYPE(dtype, pack_kernel, g, s, x, to_dev(out));
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -342,7 +342,7 @@ int launch_pack_input(const float* x, const TensorView& out, int dtype, hipStrea
 int launch_fill_random(const TensorView& out, int dtype, unsigned seed, hipStream_t s) {
   int rc = check_split_view(out, dtype);
   if (rc) return rc;
-  const int g = grid_for((long long)out.N * out.H * out.W * out.C);
+  const int g = grid_for((long long)out.N * out.H * out.W * out.C, kGridCap);
   RON_DISPATCH_DTYPE(dtype, fill_random_kernel, g, s, to_dev(out), seed);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
@@ -351,7 +351,7 @@ int launch_fill_random(const TensorView& out, int dtype, unsigned seed, hipStrea
 int launch_unpack(const TensorView& in, int dtype, int in_is_f32, float* y, hipStream_t s) {
   int rc = check_split_view(in, in_is_f32 ? RON_DTYPE_F32 : dtype);
   if (rc) return rc;
-  const int g = grid_for((long long)in.N * in.H * in.W * in.C);
+  const int g = grid_for((long long)in.N * in.H * in.W * in.C, kGridCap);
   RON_DISPATCH_DTYPE(in_is_f32 ? RON_DTYPE_F32 : dtype, unpack_kernel, g, s, to_dev(in), y);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;

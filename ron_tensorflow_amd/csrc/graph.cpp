@@ -584,7 +584,7 @@ int add_conv(ron_ctx* c, Op o, const Rows& r) {
   p.w_bytes = (int64_t)bytes.size();
   p.Npad = r.npad; p.Cout = r.cout; p.split_n = r.split_n; p.split_first = r.split_first;
   RON_HIP_CHECK(ron::dev_upload(&p.w, bytes.data(), bytes.size()));
-  if (dtype_is_half(c->cfg.dtype) && r.kh == 3 && r.kw == 3 && r.cin == 64 && r.npad == r.cout && r.cout % 64 == 0) {
+  if (conv_c64_wants_images(c->cfg.dtype, r.kh, r.kw, r.cin, r.cout, r.npad)) {
     const std::vector<uint8_t> img = pack_conv_c64_weights(r.w, r.npad, c->cfg.dtype);
     RON_HIP_CHECK(ron::dev_upload(&p.w_c64, img.data(), img.size()));
   }

@@ -4,7 +4,7 @@
 //   dx[n,i,j,ch] = round(dy[n,i/2,j/2,ch]) where (i, j) is the FIRST position of its window, in the order (0,0) (0,1) (1,0) (1,1),
 //                  whose xs equals the window's maximum; 0 everywhere else
 //
-// "First maximum" is TensorFlow's MaxPoolGrad on CPU and GPU (and torch-CPU's max_pool2d backward).  The running maximum starts at
+// "First maximum" (first_max_2x2, storage_device.h) is TensorFlow's MaxPoolGrad on CPU and GPU (and torch-CPU's max_pool2d backward).  The running maximum starts at
 // position (0,0) and a later position takes over only when it is GREATER (>), on the rounded values: two inputs that differ in fp32
 // and agree after rounding are a tie, and so are -0.0 and +0.0.  On an odd map the last window holds one row and / or one column:
 // positions that do not exist are neither read nor written.  A window that holds a NaN is outside the contract (the forward's fmaxf
@@ -18,16 +18,10 @@
 #include <algorithm>
 
 #include "conv_mfma.h"
+#include "storage_device.h"      // round_storage, first_max_2x2
 
 namespace ron {
 namespace {
-
-__device__ __forceinline__ float round_bf16_f(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return f;
-  return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
-}
-template <bool BF16> __device__ __forceinline__ float round_storage(float f) { return BF16 ? round_bf16_f(f) : (float)(_Float16)f; }
 
 RON_KERNEL_ARGS_BEGIN
 struct PoolBwdArgs {
@@ -64,14 +58,8 @@ __global__ __launch_bounds__(256) void maxpool2x2_backward_kernel(PoolBwdArgs a)
     float o[4][4];
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      float best = round_storage<BF16>(x00[e]);
-      int at = 0;
-      float v = round_storage<BF16>(x01[e]);
-      if (has_c && v > best) { best = v; at = 1; }
-      v = round_storage<BF16>(x10[e]);
-      if (has_r && v > best) { best = v; at = 2; }
-      v = round_storage<BF16>(x11[e]);
-      if (has_r && has_c && v > best) { best = v; at = 3; }
+      const int at = first_max_2x2(round_storage<BF16>(x00[e]), round_storage<BF16>(x01[e]), round_storage<BF16>(x10[e]),
+                                   round_storage<BF16>(x11[e]), has_c, has_r);
       const float grad = round_storage<BF16>(gy[e]);
 #pragma unroll
       for (int p = 0; p < 4; ++p) o[p][e] = at == p ? grad : 0.f;
@@ -97,7 +85,7 @@ extern "C" int ron_maxpool2x2_backward_nhwc(const float* x, const float* dy, int
   a.x = x; a.dy = dy; a.dx = dx;
   a.h = h; a.w = w; a.oh = (h + 1) / 2; a.ow = (w + 1) / 2; a.c = c;
   a.total = (long long)n * a.oh * a.ow * (c / 4);
-  const int grid = (int)std::max<long long>(1, std::min<long long>((a.total + 255) / 256, 256 * 16));
+  const int grid = grid_for(a.total);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == RON_DTYPE_BF16) RON_LAUNCH(maxpool2x2_backward_kernel<true>, dim3(grid), dim3(256), 0, s, a);
   else RON_LAUNCH(maxpool2x2_backward_kernel<false>, dim3(grid), dim3(256), 0, s, a);

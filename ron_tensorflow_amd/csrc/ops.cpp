@@ -1,6 +1,7 @@
 // Single-operator entry points (ron_conv2d_nhwc, ron_maxpool2x2_nhwc): the same kernels the
 // graph launches, wrapped with dense-fp32 <-> halo-tensor conversion so that the parity tests
 // can pin each kernel against the oracle.  They allocate scratch and synchronise: test/tool use.
+// conv_launch_geometry (conv_mfma.h) is here too: the launch geometry of a descriptor, which the training forward shares.
 #include <math.h>
 #include <stdio.h>
 #include <stdlib.h>
@@ -8,6 +9,27 @@
 #include <vector>
 
 #include "pack.h"
+
+void ron::conv_launch_geometry(const ron_conv_desc* d, ConvLaunch* c, int* ho, int* wo) {
+  c->dtype = d->dtype;
+  c->relu = d->relu;
+  if (d->transpose) {
+    *ho = d->h * d->stride; *wo = d->w * d->stride;
+    c->Cout = c->Npad = d->kh * d->kw * d->cout;
+    c->up = d->stride; c->up_cout = d->cout;
+    c->kh = c->kw = 1; c->stride = 1; c->dil = 1; c->cpad = 0;
+    c->Ho = d->h; c->Wo = d->w;
+    return;
+  }
+  const bool stem = d->cin == 3 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->dilation == 1;
+  *ho = d->h / d->stride; *wo = d->w / d->stride;
+  c->Cout = d->cout;
+  c->Npad = round_up(d->cout, conv_n_tile(d->cout));
+  c->kh = stem ? 1 : d->kh; c->kw = stem ? 1 : d->kw;
+  c->stride = d->stride; c->dil = d->dilation;
+  c->cpad = stem || d->stride != 1 ? 0 : (d->kh - 1) * d->dilation / 2;      // SAME
+  c->Ho = *ho; c->Wo = *wo;
+}
 
 namespace {
 
@@ -49,55 +71,39 @@ int setup_conv(const ron_conv_desc* d, const float* w, const float* bias, bool w
   const int chunk = conv_k_chunk(d->dtype);
   S->is_c3 = (!d->transpose && d->cin == 3 && d->kh == 3 && d->kw == 3 && d->stride == 1 && d->dilation == 1);
   RON_REQUIRE(S->is_c3 || d->cin % chunk == 0, "cin %d must be a multiple of %d (or the 3-channel 3x3 stem)", d->cin, chunk);
-  int cpad = 0;
   ConvLaunch& c = S->c;
-  c.dtype = d->dtype;
   c.cfg = d->tile_cfg;
-  std::vector<float> rows;
-  std::vector<float> bias_pad;
-  int cout_gemm;
   if (d->transpose) {
     RON_REQUIRE(d->kh == d->kw && d->kh == d->stride && d->dilation == 1, "transposed conv needs kernel == stride");
-    S->ho = d->h * d->stride; S->wo = d->w * d->stride;
-    cout_gemm = d->kh * d->kw * d->cout;
     RON_REQUIRE(d->cout % 128 == 0, "transposed conv: cout %d must be a multiple of 128", d->cout);
-    c.Npad = cout_gemm;
-    // TF layout [kh,kw,cout,cin] -> rows[(t*cout + co)][ci]
-    rows.assign((size_t)cout_gemm * d->cin, 0.f);
-    memcpy(rows.data(), w, rows.size() * sizeof(float));
-    bias_pad.assign(cout_gemm, 0.f);
-    if (bias) for (int t = 0; t < d->kh * d->kw; ++t) for (int co = 0; co < d->cout; ++co) bias_pad[t * d->cout + co] = bias[co];
-    c.up = d->stride; c.up_cout = d->cout;
-    c.kh = c.kw = 1; c.stride = 1; c.dil = 1; c.cpad = 0;
-    c.Ho = d->h; c.Wo = d->w;
   } else {
     RON_REQUIRE(d->stride == 1 || (d->h % d->stride == 0 && d->w % d->stride == 0 && d->kh == d->stride),
                 "strided conv: only kernel == stride on divisible maps");
-    cpad = d->stride == 1 ? ((d->kh - 1) * d->dilation) / 2 : 0;   // SAME
-    S->ho = d->h / d->stride; S->wo = d->w / d->stride;
-    cout_gemm = d->cout;
-    c.Npad = round_up(cout_gemm, conv_n_tile(cout_gemm));
+  }
+  conv_launch_geometry(d, &c, &S->ho, &S->wo);
+  const int cpad = c.cpad;
+  std::vector<float> rows;
+  std::vector<float> bias_pad(c.Npad, 0.f);
+  if (d->transpose) {
+    // TF layout [kh,kw,cout,cin] -> rows[(t*cout + co)][ci]
+    rows.assign((size_t)c.Npad * d->cin, 0.f);
+    memcpy(rows.data(), w, rows.size() * sizeof(float));
+    if (bias) for (int t = 0; t < d->kh * d->kw; ++t) for (int co = 0; co < d->cout; ++co) bias_pad[t * d->cout + co] = bias[co];
+  } else {
     if (S->is_c3) {
       rows.assign((size_t)c.Npad * chunk, 0.f);
       for (int k = 0; k < 27; ++k) for (int n = 0; n < d->cout; ++n) rows[(size_t)n * chunk + k] = w[(size_t)k * d->cout + n];
-      c.kh = c.kw = 1; c.cpad = 0;
     } else {
       hwio_to_rows(w, d->kh, d->kw, d->cin, d->cout, c.Npad, &rows);
-      c.kh = d->kh; c.kw = d->kw; c.cpad = cpad;
     }
-    bias_pad.assign(c.Npad, 0.f);
     if (bias) for (int n = 0; n < d->cout; ++n) bias_pad[n] = bias[n];
-    c.stride = d->stride; c.dil = d->dilation;
-    c.Ho = S->ho; c.Wo = S->wo;
   }
-  c.Cout = cout_gemm;
-  c.relu = d->relu;
   std::vector<uint8_t> wbytes = pack_conv_weights(rows, c.Npad, d->dtype, &c.oscale);
   int rc;
   RON_HIP_CHECK(dev_upload(&S->d_w, wbytes.data(), wbytes.size()));
   RON_HIP_CHECK(dev_upload(&S->d_b, bias_pad.data(), bias_pad.size() * 4));
   c.wgt = S->d_w.p; c.wgt_bytes = (int64_t)wbytes.size(); c.bias = (const float*)S->d_b.p;
-  if (!d->transpose && !S->is_c3 && dtype_is_half(d->dtype) && d->kh == 3 && d->kw == 3 && d->cin == 64 && c.Npad == d->cout && d->cout % 64 == 0) {
+  if (conv_c64_wants_images(d->dtype, d->kh, d->kw, d->cin, d->cout, c.Npad)) {      // (no transposed convolution: Npad = 9 cout there)
     // what ron_finalize_weights adds for such a layer: the weights once more as LDS images for the resident-weight kernel
     const std::vector<uint8_t> img = pack_conv_c64_weights(rows, c.Npad, d->dtype);
     RON_HIP_CHECK(dev_upload(&S->d_w_c64, img.data(), img.size()));

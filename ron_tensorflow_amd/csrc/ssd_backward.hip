@@ -27,16 +27,10 @@
 #include <algorithm>
 
 #include "conv_mfma.h"
+#include "storage_device.h"      // round_storage
 
 namespace ron {
 namespace {
-
-__device__ __forceinline__ float ssd_round_bf16(float f) {
-  const unsigned u = __float_as_uint(f);
-  if ((u & 0x7FFFFFFFu) > 0x7F800000u) return f;
-  return __uint_as_float((u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u);
-}
-template <bool BF16> __device__ __forceinline__ float ssd_round(float f) { return BF16 ? ssd_round_bf16(f) : (float)(_Float16)f; }
 
 // n h w c elements of 4 bytes inside 2^62 bytes (the kernels index with 64-bit integers)
 bool elems_fit(int n, int h, int w, int c, int64_t* pixels) {
@@ -86,7 +80,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s1_backward_kernel(Pool3Args a)
 #pragma unroll
     for (int q = 0; q < 5; ++q)
 #pragma unroll
-      for (int e = 0; e < 4; ++e) own[q][e] = ssd_round<BF16>(nb[2][q][e]);
+      for (int e = 0; e < 4; ++e) own[q][e] = round_storage<BF16>(nb[2][q][e]);
     // cm[r][k]: the maximum of row r over the in-bounds columns of the windows at ox = j - 1 + k (columns k .. k + 2; k + 1 exists
     // whenever the window does)
     float cm[5][3][4];
@@ -99,7 +93,7 @@ __global__ __launch_bounds__(256) void maxpool3x3s1_backward_kernel(Pool3Args a)
           float m = nb[r][k + 1][e];
           if (cv[k]) m = fmaxf(m, nb[r][k][e]);
           if (cv[k + 2]) m = fmaxf(m, nb[r][k + 2][e]);
-          cm[r][k][e] = ssd_round<BF16>(m);
+          cm[r][k][e] = round_storage<BF16>(m);
         }
     float sum[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -123,10 +117,10 @@ __global__ __launch_bounds__(256) void maxpool3x3s1_backward_kernel(Pool3Args a)
             if (q < 2) sel = sel && (!cv[q] || own[q][e] < me);
             if (q > 2) sel = sel && (!cv[q] || own[q][e] <= me);
           }
-          sum[e] += sel ? ssd_round<BF16>(gy[e]) : 0.f;
+          sum[e] += sel ? round_storage<BF16>(gy[e]) : 0.f;
         }
       }
-    *reinterpret_cast<float4*>(a.dx + at) = make_float4(ssd_round<BF16>(sum[0]), ssd_round<BF16>(sum[1]), ssd_round<BF16>(sum[2]), ssd_round<BF16>(sum[3]));
+    *reinterpret_cast<float4*>(a.dx + at) = make_float4(round_storage<BF16>(sum[0]), round_storage<BF16>(sum[1]), round_storage<BF16>(sum[2]), round_storage<BF16>(sum[3]));
   }
 }
 
@@ -174,8 +168,8 @@ __global__ __launch_bounds__(256) void l2norm_backward_kernel(L2Args a) {
         vx = *reinterpret_cast<const float4*>(a.x + base + c0);
         vd = *reinterpret_cast<const float4*>(a.dy + base + c0);
       }
-      xs[k][0] = ssd_round<BF16>(vx.x); xs[k][1] = ssd_round<BF16>(vx.y); xs[k][2] = ssd_round<BF16>(vx.z); xs[k][3] = ssd_round<BF16>(vx.w);
-      dz[k][0] = ssd_round<BF16>(vd.x); dz[k][1] = ssd_round<BF16>(vd.y); dz[k][2] = ssd_round<BF16>(vd.z); dz[k][3] = ssd_round<BF16>(vd.w);
+      xs[k][0] = round_storage<BF16>(vx.x); xs[k][1] = round_storage<BF16>(vx.y); xs[k][2] = round_storage<BF16>(vx.z); xs[k][3] = round_storage<BF16>(vx.w);
+      dz[k][0] = round_storage<BF16>(vd.x); dz[k][1] = round_storage<BF16>(vd.y); dz[k][2] = round_storage<BF16>(vd.z); dz[k][3] = round_storage<BF16>(vd.w);
 #pragma unroll
       for (int e = 0; e < 4; ++e) ss += xs[k][e] * xs[k][e];
     }
@@ -203,7 +197,7 @@ __global__ __launch_bounds__(256) void l2norm_backward_kernel(L2Args a) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
           const float g = dz[k][e] * gm[k][e];
-          o[e] = ssd_round<BF16>(live ? inv * (g - xs[k][e] * t) : inv * g);
+          o[e] = round_storage<BF16>(live ? inv * (g - xs[k][e] * t) : inv * g);
         }
         *reinterpret_cast<float4*>(a.dx + base + c0) = make_float4(o[0], o[1], o[2], o[3]);
       }
@@ -286,7 +280,7 @@ extern "C" int ron_maxpool3x3s1_backward_nhwc(const float* x, const float* dy, i
   a.x = x; a.dy = dy; a.dx = dx;
   a.h = h; a.w = w; a.c = c;
   a.total = pixels * (c / 4);
-  const int grid = (int)std::max<long long>(1, std::min<long long>((a.total + 255) / 256, 256 * 16));
+  const int grid = grid_for(a.total);
   hipStream_t s = (hipStream_t)stream;
   if (dtype == RON_DTYPE_BF16) RON_LAUNCH(maxpool3x3s1_backward_kernel<true>, dim3(grid), dim3(256), 0, s, a);
   else RON_LAUNCH(maxpool3x3s1_backward_kernel<false>, dim3(grid), dim3(256), 0, s, a);
@@ -310,9 +304,7 @@ extern "C" int ron_l2norm_backward_nhwc(const float* x, const float* gamma, cons
   RON_REQUIRE(x != nullptr && gamma != nullptr && dy != nullptr, "l2norm backward: NULL tensor (x, gamma and dy are always read)");
   RON_REQUIRE((((uintptr_t)x | (uintptr_t)gamma | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)dgamma) & 15) == 0,
               "l2norm backward: x, gamma, dy, dx and dgamma must be 16-byte aligned (16 bytes per access)");
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= need, "l2norm backward: workspace of %lld bytes, %lld needed (ron_l2norm_backward_workspace_bytes)",
-              (long long)workspace_bytes, (long long)need);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "l2norm backward: the workspace must be 256-byte aligned");
+  if (int rc = check_workspace("l2norm backward", "ron_l2norm_backward_workspace_bytes", workspace, workspace_bytes, need)) return rc;
   if (dx == nullptr && dgamma == nullptr) return RON_OK;
   L2Args a = L2Args();
   a.x = x; a.gamma = gamma; a.dy = dy; a.dx = dx;

@@ -12,7 +12,7 @@
 // four waves owns every S-th of the 32-pixel K steps (workgroup s: steps s, s + S, ...), so that at any time the S workgroups read
 // one contiguous stretch of dy and y (contiguous slices of steps, 2 S streams far apart: 504 against 483 us at batch 32, measured
 // together with the unrolled loop of the reduce kernel).  Per step:
-//   * dy (and y) 16 bytes per lane, two pixel rows per lane; masked, rounded, written as a [32 pixels][64 channels] image of the
+//   * dy (and y) 16 bytes per lane, two pixel rows per lane; masked, rounded (round_pair, storage_device.h), written as a [32 pixels][64 channels] image of the
 //     storage type; the rounded values are added to the lane's four dbias partials (fixed order: the lane's rows, step by step);
 //   * the x operand [32 pixels][32 k] is gathered 4 k per lane with a bounds test PER PIXEL (a step may straddle rows and images):
 //     taps outside the image, k >= 27 and pixels behind the last one are staged as zeros, as the forward's patch staging does;
@@ -36,12 +36,10 @@
 #include <algorithm>
 
 #include "conv_mfma.h"
-#include "wgrad_device.h"
+#include "storage_device.h"      // round_pair, bits_to_f, the MFMA and its transposed operand read (shared with conv_wgrad.hip)
 
 namespace ron {
 namespace {
-
-using namespace wgrad;
 
 constexpr int kStep = 32;                           // pixels per K step
 constexpr int kCout = 64, kRows = 27;               // dw as a matrix: [27][64]
@@ -54,17 +52,6 @@ constexpr int kReduceGroups = 16;
 // the kernel holds pixel indices, rounded up to the step, in 32-bit signed integers
 constexpr int64_t kMaxPixels = RON_STEM_BACKWARD_MAX_PIXELS;
 static_assert(kMaxPixels + kStep - 1 <= 0x7FFFFFFFLL, "a pixel index of the last step must fit an int");
-
-// two values rounded to the storage type (nearest even) and packed; bf16 through the hardware conversion (v_cvt_pk_bf16_f32) - the
-// integer rounding of wgrad_device.h costs six instructions a value, and this kernel's vector work per byte is what bounds it
-template <bool BF16> __device__ __forceinline__ unsigned round_pair(float lo, float hi) {
-  if (BF16) {
-    typedef __bf16 v2bf16 __attribute__((ext_vector_type(2)));
-    typedef float v2f32 __attribute__((ext_vector_type(2)));
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v2f32{lo, hi}, v2bf16));
-  }
-  return round_f16_bits(lo) | ((unsigned)round_f16_bits(hi) << 16);
-}
 
 __device__ __forceinline__ int z_off(int row, int blk) { return 128 * row + 32 * (blk ^ (((row >> 1) & 1) | (((row >> 3) & 1) << 1))); }
 __device__ __forceinline__ int x_off(int row, int blk) { return 64 * row + 32 * (blk ^ ((row >> 3) & 1)); }
@@ -295,9 +282,7 @@ extern "C" int ron_conv2d_stem_backward_nhwc(const ron_conv_desc* d, const float
   RON_REQUIRE(dy != nullptr, "%s: dy is NULL", what);
   RON_REQUIRE(!d->relu || y != nullptr, "%s: relu is set and y is NULL (the mask is y > 0)", what);
   RON_REQUIRE(dw == nullptr || x != nullptr, "%s: dw needs x", what);
-  RON_REQUIRE(workspace != nullptr && workspace_bytes >= P.total, "%s: workspace of %lld bytes, %lld needed (ron_conv2d_stem_backward_workspace_bytes)",
-              what, (long long)workspace_bytes, (long long)P.total);
-  RON_REQUIRE(((uintptr_t)workspace & 255) == 0, "%s: the workspace must be 256-byte aligned", what);
+  if (int rc = check_workspace(what, "ron_conv2d_stem_backward_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
   RON_REQUIRE((((uintptr_t)y | (uintptr_t)dy) & 15) == 0, "%s: y and dy must be 16-byte aligned (they are read 16 bytes at a time)", what);
   RON_REQUIRE(((uintptr_t)x & 3) == 0, "%s: x must be 4-byte aligned", what);
   if (dw == nullptr && dbias == nullptr) return RON_OK;
