@@ -778,8 +778,8 @@ int ron_conv2d_forward_parts_nhwc(const ron_conv_desc* d, const float* x, const 
  * The workspace is 64-bit sized; each tensor inside it stays below 2 GiB (a larger one is refused).
  * ron_conv_chain_workspace_bytes is host arithmetic only; -1 + ron_last_error() on a descriptor the calls would refuse.
  * ron_conv_chain_shape: the output shape of `layer`.
- * Out of scope: the stem; the 3x3 stride-1 pool, the L2 normalisation and batch normalisation; the 2x2 stride-2
- * convolutions; fp32 and f16x3 arithmetic; taps on pool layers.
+ * Out of scope: the stem; the 3x3 stride-1 pool and the L2 normalisation; the 2x2 stride-2 convolutions; fp32 and f16x3
+ * arithmetic; taps on pool layers.  Batch normalisation and the two-branch convolution: ron_head_chain_* below.
  * ---------------------------------------------------------------------------------------- */
 enum { RON_CHAIN_CONV = 0, RON_CHAIN_POOL2 = 1 };
 #define RON_CHAIN_MAX_LAYERS 32
@@ -801,6 +801,85 @@ int ron_conv_chain_forward(const ron_chain_desc* d, const float* x, const float*
 int ron_conv_chain_backward(const ron_chain_desc* d, const float* dy, const float* const* dtaps, const float* const* w,
                             float* dx, float* const* dw, float* const* dbias, void* workspace, int64_t workspace_bytes,
                             void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * Head chain: the convolution chain with two more layer kinds - training-mode batch normalisation and the two-branch
+ * 3x3 | 1x1 convolution of pred_cls_module - so that every branch of a reverse_connection_module_with_pred
+ * (nets/ron_vgg_320.py:378-432) is one chain: `_conv_left` (conv, BN), `_objectness` + `_objectness_score` (conv, BN, conv),
+ * pred_cls_module (pair, BN, pair, BN, conv), reg_bbox_module (conv, BN, conv).  One planner and one runner serve both
+ * families: ron_conv_chain_* is the case "no BN, no pair" of these entry points, with the same launches.  Everything the
+ * convolution chain's contract says holds here (stream-ordered, no allocation, no synchronisation, dry run, refusals before
+ * any HIP call, nothing assumed about the workspace's contents, the backward repeatable); RON_CHAIN_CONV and RON_CHAIN_POOL2
+ * layers are the same.
+ *
+ *   RON_CHAIN_BN         batch normalisation of the previous layer's stored output with batch statistics over M = n h w, then
+ *                        ReLU when `relu`: the contract of ron_batchnorm_train_nhwc / ron_batchnorm_backward_nhwc (its
+ *                        geometry, shifted sums, Chan merges and fixed tree for this (M, c); rstd recomputed in the backward),
+ *                        read and written as storage-type halo tensors.  The input already holds storage-type values, so
+ *                        round(x) is the identity.  eps finite and >= 0, decay in [0, 1]; M at most 2^24.  moving_mean /
+ *                        moving_var (both or neither) are updated in place by the forward.  mean and var stay in the workspace
+ *                        for the backward and are also written to mean / var when those are not NULL.  May be the first layer,
+ *                        the last one, follow a pool or another BN.  k, dilation, cout, cout2, has_bias are ignored.
+ *   RON_CHAIN_CONV_PAIR  concat(conv3x3(x, w, bias), conv1x1(x, w2, bias2)) along the channels: cout channels of the 3x3
+ *                        branch, then cout2 of the 1x1; both multiples of 64; relu and has_bias apply to both; k and dilation
+ *                        are ignored.  Each branch runs the launches ron_conv2d_forward_nhwc / ron_conv2d_backward_nhwc make
+ *                        for it on its own and writes its channel slice of one tensor.  The gradient of the pair's input is
+ *                        float(dx of the 3x3) + float(dx of the 1x1) in fp32 - two terms, so the order does not matter -
+ *                        which then enters the previous layer's mask and single rounding, or leaves as dx unrounded.
+ * A chain that starts with a convolution or a pair needs cin a multiple of 64, as the convolution chain does; one that starts
+ * with a batch normalisation or a pool a multiple of 8 (a convolution further on still asks for its 64).
+ * Taps: convolution layers only.  A tap on a BN or pair layer is refused (not built), and so is a pair directly behind a
+ * tapped layer (that gradient would be a sum of three terms whose order autograd does not fix).
+ *
+ * Bytes: y, taps, mean, var, the moving statistics, dx and every parameter gradient are those of the per-operator entry points
+ * chained through fp32 (the pair: the two convolutions and a concatenation; BN: ron_batchnorm_*), for any input.
+ *
+ * Pointers travel as a HOST array of num_layers ron_head_chain_ptrs, one per layer; members a layer's kind does not use are
+ * ignored.  The forward reads w, bias, w2, bias2, gamma, beta, updates moving_mean / moving_var and writes mean, var, tap;
+ * the backward reads w, w2, gamma, dtap and writes dw, dbias, dw2, dbias2, dgamma, dbeta (each may be NULL: not computed; layers
+ * in front of the first requested gradient do not run).  x, y, dy, dx, tap, dtap and every BN vector must be 16-byte
+ * aligned, weights, biases and their gradients 4-byte, the workspace 256-byte.
+ * ---------------------------------------------------------------------------------------- */
+enum { RON_CHAIN_BN = 2, RON_CHAIN_CONV_PAIR = 3 };
+typedef struct {
+  int32_t kind;             /* RON_CHAIN_CONV / RON_CHAIN_POOL2 / RON_CHAIN_BN / RON_CHAIN_CONV_PAIR */
+  int32_t k, dilation, cout, relu, has_bias;
+  int32_t tap;
+  int32_t cout2;            /* RON_CHAIN_CONV_PAIR: channels of the 1x1 branch */
+  float eps, decay;         /* RON_CHAIN_BN */
+} ron_head_chain_layer;
+typedef struct {
+  int32_t n, h, w, cin;
+  int32_t dtype;            /* ron_dtype: bf16 or fp16 */
+  int32_t num_layers;
+  ron_head_chain_layer layers[RON_CHAIN_MAX_LAYERS];
+} ron_head_chain_desc;
+typedef struct {
+  const float* w;           /* conv, pair (3x3 branch): HWIO */
+  const float* bias;
+  const float* w2;          /* pair: the 1x1 branch [1,1,cin,cout2] */
+  const float* bias2;
+  const float* gamma;       /* BN [c] */
+  const float* beta;
+  float* moving_mean;       /* BN [c], updated in place by the forward; both or neither */
+  float* moving_var;
+  float* mean;              /* out, forward: BN batch statistics [c] (NULL: kept in the workspace only) */
+  float* var;
+  float* tap;               /* out, forward: a tapped convolution's output */
+  const float* dtap;        /* in, backward: its gradient (NULL: none) */
+  float* dw;                /* out, backward */
+  float* dbias;
+  float* dw2;
+  float* dbias2;
+  float* dgamma;
+  float* dbeta;
+} ron_head_chain_ptrs;
+int ron_head_chain_shape(const ron_head_chain_desc* d, int layer, int64_t nhwc[4]);
+int64_t ron_head_chain_workspace_bytes(const ron_head_chain_desc* d);
+int ron_head_chain_forward(const ron_head_chain_desc* d, const float* x, const ron_head_chain_ptrs* p, float* y, void* workspace,
+                           int64_t workspace_bytes, void* stream);
+int ron_head_chain_backward(const ron_head_chain_desc* d, const float* dy, const ron_head_chain_ptrs* p, float* dx, void* workspace,
+                            int64_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Backward of the 3-channel stem convolution conv1_1 (3 -> 64 channels, 3x3, stride 1, SAME): its weight and bias

@@ -129,6 +129,29 @@ class ChainDesc(C.Structure):
                 ('num_layers', C.c_int32), ('layers', ChainLayer * RON_CHAIN_MAX_LAYERS)]
 
 
+RON_CHAIN_BN = 2
+RON_CHAIN_CONV_PAIR = 3
+
+
+class HeadChainLayer(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('k', C.c_int32), ('dilation', C.c_int32), ('cout', C.c_int32), ('relu', C.c_int32),
+                ('has_bias', C.c_int32), ('tap', C.c_int32), ('cout2', C.c_int32), ('eps', C.c_float), ('decay', C.c_float)]
+
+
+class HeadChainDesc(C.Structure):
+    _fields_ = [('n', C.c_int32), ('h', C.c_int32), ('w', C.c_int32), ('cin', C.c_int32), ('dtype', C.c_int32),
+                ('num_layers', C.c_int32), ('layers', HeadChainLayer * RON_CHAIN_MAX_LAYERS)]
+
+
+# one per layer (ron_head_chain_ptrs): in, forward out, backward in, backward out
+HEAD_CHAIN_PTRS = ('w', 'bias', 'w2', 'bias2', 'gamma', 'beta', 'moving_mean', 'moving_var', 'mean', 'var', 'tap', 'dtap',
+                   'dw', 'dbias', 'dw2', 'dbias2', 'dgamma', 'dbeta')
+
+
+class HeadChainPtrs(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in HEAD_CHAIN_PTRS]
+
+
 OPT_RULES = {'sgd': 0, 'momentum': 1, 'rmsprop': 2, 'adam': 3}
 
 
@@ -230,6 +253,10 @@ SIGNATURES = {
     'ron_conv_chain_forward': (C.c_int, [C.POINTER(ChainDesc), _P, C.POINTER(_P), C.POINTER(_P), C.POINTER(_P), _P, _P, C.c_int64, _P]),
     'ron_conv_chain_backward': (C.c_int, [C.POINTER(ChainDesc), _P, C.POINTER(_P), C.POINTER(_P), _P, C.POINTER(_P), C.POINTER(_P), _P,
                                           C.c_int64, _P]),
+    'ron_head_chain_shape': (C.c_int, [C.POINTER(HeadChainDesc), C.c_int, C.POINTER(C.c_int64)]),
+    'ron_head_chain_workspace_bytes': (C.c_int64, [C.POINTER(HeadChainDesc)]),
+    'ron_head_chain_forward': (C.c_int, [C.POINTER(HeadChainDesc), _P, C.POINTER(HeadChainPtrs), _P, _P, C.c_int64, _P]),
+    'ron_head_chain_backward': (C.c_int, [C.POINTER(HeadChainDesc), _P, C.POINTER(HeadChainPtrs), _P, _P, C.c_int64, _P]),
     'ron_conv2d_stem_backward_workspace_bytes': (C.c_int64, [C.POINTER(ConvDesc)]),
     'ron_conv2d_stem_backward_nhwc': (C.c_int, [C.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
     'ron_maxpool2x2_backward_nhwc': (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),

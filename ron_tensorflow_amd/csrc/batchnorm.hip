@@ -20,13 +20,18 @@
 // merged with Chan's formula behind a fixed binary tree (lane i with lane i + stride, the stride halving).  All counts follow
 // from the shape, so the same inputs give the same bytes; with M and hence every count a power of two each merge joins equal counts
 // and small-integer inputs come out exact.  The gradient sums take the same route with plain additions.  No atomics anywhere.
+//
+// Every kernel that touches a [M][c] tensor takes its PLACE as a template parameter (DensePlace: the entry points' fp32 dense tensors;
+// HaloPlace: a storage-type halo view of the head chain, batchnorm.h / conv_chain.hip).  The geometry, the lane that owns a value and
+// the order of every sum do not depend on the place, so the chain's statistics and gradient sums have the operators' bytes.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 
+#include "batchnorm.h"
 #include "common.h"
-#include "storage_device.h"      // round_storage
+#include "storage_device.h"      // round_storage, bits_to_f, round_bits, halo_off
 
 namespace ron {
 namespace {
@@ -60,6 +65,51 @@ __device__ __forceinline__ void load4(const float* p, float* o) {
 }
 __device__ __forceinline__ void store4(float* p, const float* o) { *reinterpret_cast<float4*>(p) = make_float4(o[0], o[1], o[2], o[3]); }
 
+// ---- the place of a [rows][c] tensor: where row r, channels ch .. ch + 3 of the walk lie ------------------------------------------------
+// DensePlace: fp32 dense NHWC, the operators' boundary (one 16-byte access).  HaloPlace: a storage-type halo tensor of the chain
+// (conv_chain.hip), possibly a channel slice of a wider one: row r of the dense walk is pixel (img, y, x) = halo_off, so every lane
+// meets the same values in the same order as in the dense walk and the sums have the same bytes.  4 channels are 8 bytes there; the
+// lanes of a row are adjacent, so a wave still reads or writes whole 128-byte pieces of a pixel's channels.
+RON_KERNEL_ARGS_BEGIN
+struct DensePlace {
+  float* p;
+};
+RON_KERNEL_ARGS_END(DensePlace)
+RON_KERNEL_ARGS_BEGIN
+struct HaloPlace {
+  unsigned short* p;        // halo pixel 0, channel 0 of the allocation
+  int H, W, pad, cs, coff;  // the map, its halo, elements per pixel, first channel of the slice
+  int fill_ = 0;
+};
+RON_KERNEL_ARGS_END(HaloPlace)
+
+__device__ __forceinline__ long long place_off(const DensePlace&, const BnGeom& g, long long row, long long ch) { return row * g.c + ch; }
+__device__ __forceinline__ long long place_off(const HaloPlace& t, const BnGeom&, long long row, long long ch) {
+  // (rows <= 2^24: 32-bit divisions)
+  const unsigned r = (unsigned)row, hw = (unsigned)(t.H * t.W);
+  const unsigned img = r / hw, rem = r - img * hw;
+  const unsigned y = rem / (unsigned)t.W, x = rem - y * (unsigned)t.W;
+  return halo_off(img, (int)y, (int)x, t.H, t.W, t.pad, t.cs) + t.coff + ch;
+}
+template <bool BF16> __device__ __forceinline__ void place_load(const DensePlace& t, const BnGeom& g, long long row, long long ch, float* o) {
+  load4(t.p + place_off(t, g, row, ch), o);
+}
+template <bool BF16> __device__ __forceinline__ void place_load(const HaloPlace& t, const BnGeom& g, long long row, long long ch, float* o) {
+  const uint2 v = *reinterpret_cast<const uint2*>(t.p + place_off(t, g, row, ch));
+  o[0] = bits_to_f<BF16>((unsigned short)(v.x & 0xFFFFu)); o[1] = bits_to_f<BF16>((unsigned short)(v.x >> 16));
+  o[2] = bits_to_f<BF16>((unsigned short)(v.y & 0xFFFFu)); o[3] = bits_to_f<BF16>((unsigned short)(v.y >> 16));
+}
+// o holds storage-type values (every caller rounds first): the halo place stores their bits
+template <bool BF16> __device__ __forceinline__ void place_store(const DensePlace& t, const BnGeom& g, long long row, long long ch, const float* o) {
+  store4(t.p + place_off(t, g, row, ch), o);
+}
+template <bool BF16> __device__ __forceinline__ void place_store(const HaloPlace& t, const BnGeom& g, long long row, long long ch, const float* o) {
+  uint2 v;
+  v.x = round_bits<BF16>(o[0]) | ((unsigned)round_bits<BF16>(o[1]) << 16);
+  v.y = round_bits<BF16>(o[2]) | ((unsigned)round_bits<BF16>(o[3]) << 16);
+  *reinterpret_cast<uint2*>(t.p + place_off(t, g, row, ch)) = v;
+}
+
 // Chan's merge of (nb, mb, Mb) into (na, ma, Ma); an empty side changes nothing, equal counts give f = 1/2 exactly
 __device__ __forceinline__ void chan_merge(float& na, float* ma, float* Ma, float nb, const float* mb, const float* Mb) {
   if (nb == 0.f) return;
@@ -86,8 +136,8 @@ __device__ __forceinline__ long long slice_count(const BnGeom& g, long long s) {
 }
 
 // ---- forward, pass 1: per slice (mean, M2) of every channel -> part [slices][2][c] ---------------------------------------------------
-template <bool BF16>
-__global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(BnGeom g, const float* __restrict__ x, float* __restrict__ part) {
+template <bool BF16, class PL>
+__global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(BnGeom g, PL x, float* __restrict__ part) {
   __shared__ float sh_n[kBnThreads];
   __shared__ Stat4 sh_mean[kBnThreads], sh_m2[kBnThreads];
   const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
@@ -96,17 +146,16 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_kernel(BnGeom g, const fl
   const long long r0 = (long long)blockIdx.x * g.slice_rows, cnt = slice_count(g, blockIdx.x);
   float n = 0.f, mean[4] = {0.f, 0.f, 0.f, 0.f}, m2[4] = {0.f, 0.f, 0.f, 0.f};
   if (active && rl < cnt) {
-    const float* p = x + (r0 + rl) * g.c + (long long)cgi * 4;
-    const long long step = (long long)g.rpb * g.c;
+    const long long row = r0 + rl, ch = (long long)cgi * 4;
     const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
     float k[4], s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
-    load4(p, k);
+    place_load<BF16>(x, g, row, ch, k);
 #pragma unroll
     for (int e = 0; e < 4; ++e) k[e] = round_storage<BF16>(k[e]);
 #pragma unroll 4
     for (int i = 1; i < mine; ++i) {
       float v[4];
-      load4(p + i * step, v);
+      place_load<BF16>(x, g, row + (long long)i * g.rpb, ch, v);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float d = round_storage<BF16>(v[e]) - k[e];
@@ -203,11 +252,21 @@ __global__ __launch_bounds__(kBnThreads) void bn_stats_final_kernel(BnGeom g, co
   }
 }
 
+// the chain keeps mean and var in its workspace and delivers them too: [c] floats each, 4 per lane
+__global__ __launch_bounds__(kBnThreads) void bn_copy_stats_kernel(int groups, const float* __restrict__ mean, const float* __restrict__ var,
+                                                                   float* mean_out, float* var_out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= groups) return;
+  float v[4];
+  if (mean_out != nullptr) { load4(mean + 4 * i, v); store4(mean_out + 4 * i, v); }
+  if (var_out != nullptr) { load4(var + 4 * i, v); store4(var_out + 4 * i, v); }
+}
+
 // ---- forward, pass 3: y = round(act(gamma (xs - mean) rstd + beta)) -------------------------------------------------------------------
-template <bool BF16, bool RELU>
-__global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ gamma,
+template <bool BF16, bool RELU, class PL>
+__global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, PL x, const float* __restrict__ gamma,
                                                               const float* __restrict__ beta, const float* __restrict__ mean,
-                                                              const float* __restrict__ var, float eps, float* __restrict__ y) {
+                                                              const float* __restrict__ var, float eps, PL y) {
   const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
   const int cgi = blockIdx.y * g.lpr + gl;
   const long long cnt = slice_count(g, blockIdx.x);
@@ -220,12 +279,13 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, const fl
   load4(var + ch, rstd);
 #pragma unroll
   for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(rstd[e] + eps);
-  const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+  const long long row0 = (long long)blockIdx.x * g.slice_rows + rl;
   const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
 #pragma unroll 4
   for (int i = 0; i < mine; ++i) {
+    const long long row = row0 + (long long)i * g.rpb;
     float v[4], o[4];
-    load4(x + base + i * step, v);
+    place_load<BF16>(x, g, row, ch, v);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float xhat = (round_storage<BF16>(v[e]) - mu[e]) * rstd[e];
@@ -233,14 +293,13 @@ __global__ __launch_bounds__(kBnThreads) void bn_apply_kernel(BnGeom g, const fl
       if (RELU) t = t > 0.f ? t : (t == t ? 0.f : t);          // NaN stays NaN
       o[e] = round_storage<BF16>(t);
     }
-    store4(y + base + i * step, o);
+    place_store<BF16>(y, g, row, ch, o);
   }
 }
 
 // ---- backward, pass 1: per slice sum(dz) and sum(dz xhat) -> part [slices][2][c] -------------------------------------------------------
-template <bool BF16, bool RELU>
-__global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ y,
-                                                                 const float* __restrict__ dy, const float* __restrict__ mean,
+template <bool BF16, bool RELU, class PL>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_kernel(BnGeom g, PL x, PL y, PL dy, const float* __restrict__ mean,
                                                                  const float* __restrict__ var, float eps, float* __restrict__ part) {
   __shared__ Stat4 sh_b[kBnThreads], sh_g[kBnThreads];
   const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
@@ -255,14 +314,15 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_sums_kernel(BnGeom g, const
     load4(var + ch, rstd);
 #pragma unroll
     for (int e = 0; e < 4; ++e) rstd[e] = 1.f / sqrtf(rstd[e] + eps);
-    const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+    const long long row0 = (long long)blockIdx.x * g.slice_rows + rl;
     const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
 #pragma unroll 4
     for (int i = 0; i < mine; ++i) {
+      const long long row = row0 + (long long)i * g.rpb;
       float v[4], d[4], m[4] = {1.f, 1.f, 1.f, 1.f};
-      load4(x + base + i * step, v);
-      load4(dy + base + i * step, d);
-      if (RELU) load4(y + base + i * step, m);
+      place_load<BF16>(x, g, row, ch, v);
+      place_load<BF16>(dy, g, row, ch, d);
+      if (RELU) place_load<BF16>(y, g, row, ch, m);
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         const float dz = round_storage<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
@@ -341,11 +401,10 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_final_kernel(BnGeom g, cons
 }
 
 // ---- backward, pass 3: dx = round(gamma rstd (dz - dbeta / M - xhat dgamma / M)) -------------------------------------------------------
-template <bool BF16, bool RELU>
-__global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(BnGeom g, const float* __restrict__ x, const float* __restrict__ y,
-                                                               const float* __restrict__ dy, const float* __restrict__ gamma,
+template <bool BF16, bool RELU, class PL>
+__global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(BnGeom g, PL x, PL y, PL dy, const float* __restrict__ gamma,
                                                                const float* __restrict__ mean, const float* __restrict__ var, float eps,
-                                                               const float* __restrict__ fin, float* __restrict__ dx) {
+                                                               const float* __restrict__ fin, PL dx) {
   const int tid = threadIdx.x, gl = tid & (g.lpr - 1), rl = tid >> g.lpr_log2;
   const int cgi = blockIdx.y * g.lpr + gl;
   const long long cnt = slice_count(g, blockIdx.x);
@@ -365,21 +424,22 @@ __global__ __launch_bounds__(kBnThreads) void bn_bwd_dx_kernel(BnGeom g, const f
     mb[e] = mb[e] / rows;
     mg[e] = mg[e] / rows;
   }
-  const long long base = ((long long)blockIdx.x * g.slice_rows + rl) * g.c + ch, step = (long long)g.rpb * g.c;
+  const long long row0 = (long long)blockIdx.x * g.slice_rows + rl;
   const int mine = (int)((cnt - rl + g.rpb - 1) / g.rpb);
 #pragma unroll 4
   for (int i = 0; i < mine; ++i) {
+    const long long row = row0 + (long long)i * g.rpb;
     float v[4], d[4], m[4] = {1.f, 1.f, 1.f, 1.f}, o[4];
-    load4(x + base + i * step, v);
-    load4(dy + base + i * step, d);
-    if (RELU) load4(y + base + i * step, m);
+    place_load<BF16>(x, g, row, ch, v);
+    place_load<BF16>(dy, g, row, ch, d);
+    if (RELU) place_load<BF16>(y, g, row, ch, m);
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       const float dz = round_storage<BF16>(RELU ? (m[e] > 0.f ? d[e] : 0.f) : d[e]);
       const float xhat = (round_storage<BF16>(v[e]) - mu[e]) * rstd[e];
       o[e] = round_storage<BF16>(scale[e] * ((dz - mb[e]) - xhat * mg[e]));
     }
-    store4(dx + base + i * step, o);
+    place_store<BF16>(dx, g, row, ch, o);
   }
 }
 
@@ -417,9 +477,11 @@ int plan_bn(const char* what, const ron_bn_desc* d, BnPlan* P) {
   return RON_OK;
 }
 
-template <bool BF16, bool RELU>
-int run_forward(const ron_bn_desc* d, const BnPlan& P, const float* x, const float* gamma, const float* beta, float* y, float* mean,
-                float* var, float* moving_mean, float* moving_var, char* ws, hipStream_t s) {
+
+template <bool BF16, bool RELU, class PL>
+int run_forward(const ron_bn_desc* d, const BnPlan& P, PL x, const float* gamma, const float* beta, PL y, float* mean, float* var,
+                float* moving_mean, float* moving_var, char* ws, hipStream_t s) {
+  // (the kernels are spelled as the operators' launch trace has them since before the place: PL is deduced from the arguments)
   const BnGeom& g = P;
   float* part = reinterpret_cast<float*>(ws + P.off_part);
   const dim3 grid(P.slices, P.tiles);
@@ -430,21 +492,69 @@ int run_forward(const ron_bn_desc* d, const BnPlan& P, const float* x, const flo
   return RON_OK;
 }
 
-template <bool BF16, bool RELU>
-int run_backward(const ron_bn_desc* d, const BnPlan& P, const float* x, const float* y, const float* dy, const float* gamma,
-                 const float* mean, const float* var, float* dx, float* dgamma, float* dbeta, char* ws, hipStream_t s) {
+template <bool BF16, bool RELU, class PL>
+int run_backward(const ron_bn_desc* d, const BnPlan& P, PL x, PL y, PL dy, const float* gamma, const float* mean, const float* var,
+                 bool want_dx, PL dx, float* dgamma, float* dbeta, char* ws, hipStream_t s) {
   const BnGeom& g = P;
   float* part = reinterpret_cast<float*>(ws + P.off_part);
   float* fin = reinterpret_cast<float*>(ws + P.off_fin);
   const dim3 grid(P.slices, P.tiles);
   RON_LAUNCH((bn_bwd_sums_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, y, dy, mean, var, d->eps, part);
   RON_LAUNCH(bn_bwd_final_kernel, dim3(P.cg), dim3(kBnThreads), 0, s, g, part, fin, dbeta, dgamma);
-  if (dx != nullptr) RON_LAUNCH((bn_bwd_dx_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, y, dy, gamma, mean, var, d->eps, fin, dx);
+  if (want_dx) RON_LAUNCH((bn_bwd_dx_kernel<BF16, RELU>), grid, dim3(kBnThreads), 0, s, g, x, y, dy, gamma, mean, var, d->eps, fin, dx);
   RON_HIP_CHECK(ron::launch_error());
   return RON_OK;
 }
 
+// the four (storage type, activation) instantiations behind one call
+template <class PL, class... A>
+int forward_by_type(const ron_bn_desc* d, A... a) {
+  if (d->dtype == RON_DTYPE_BF16) return d->relu ? run_forward<true, true, PL>(d, a...) : run_forward<true, false, PL>(d, a...);
+  return d->relu ? run_forward<false, true, PL>(d, a...) : run_forward<false, false, PL>(d, a...);
+}
+template <class PL, class... A>
+int backward_by_type(const ron_bn_desc* d, A... a) {
+  if (d->dtype == RON_DTYPE_BF16) return d->relu ? run_backward<true, true, PL>(d, a...) : run_backward<true, false, PL>(d, a...);
+  return d->relu ? run_backward<false, true, PL>(d, a...) : run_backward<false, false, PL>(d, a...);
+}
+
+DensePlace dense(const float* p) { return DensePlace{const_cast<float*>(p)}; }
+HaloPlace halo(const TensorView& v) {
+  HaloPlace t = HaloPlace();
+  t.p = static_cast<unsigned short*>(v.base);
+  t.H = v.H; t.W = v.W; t.pad = v.pad; t.cs = v.cstride; t.coff = v.coff;
+  return t;
+}
+
 }  // namespace
+
+int bn_view_plan(const char* what, const ron_bn_desc* d, int64_t* scratch_bytes) {
+  BnPlan P = BnPlan();
+  if (int rc = plan_bn(what, d, &P)) return rc;
+  *scratch_bytes = P.total;
+  return RON_OK;
+}
+
+int bn_view_forward(const ron_bn_desc* d, const TensorView& x, const TensorView& y, const float* gamma, const float* beta, float* mean,
+                    float* var, float* mean_copy, float* var_copy, float* moving_mean, float* moving_var, char* scratch, hipStream_t s) {
+  BnPlan P = BnPlan();
+  if (int rc = plan_bn("batchnorm on views", d, &P)) return rc;
+  if (int rc = forward_by_type<HaloPlace>(d, P, halo(x), gamma, beta, halo(y), mean, var, moving_mean, moving_var, scratch, s)) return rc;
+  if (mean_copy != nullptr || var_copy != nullptr) {
+    RON_LAUNCH(bn_copy_stats_kernel, dim3((d->c / 4 + kBnThreads - 1) / kBnThreads), dim3(kBnThreads), 0, s, d->c / 4, mean, var, mean_copy, var_copy);
+    RON_HIP_CHECK(ron::launch_error());
+  }
+  return RON_OK;
+}
+
+int bn_view_backward(const ron_bn_desc* d, const TensorView& x, const TensorView& y, const TensorView& dy, const float* gamma,
+                     const float* mean, const float* var, const TensorView* dx, float* dgamma, float* dbeta, char* scratch, hipStream_t s) {
+  BnPlan P = BnPlan();
+  if (int rc = plan_bn("batchnorm on views", d, &P)) return rc;
+  return backward_by_type<HaloPlace>(d, P, halo(x), halo(y), halo(dy), gamma, mean, var, dx != nullptr, dx != nullptr ? halo(*dx) : HaloPlace(),
+                                     dgamma, dbeta, scratch, s);
+}
+
 }  // namespace ron
 
 extern "C" int64_t ron_batchnorm_workspace_bytes(const ron_bn_desc* d) {
@@ -467,13 +577,8 @@ extern "C" int ron_batchnorm_train_nhwc(const ron_bn_desc* d, const float* x, co
                 (uintptr_t)moving_mean | (uintptr_t)moving_var) & 15) == 0,
               "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
   if (int rc = check_workspace(what, "ron_batchnorm_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  if (d->dtype == RON_DTYPE_BF16)
-    return d->relu ? run_forward<true, true>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s)
-                   : run_forward<true, false>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s);
-  return d->relu ? run_forward<false, true>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s)
-                 : run_forward<false, false>(d, P, x, gamma, beta, y, mean, var, moving_mean, moving_var, ws, s);
+  return forward_by_type<DensePlace>(d, P, dense(x), gamma, beta, dense(y), mean, var, moving_mean, moving_var,
+                                     static_cast<char*>(workspace), (hipStream_t)stream);
 }
 
 extern "C" int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x, const float* y, const float* dy, const float* gamma,
@@ -490,11 +595,6 @@ extern "C" int ron_batchnorm_backward_nhwc(const ron_bn_desc* d, const float* x,
                 (uintptr_t)dx | (uintptr_t)dgamma | (uintptr_t)dbeta) & 15) == 0,
               "%s: every tensor must be 16-byte aligned (16 bytes per access)", what);
   if (int rc = check_workspace(what, "ron_batchnorm_workspace_bytes", workspace, workspace_bytes, P.total)) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  char* ws = static_cast<char*>(workspace);
-  if (d->dtype == RON_DTYPE_BF16)
-    return d->relu ? run_backward<true, true>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s)
-                   : run_backward<true, false>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s);
-  return d->relu ? run_backward<false, true>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s)
-                 : run_backward<false, false>(d, P, x, y, dy, gamma, mean, var, dx, dgamma, dbeta, ws, s);
+  return backward_by_type<DensePlace>(d, P, dense(x), dense(y), dense(dy), gamma, mean, var, dx != nullptr, dense(dx), dgamma, dbeta,
+                                      static_cast<char*>(workspace), (hipStream_t)stream);
 }

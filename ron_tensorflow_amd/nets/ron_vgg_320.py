@@ -56,6 +56,131 @@ def vgg_body_chain(variant='reducedfc', scope='ron_320_vgg'):
     return layers, names
 
 
+_BN_KEYS = (('gamma', 'gamma'), ('beta', 'beta'), ('moving_mean', 'moving_mean'), ('moving_var', 'moving_variance'))
+
+
+def head_chains(num_anchors, num_classes, layer, top=False, scope='ron_320_vgg', width=512):
+    """One reverse_connection_module_with_pred (nets/ron_vgg_320.py:378-432 of the reference) as the layer lists of ops.head_chain_fn.
+
+    Returns a dict: 'left', 'objness', 'cls', 'reg' are (layers, names) - layers[i] an ops.chain_conv / chain_bn / chain_conv_pair
+    entry, names[i] a dict from the keys of head_chain_forward's `params` ('w', 'bias', 'w2', 'bias2', 'gamma', 'beta',
+    'moving_mean', 'moving_var') to the variable names of weights.variable_shapes, the ones optim.Optimizer knows.  'left_conv'
+    ({'w': name}) is the 2x2 stride-2 convolution in front of the left chain at the top scale (`top`: no right input; the left chain is
+    then its batch normalisation alone) and None elsewhere; 'deconv' ({'w': name, 'bias': name}) the transposed convolution of the right
+    input, None at the top scale.  Every variable of the module appears exactly once.  `width` is 512 in the network."""
+    L = '%s/reverse_module/%s_reverse' % (scope, layer)
+
+    def conv(chain, name, cout, relu, bias):
+        chain[0].append(ops.chain_conv(cout, k=3, relu=relu, bias=bias, name=name))
+        chain[1].append(dict({'w': '%s/weights' % name}, **({'bias': '%s/biases' % name} if bias else {})))
+
+    def bn(chain, name):
+        chain[0].append(ops.chain_bn(relu=True, eps=1e-5, decay=0.997, name=name))          # ron_arg_scope's
+        chain[1].append({key: '%s/BatchNorm/%s' % (name, var) for key, var in _BN_KEYS})
+
+    left, objness, cls, reg = ([], []), ([], []), ([], []), ([], [])
+    if not top:
+        conv(left, L + '_conv_left', width, False, False)
+    bn(left, L + '_conv_left')
+    conv(objness, L + '_objectness', width, False, False)
+    bn(objness, L + '_objectness')
+    conv(objness, L + '_objectness_score', 2 * num_anchors, False, True)
+    for blk in (1, 2):
+        name = '%s_inception%d' % (L, blk)
+        cls[0].append(ops.chain_conv_pair(width, width, relu=False, bias=True, name=name))
+        cls[1].append({'w': name + '/Branch_0/Conv2d_3x3/weights', 'bias': name + '/Branch_0/Conv2d_3x3/biases',
+                       'w2': name + '/Branch_1/Conv2d_1x1/weights', 'bias2': name + '/Branch_1/Conv2d_1x1/biases'})
+        bn(cls, name)
+    conv(cls, L + '_inception2/Conv2d_pred_3x3', num_anchors * num_classes, False, True)
+    conv(reg, L + '/Conv2d_0_3x3', width, False, False)
+    bn(reg, L + '/Conv2d_0_3x3')
+    conv(reg, L + '/Conv2d_1_3x3', 4 * num_anchors, False, True)
+    return {'left': left, 'objness': objness, 'cls': cls, 'reg': reg,
+            'left_conv': {'w': L + '_conv_left/weights'} if top else None,
+            'deconv': None if top else {'w': L + '_deconv_right/weights', 'bias': L + '_deconv_right/biases'}}
+
+
+def _chain_params(names, variables):
+    return [None if n is None else {key: variables[var] for key, var in n.items()} for n in names]
+
+
+def reverse_module_parts(left, right, variables, chains, dtype='bf16'):
+    """The two halves of a module on autograd tensors: (ref_map, branches) where branches(ref) -> (objness, cls, reg) as [N,H,W,C]
+    maps.  `chains`: head_chains(...).  Plain composition: torch.autograd differentiates it as it stands."""
+    if chains['left_conv'] is not None:
+        a = ops.conv2d_k2s2_nhwc_fn(left, variables[chains['left_conv']['w']], None, relu=False, transpose=False, dtype=dtype)
+        ref = ops.head_chain_fn(a, chains['left'][0], _chain_params(chains['left'][1], variables), dtype=dtype)[0]
+    else:
+        a = ops.head_chain_fn(left, chains['left'][0], _chain_params(chains['left'][1], variables), dtype=dtype)[0]
+        up = ops.conv2d_k2s2_nhwc_fn(right, variables[chains['deconv']['w']], variables[chains['deconv']['bias']], relu=True, transpose=True,
+                                     dtype=dtype)
+        ref = torch.relu(a + up)
+
+    def branches(ref_map):
+        return tuple(ops.head_chain_fn(ref_map, chains[k][0], _chain_params(chains[k][1], variables), dtype=dtype)[0] for k in ('objness', 'cls', 'reg'))
+    return ref, branches
+
+
+class _ReverseModuleFn(torch.autograd.Function):
+    """One module with a STATED order for the sum of the gradients that meet at ref_map (see reverse_module_fn)."""
+
+    @staticmethod
+    def forward(ctx, left, right, chains, dtype, names, *tensors):
+        with torch.enable_grad():
+            leaves = [t.detach().requires_grad_(t.is_floating_point() and t.requires_grad) for t in tensors]
+            variables = dict(zip(names, leaves))
+            lin = left.detach().requires_grad_(left.requires_grad)
+            rin = None if right is None else right.detach().requires_grad_(right.requires_grad)
+            ref, branches = reverse_module_parts(lin, rin, variables, chains, dtype)
+            leaf = ref.detach().requires_grad_(True)
+            heads = branches(leaf)
+        ctx.graph = (lin, rin, leaves, ref, leaf, heads)
+        return (ref.detach(),) + tuple(h.detach() for h in heads)
+
+    @staticmethod
+    def backward(ctx, d_ref, d_obj, d_cls, d_reg):
+        if ctx.graph is None:
+            raise RuntimeError('reverse_module_fn: a second backward through the same forward (the module keeps its inner graph for one)')
+        lin, rin, leaves, ref, leaf, heads = ctx.graph
+        ctx.graph = None
+        wanted = [t for t in leaves if t.requires_grad]
+        got = {}
+        # the gradient of ref_map: (((d_ref_map + d_objness) + d_cls) + d_reg), fp32, in this order
+        total = d_ref
+        for head, g in zip(heads, (d_obj, d_cls, d_reg)):
+            grads = torch.autograd.grad([head], [leaf] + wanted, [g], allow_unused=True)
+            total = total + grads[0]
+            got.update({id(t): v for t, v in zip(wanted, grads[1:]) if v is not None})
+        ins = [t for t in (lin, rin) if t is not None and t.requires_grad]
+        if ins + wanted:
+            grads = torch.autograd.grad([ref], ins + wanted, [total], allow_unused=True)
+            got.update({id(t): v for t, v in zip(ins + wanted, grads) if v is not None})
+        return (got.get(id(lin)), None if rin is None else got.get(id(rin)), None, None, None) + tuple(got.get(id(t)) for t in leaves)
+
+
+def reverse_module_fn(left, right, variables, num_anchors, num_classes, layer, dtype='bf16', scope='ron_320_vgg', width=512):
+    """One reverse_connection_module_with_pred in training mode as a torch.autograd.Function built from ops.head_chain_fn (the four
+    chains of head_chains), ops.conv2d_k2s2_nhwc_fn (the transposed convolution of `right`; at the top scale, `right` None, the
+    2x2 stride-2 convolution of `left`) and relu(left + up).  left / right: [N,H,W,C] GPU fp32 maps; `variables`: {variable name:
+    GPU fp32 tensor} with the names of weights.variable_shapes; the moving statistics in it are buffers updated in place.
+
+    Returns (ref_map [N,H,W,width], objness_logits [N,H,W,A,2], cls_pred [N,H,W,A,C], loc_pred [N,H,W,A,4]).
+
+    Four gradients meet at ref_map: its own and those of the three branches.  torch.autograd leaves the order of such a sum open; this
+    function adds them as (((d_ref_map + d_objness) + d_cls) + d_reg) in fp32, in this order, which is what makes its gradients
+    reproducible byte for byte (and testable against the per-operator composition).
+
+    The forward keeps the graph of its parts for ONE backward: a second backward through the same outputs raises (call the function
+    again).  With no input and no variable that requires a gradient the backward computes nothing.  `width` (512 in the network)
+    exists for tests at small sizes; the transposed convolution wants it a multiple of 128."""
+    chains = head_chains(num_anchors, num_classes, layer, top=right is None, scope=scope, width=width)
+    names = [v for key in ('left', 'objness', 'cls', 'reg') for n in chains[key][1] for v in n.values()]
+    names += [v for key in ('left_conv', 'deconv') if chains[key] is not None for v in chains[key].values()]
+    ref, obj, cls, reg = _ReverseModuleFn.apply(left, right, chains, dtype, names, *[variables[n] for n in names])
+    n, h, w = ref.shape[:3]
+    return (ref, obj.reshape(n, h, w, num_anchors, 2), cls.reshape(n, h, w, num_anchors, num_classes), reg.reshape(n, h, w, num_anchors, 4))
+
+
 class _DataFormatScope(object):
     """What `arg_scope(data_format=...)` returns: inside the `with`, the networks it was made for take / return that layout."""
 

@@ -890,6 +890,188 @@ def conv_chain_fn(x, layers, weights, biases, dtype='bf16'):
 
 
 # --------------------------------------------------------------------------- #
+# head chain (ron_head_chain_forward / ron_head_chain_backward): the convolution chain plus training-mode batch normalisation and the
+# two-branch 3x3 | 1x1 convolution, so that every branch of a reverse-connection module is one chain.  `params` is a list with one
+# dict per layer (or None): 'w', 'bias' (conv, pair), 'w2', 'bias2' (pair), 'gamma', 'beta', 'moving_mean', 'moving_var' (bn)
+# --------------------------------------------------------------------------- #
+_HEAD_IN = ('w', 'bias', 'w2', 'bias2', 'gamma', 'beta')                            # what the forward reads and autograd differentiates
+_HEAD_GRAD = {'w': 'dw', 'bias': 'dbias', 'w2': 'dw2', 'bias2': 'dbias2', 'gamma': 'dgamma', 'beta': 'dbeta'}
+
+
+def chain_bn(relu=True, eps=1e-5, decay=0.997, name=None):
+    """One training-mode batch normalisation layer (then ReLU when `relu`) of a head chain's layer list."""
+    return {'kind': 'bn', 'relu': bool(relu), 'eps': float(eps), 'decay': float(decay), 'tap': False, 'name': name}
+
+
+def chain_conv_pair(cout, cout2, relu=False, bias=True, name=None):
+    """One two-branch layer of a head chain's layer list: concat(conv3x3 -> cout channels, conv1x1 -> cout2 channels)."""
+    return {'kind': 'pair', 'cout': int(cout), 'cout2': int(cout2), 'relu': bool(relu), 'bias': bool(bias), 'tap': False, 'name': name}
+
+
+def _head_chain_desc(n, h, w, cin, layers, dtype):
+    d = _lib.HeadChainDesc()
+    d.n, d.h, d.w, d.cin, d.dtype, d.num_layers = int(n), int(h), int(w), int(cin), _lib.DTYPES[dtype], len(layers)
+    if len(layers) > _lib.RON_CHAIN_MAX_LAYERS:
+        raise _lib.RonError('head chain: %d layers, at most %d' % (len(layers), _lib.RON_CHAIN_MAX_LAYERS))
+    for i, l in enumerate(layers):
+        tap = int(bool(l.get('tap', False)))
+        if l['kind'] == 'pool':
+            d.layers[i] = _lib.HeadChainLayer(_lib.RON_CHAIN_POOL2, 0, 0, 0, 0, 0, tap, 0, 0.0, 0.0)
+        elif l['kind'] == 'conv':
+            d.layers[i] = _lib.HeadChainLayer(_lib.RON_CHAIN_CONV, l['k'], l.get('dilation', 1), l['cout'], int(l.get('relu', True)),
+                                              int(l.get('bias', True)), tap, 0, 0.0, 0.0)
+        elif l['kind'] == 'pair':
+            d.layers[i] = _lib.HeadChainLayer(_lib.RON_CHAIN_CONV_PAIR, 0, 0, l['cout'], int(l.get('relu', False)), int(l.get('bias', True)),
+                                              tap, l['cout2'], 0.0, 0.0)
+        elif l['kind'] == 'bn':
+            d.layers[i] = _lib.HeadChainLayer(_lib.RON_CHAIN_BN, 0, 0, 0, int(l.get('relu', True)), 0, tap, 0, float(l.get('eps', 1e-5)),
+                                              float(l.get('decay', 0.997)))
+        else:
+            raise _lib.RonError('head chain: layer %d: unknown kind %r' % (i, l['kind']))
+    return d
+
+
+def head_chain_shapes(n, h, w, cin, layers, dtype='bf16'):
+    """The output shape (n, h, w, c) of every layer of the head chain (ron_head_chain_shape); raises on a refused descriptor."""
+    d = _head_chain_desc(n, h, w, cin, layers, dtype)
+    out = []
+    for i in range(len(layers)):
+        s = (C.c_int64 * 4)()
+        check(lib().ron_head_chain_shape(C.byref(d), i, s))
+        out.append(tuple(int(v) for v in s))
+    return out
+
+
+def head_chain_workspace_bytes(n, h, w, cin, layers, dtype='bf16'):
+    """Bytes of the workspace head_chain_forward and head_chain_backward share for this chain (host arithmetic; raises on a refused
+    descriptor)."""
+    return _desc_workspace_bytes('head_chain', _head_chain_desc(n, h, w, cin, layers, dtype))
+
+
+def _head_ptrs(L, **columns):
+    """The host array of ron_head_chain_ptrs: columns[name] is a list with one tensor (or None) per layer."""
+    table = (_lib.HeadChainPtrs * L)()
+    for name, tensors in columns.items():
+        assert len(tensors) == L, '%s: %d entries for %d layers' % (name, len(tensors), L)
+        for i, t in enumerate(tensors):
+            if t is not None:
+                setattr(table[i], name, t.data_ptr())
+    return table
+
+
+def _head_column(params, name):
+    return [None if p is None else p.get(name) for p in params]
+
+
+def head_chain_forward(x, layers, params, dtype='bf16', workspace=None):
+    """The head chain's forward: x [N,H,W,Cin] GPU fp32, `layers` a list of chain_conv / chain_pool / chain_bn / chain_conv_pair
+    entries, `params` one dict of GPU fp32 tensors per layer (None for pools).  A bn layer's 'moving_mean' / 'moving_var' (both or
+    neither) are updated IN PLACE.  Returns (y, taps, stats, workspace): taps[i] the fp32 output of a tapped convolution, stats[i] the
+    batch (mean, var) of a bn layer (None elsewhere), and the workspace that now holds what head_chain_backward reads.  ONE
+    ron_head_chain_forward call on the current stream, no synchronisation."""
+    assert x.dim() == 4 and len(params) == len(layers)
+    x = x.contiguous()
+    L = len(layers)
+    cols = {name: _head_column(params, name) for name in _HEAD_IN + ('moving_mean', 'moving_var')}
+    _chain_check('head_chain_forward', [x] + [t for col in cols.values() for t in col])
+    n, h, w, cin = x.shape
+    d = _head_chain_desc(n, h, w, cin, layers, dtype)
+    nbytes = _desc_workspace_bytes('head_chain', d)
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device) if workspace is None else workspace
+    shapes = head_chain_shapes(n, h, w, cin, layers, dtype)
+    new = lambda shape: torch.empty(shape, dtype=torch.float32, device=x.device)
+    taps = [new(shapes[i]) if l.get('tap') else None for i, l in enumerate(layers)]
+    stats = [(new((shapes[i][3],)), new((shapes[i][3],))) if l['kind'] == 'bn' else None for i, l in enumerate(layers)]
+    y = new(shapes[-1])
+    table = _head_ptrs(L, tap=taps, mean=[None if s is None else s[0] for s in stats], var=[None if s is None else s[1] for s in stats], **cols)
+    check(lib().ron_head_chain_forward(C.byref(d), ptr(x), table, ptr(y), ptr(ws), int(ws.numel()), current_stream()))
+    return y, taps, stats, ws
+
+
+def head_chain_backward(x_shape, layers, params, dy, dtaps, workspace, dtype='bf16', need_dx=True, need=None):
+    """The head chain's backward from the workspace head_chain_forward filled.  `need`: per layer the names of the parameters whose
+    gradients are computed (default: every parameter the layer has in `params` among w, bias, w2, bias2, gamma, beta).  Returns
+    (dx, grads): grads[i] a dict {'dw': ..., 'dbias': ..., 'dw2': ..., 'dbias2': ..., 'dgamma': ..., 'dbeta': ...} with the requested
+    entries (None for a layer without parameters).  ONE ron_head_chain_backward call on the current stream; it may be repeated and
+    gives the same bytes."""
+    n, h, w, cin = x_shape
+    L = len(layers)
+    assert len(params) == L
+    dy = dy.contiguous()
+    dtaps = [None] * L if dtaps is None else [None if t is None else t.contiguous() for t in dtaps]
+    cols = {name: _head_column(params, name) for name in ('w', 'w2', 'gamma')}
+    _chain_check('head_chain_backward', [dy] + dtaps + [t for col in cols.values() for t in col])
+    d = _head_chain_desc(n, h, w, cin, layers, dtype)
+    shapes = head_chain_shapes(n, h, w, cin, layers, dtype)
+    assert tuple(dy.shape) == shapes[-1], 'dy %s, the chain ends in %s' % (tuple(dy.shape), shapes[-1])
+    for i, t in enumerate(dtaps):
+        assert t is None or (layers[i].get('tap') and tuple(t.shape) == shapes[i]), 'dtaps[%d]' % i
+    dev = dy.device
+    grads = []
+    for i in range(L):
+        have = [name for name in _HEAD_IN if params[i] is not None and params[i].get(name) is not None]
+        want = have if need is None else [name for name in have if name in (need[i] or ())]
+        grads.append({_HEAD_GRAD[name]: torch.empty(tuple(params[i][name].shape), dtype=torch.float32, device=dev) for name in want} or None)
+    dx = torch.empty((n, h, w, cin), dtype=torch.float32, device=dev) if need_dx else None
+    out_cols = {g: [None if gr is None else gr.get(g) for gr in grads] for g in _HEAD_GRAD.values()}
+    table = _head_ptrs(L, dtap=dtaps, **cols, **out_cols)
+    check(lib().ron_head_chain_backward(C.byref(d), ptr(dy), table, ptr(dx), ptr(workspace), int(workspace.numel()), current_stream()))
+    return dx, grads
+
+
+class _HeadChainFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, layers, dtype, buffers, slots, *flat):
+        L = len(layers)
+        params = [None] * L
+        for (i, name), t in zip(slots, flat):
+            params[i] = params[i] or {}
+            params[i][name] = t.detach().contiguous()
+        for i, b in enumerate(buffers):
+            if b is not None:
+                params[i] = dict(params[i] or {}, moving_mean=b[0], moving_var=b[1])
+        y, taps, _, ws = head_chain_forward(x.detach(), layers, params, dtype=dtype)
+        ctx.save_for_backward(*flat)
+        ctx.cfg = (tuple(x.shape), layers, dtype, slots, ws)
+        ctx.tapped = [i for i, l in enumerate(layers) if l.get('tap')]
+        ctx.y_shape = tuple(y.shape)
+        ctx.set_materialize_grads(False)        # an output nobody used has no gradient: its dtap stays NULL
+        return (y,) + tuple(taps[i] for i in ctx.tapped)
+
+    @staticmethod
+    def backward(ctx, dy, *dtap_list):
+        x_shape, layers, dtype, slots, ws = ctx.cfg
+        L = len(layers)
+        params, need = [None] * L, [set() for _ in range(L)]
+        for k, ((i, name), t) in enumerate(zip(slots, ctx.saved_tensors)):
+            params[i] = params[i] or {}
+            params[i][name] = t.detach().contiguous()
+            if ctx.needs_input_grad[5 + k]:
+                need[i].add(name)
+        dtaps = [None] * L
+        for i, g in zip(ctx.tapped, dtap_list):
+            dtaps[i] = g
+        if dy is None:          # only the taps carry gradients
+            dy = torch.zeros(ctx.y_shape, dtype=torch.float32, device=ws.device)
+        dx, grads = head_chain_backward(x_shape, layers, params, dy, dtaps, ws, dtype=dtype, need_dx=bool(ctx.needs_input_grad[0]), need=need)
+        flat = tuple(None if grads[i] is None else grads[i].get(_HEAD_GRAD[name]) for i, name in slots)
+        return (dx, None, None, None, None) + flat
+
+
+def head_chain_fn(x, layers, params, dtype='bf16'):
+    """The head chain as a torch.autograd.Function: returns (y, *taps), the taps in layer order.  `params` as in head_chain_forward;
+    w, bias, w2, bias2, gamma, beta get gradients where autograd asks for them, 'moving_mean' / 'moving_var' are plain buffers that
+    the forward updates in place and that get none.  The forward is ONE ron_head_chain_forward call into a workspace of its own, the
+    backward ONE ron_head_chain_backward call reading it.  The results have the bytes of conv2d_nhwc_fn, batchnorm_nhwc_fn,
+    maxpool2x2_nhwc_fn (and torch.cat for a pair) chained layer by layer."""
+    L = len(layers)
+    assert len(params) == L
+    slots = [(i, name) for i in range(L) for name in _HEAD_IN if params[i] is not None and params[i].get(name) is not None]
+    buffers = [None if p is None or p.get('moving_mean') is None else (p['moving_mean'], p['moving_var']) for p in params]
+    return _HeadChainFn.apply(x, layers, dtype, buffers, slots, *[params[i][name] for i, name in slots])
+
+
+# --------------------------------------------------------------------------- #
 # backward of the 2x2 pool and of the 2x2 stride-2 convolutions (ron_maxpool2x2_backward_nhwc, ron_conv2d_k2s2_backward_nhwc):
 # real entry points like the convolution backward - they enqueue on the current stream and never synchronise
 # --------------------------------------------------------------------------- #

@@ -286,6 +286,121 @@ static int conv_chain_arguments() {
   return 0;
 }
 
+// ron_head_chain_forward / ron_head_chain_backward in the dry run: the cases of tests/head_chain_cases.py and the four chains of each
+// RON-320 scale (nets.ron_vgg_320.head_chains: 40^2, 20^2, 10^2, 5^2; 21 classes) at batch 1 and 32, with full and with NULL output
+// sets, and the refusals the two new layer kinds add.
+static int head_chain_arguments() {
+  struct Layer { int kind, k, cout, cout2, relu, bias; };
+  struct Chain { int n, h, w, cin; std::vector<Layer> layers; };
+  const Layer P = {RON_CHAIN_POOL2, 0, 0, 0, 0, 0};
+  auto cv = [](int k, int cout, int relu = 1, int bias = 1) { return Layer{RON_CHAIN_CONV, k, cout, 0, relu, bias}; };
+  auto bn = [](int relu = 1) { return Layer{RON_CHAIN_BN, 0, 0, 0, relu, 0}; };
+  auto pr = [](int cout, int cout2, int relu = 0) { return Layer{RON_CHAIN_CONV_PAIR, 0, cout, cout2, relu, 1}; };
+  std::vector<Chain> chains = {
+      {2, 6, 10, 64, {cv(3, 64, 0, 0), bn(), cv(3, 12, 0)}},
+      {2, 6, 10, 64, {pr(64, 64), bn(), pr(128, 64), bn(), cv(3, 18, 0)}},
+      {3, 5, 7, 64, {cv(3, 64, 0, 0), bn()}},
+      {2, 4, 4, 128, {bn(0), cv(1, 64)}},
+      {2, 9, 6, 64, {cv(3, 64), P, bn(), P, bn(0)}},
+      {1, 4, 4, 64, {cv(3, 64), pr(64, 64, 1)}},
+      {1, 3, 3, 64, {cv(1, 512, 0, 0), bn(), cv(1, 8)}},
+      {1, 1, 1, 8, {bn()}},
+      {1, 1, 1027, 8, {bn()}},
+      {2, 40, 40, 512, {bn()}}};
+  const int anchors = 10, classes = 21;
+  for (int n : {1, 32}) {
+    for (int s = 0; s < 4; ++s) {
+      const int hw = 5 << s, left_c = s < 2 ? 1024 : 512;
+      if (s == 0) chains.push_back({n, hw, hw, 512, {bn()}});                               // the top scale: the 2x2 convolution is in front
+      else chains.push_back({n, hw, hw, left_c, {cv(3, 512, 0, 0), bn()}});
+      chains.push_back({n, hw, hw, 512, {cv(3, 512, 0, 0), bn(), cv(3, 2 * anchors, 0)}});
+      chains.push_back({n, hw, hw, 512, {pr(512, 512), bn(), pr(512, 512), bn(), cv(3, anchors * classes, 0)}});
+      chains.push_back({n, hw, hw, 512, {cv(3, 512, 0, 0), bn(), cv(3, 4 * anchors, 0)}});
+    }
+  }
+  float* const f = reinterpret_cast<float*>(uintptr_t(1) << 30);          // fake device addresses, 256-byte aligned
+  void* const ws = reinterpret_cast<void*>(uintptr_t(1) << 40);
+  for (const Chain& c : chains) {
+    for (int dtype : {(int)RON_DTYPE_BF16, (int)RON_DTYPE_F16}) {
+      ron_head_chain_desc d;
+      memset(&d, 0, sizeof d);
+      d.n = c.n; d.h = c.h; d.w = c.w; d.cin = c.cin; d.dtype = dtype; d.num_layers = (int)c.layers.size();
+      ron_head_chain_ptrs all[RON_CHAIN_MAX_LAYERS], some[RON_CHAIN_MAX_LAYERS];
+      int first_bn = -1, first_pair = -1;
+      for (int i = 0; i < d.num_layers; ++i) {
+        const Layer& l = c.layers[i];
+        ron_head_chain_layer& t = d.layers[i];
+        t.kind = l.kind; t.k = l.k; t.dilation = 1; t.cout = l.cout; t.cout2 = l.cout2; t.relu = l.relu; t.has_bias = l.bias;
+        t.eps = 1e-5f; t.decay = 0.997f;
+        float* const p = f + 64 * i;
+        all[i] = ron_head_chain_ptrs{p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p, p};
+        some[i] = ron_head_chain_ptrs{p, p, p, p, p, p, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                                      nullptr, nullptr};
+        if (l.kind == RON_CHAIN_BN && first_bn < 0) first_bn = i;
+        if (l.kind == RON_CHAIN_CONV_PAIR && first_pair < 0) first_pair = i;
+      }
+      const int64_t bytes = ron_head_chain_workspace_bytes(&d);
+      if (bytes <= 0 || bytes % 256 != 0) return 1;
+      int64_t shape[4];
+      CHECK(ron_head_chain_shape(&d, d.num_layers - 1, shape));
+      if (shape[0] != c.n || ron_head_chain_shape(&d, d.num_layers, shape) != RON_ERR_INVALID) return 1;
+      CHECK(ron_head_chain_forward(&d, f, all, f, ws, bytes, nullptr));
+      CHECK(ron_head_chain_forward(&d, f, some, f, ws, bytes, nullptr));          // no moving statistics, no mean / var outputs
+      CHECK(ron_head_chain_backward(&d, f, all, f, ws, bytes, nullptr));
+      CHECK(ron_head_chain_backward(&d, f, all, nullptr, ws, bytes, nullptr));
+      CHECK(ron_head_chain_backward(&d, f, some, f, ws, bytes, nullptr));          // dx alone
+      CHECK(ron_head_chain_backward(&d, f, some, nullptr, ws, bytes, nullptr));    // nothing asked for: nothing runs
+      if (ron_head_chain_forward(&d, nullptr, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_head_chain_forward(&d, f, nullptr, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_head_chain_forward(&d, f, all, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_head_chain_backward(&d, f + 1, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+      if (ron_head_chain_backward(&d, f, all, f, ws, bytes - 1, nullptr) != RON_ERR_INVALID) return 1;
+      if (first_bn >= 0) {
+        ron_head_chain_ptrs keep = all[first_bn];
+        all[first_bn].moving_var = nullptr;
+        if (ron_head_chain_forward(&d, f, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        all[first_bn] = keep; all[first_bn].gamma = f + 1;
+        if (ron_head_chain_forward(&d, f, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_head_chain_backward(&d, f, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        all[first_bn] = keep;
+        ron_head_chain_desc bad = d;
+        bad.layers[first_bn].tap = 1;
+        if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.layers[first_bn].eps = -1.f;
+        if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.layers[first_bn].decay = 1.5f;
+        if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+      }
+      if (first_pair >= 0) {
+        ron_head_chain_ptrs keep = all[first_pair];
+        all[first_pair].w2 = nullptr;
+        if (ron_head_chain_forward(&d, f, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        if (ron_head_chain_backward(&d, f, all, f, ws, bytes, nullptr) != RON_ERR_INVALID) return 1;
+        all[first_pair] = keep;
+        ron_head_chain_desc bad = d;
+        bad.layers[first_pair].tap = 1;
+        if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+        bad = d; bad.layers[first_pair].cout2 = 96;
+        if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+        if (first_pair > 0 && c.layers[first_pair - 1].kind == RON_CHAIN_CONV) {
+          bad = d; bad.layers[first_pair - 1].tap = 1;
+          if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+        }
+      }
+      ron_head_chain_desc bad = d;
+      bad.num_layers = 0;
+      if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.layers[0].kind = 4;
+      if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.cin = 12;
+      if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+      bad = d; bad.n = 1 << 26;          // an activation of 2 GiB or more, or a batch normalisation over more than 2^24 rows
+      if (ron_head_chain_workspace_bytes(&bad) != -1) return 1;
+    }
+  }
+  return 0;
+}
+
 // ron_conv2d_forward_nhwc in the dry run: the descriptor checks, the ConvLaunch of every route (plain, 7 x 7, the stem with and without
 // its kernel, 2 x 2 stride 2, transposed, the resident-weight images), the workspace and the refusals, over the case table of
 // tests/conv_fwd_cases.py plus the layer shapes of tools/conv_forward_time.py; and the 7 x 7 filter through ron_conv2d_backward_nhwc.
@@ -887,6 +1002,15 @@ int main(int argc, char** argv) {
     return 2;
   }
   const bool quick = argc > 1 && strcmp(argv[1], "--quick") == 0;
+  // --head-chain: the head chain's pass alone (it is part of the full sweep; --quick leaves it out, its sections being pinned one by one)
+  if (argc > 1 && strcmp(argv[1], "--head-chain") == 0) {
+    if (head_chain_arguments()) {
+      fprintf(stderr, "plan_sweep: ron_head_chain_forward / ron_head_chain_backward planning / argument handling: %s\n", ron_last_error());
+      return 1;
+    }
+    printf("plan_sweep: 0 contexts planned, no sanitizer report\n");
+    return 0;
+  }
   if (const char* path = getenv("RON_PLAN_TRACE")) {
     FILE* f = fopen(path, "w");           // a fresh file; the library appends to it from its first skipped launch on
     if (f != nullptr) fclose(f);
@@ -989,6 +1113,13 @@ int main(int argc, char** argv) {
   if (conv_chain_arguments()) {
     fprintf(stderr, "plan_sweep: ron_conv_chain_forward / ron_conv_chain_backward planning / argument handling: %s\n", ron_last_error());
     return 1;
+  }
+  if (!quick) {
+    trace_note("pass head_chain_arguments");
+    if (head_chain_arguments()) {
+      fprintf(stderr, "plan_sweep: ron_head_chain_forward / ron_head_chain_backward planning / argument handling: %s\n", ron_last_error());
+      return 1;
+    }
   }
   if (g_trace != nullptr) fclose(g_trace);
   printf("plan_sweep: %d contexts planned, no sanitizer report\n", runs);
